@@ -11,6 +11,7 @@ PSNR/SSIM bookkeeping is excluded.  Per-GPU work is fixed
 reference's train.py semantics: global batch = batch_size x replicas).
 
     python bench.py --mode fit [--config cfg2|cfg4]     what NeRF.fit delivers (loader -> train_step with metrics -> monitor), see bench_fit
+    python bench.py ... --dump-outputs DIR               also writes what the last timed step computed to DIR/<name>.npy (dump_outputs)
 
 One JSON line is printed by rank 0; see the task contract for the fields.  `roofline` is measured live with HIP events
 around the dominant kernel (knerf_profile_*), `cpu_baseline` times the op-for-op torch-CPU restatement of the reference
@@ -244,6 +245,8 @@ def bench_render(args, world, rank, wh, chunks, desc, backend="nccl"):
     sync(world)
     elapsed = max_over_ranks(time.perf_counter() - t0, world)
     assert len(frames_out) == n_frames
+    if args.dump_outputs and rank == 0:          # the last timed frame as the host received it
+        dump_outputs(args.dump_outputs, {"fine_image": frames_out[-1][0], "fine_depth": frames_out[-1][1]})
     fps = world * n_frames / elapsed
     rs = fps * wh * wh * 256
     roofline = None
@@ -330,6 +333,25 @@ def provenance():
             "git_head": git_head(), "git_head_at_build": info["git_head_at_build"], "bench_py_sha16": file_sha16(os.path.abspath(__file__))}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs DIR` (rank 0, after the timed region): what the timed path computed in its last step -- the arrays its caller
+    receives -- as DIR/<name>.npy in float32 / float64, so that two builds run with the same arguments (same seeds, same inputs) can be
+    compared output for output.  Every output of the bench's workloads fits the 64 MB budget whole: nothing is sampled."""
+    out = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        out[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def write_synthetic_dataset(root, wh, n=(100, 4, 4)):
     """nerf_synthetic-layout directory (transforms_{train,val,test}.json + RGBA PNGs, reference loader.py:55-113) with procedural
     images: 100 training views like the real scenes; the pixel content is irrelevant to throughput"""
@@ -400,8 +422,11 @@ def bench_fit(args, world, rank, wh, batch, chunks, desc, backend):
     skip_default = bool(nerf._ctx.get_option("skip_dead_tiles"))
     nerf._ctx.set_option("skip_dead_tiles", 0)
     epochs = 1 + args.epochs
-    nerf.fit(train, epochs=epochs, validation_data=val, callbacks=[Clock(), monitor], verbose=0)
+    history = nerf.fit(train, epochs=epochs, validation_data=val, callbacks=[Clock(), monitor], verbose=0)
     torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:          # what fit hands back (the per-epoch logs) and the weights it leaves behind
+        dump_outputs(args.dump_outputs, {**{"history_" + k: np.asarray(v, np.float64) for k, v in history.history.items()},
+                                         "coarse_weights": nerf.coarse.get_flat_weights(), "fine_weights": nerf.fine.get_flat_weights()})
     t = {k: [m[1] for m in marks if m[0] == k] for k in ("begin", "train_end", "end")}
     steps = len(train)
     loop = sum(t["train_end"][e] - t["begin"][e] for e in range(1, epochs))
@@ -526,7 +551,7 @@ def allreduce_selftest(nerf, world, backend, n=20):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (cfg5: frames); --mode fit times --epochs whole epochs instead")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--ray-chunks", type=int, default=None, help="override the configuration's ray_chunks (sensitivity sweeps; the line's workload says so)")
@@ -542,7 +567,12 @@ def main():
     ap.add_argument("--check-replicas", type=int, default=None, help="after the timed region: exact weight checksum of every rank reduced "
                     "with MAX and MIN; `replica_drift` (must be 0.0) goes on the line.  Default: on for N > 1 (two one-word collectives, "
                     "outside every timed region), off for N = 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed region: write what the last timed step computed "
+                    "(train step: both losses and both nets' weights after Adam; cfg5: the last frame's fine image and depth; --mode fit: "
+                    "the per-epoch logs and the weights) to DIR/<name>.npy, float32 / float64, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     from keras_nerf_amd import parallel
     if args.check_replicas is None:
         args.check_replicas = int(args.gpus > 1 or parallel.single_rank_rehearsal())
@@ -623,9 +653,13 @@ def run(args, world, rank, device_index, backend):
         nerf._allreduce_events = []            # HIP events on the compute stream around the gradient all-reduce of every timed step
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        nerf.train_step(data, with_metrics=False)
+        logs = nerf.train_step(data, with_metrics=False)
     sync(world)
     local_elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # now, before any further step: the losses live in a device buffer the next step overwrites
+        dump_outputs(args.dump_outputs, {"coarse_loss": logs["coarse_loss"], "fine_loss": logs["fine_loss"],
+                                         "coarse_weights": nerf.coarse.get_flat_weights(), "fine_weights": nerf.fine.get_flat_weights()})
     elapsed = max_over_ranks(local_elapsed, world)
     value = world * n_rays * samples_per_ray * args.steps / elapsed
     comm = {}

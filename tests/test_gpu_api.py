@@ -533,11 +533,13 @@ def _bench(args, env_extra, timeout=420):
                           env=dict(base, **env_extra))
 
 
-def test_bench_line_of_the_references_own_command_line_and_of_small_chunks():
+def test_bench_line_of_the_references_own_command_line_and_of_small_chunks(tmp_path):
     """`bench.py --config ref1` = train_single.py:16-17 (--img_wh 128 --ray_chunks 2048, batch 1), the command line the reference's
     comment quotes 3 s per step for: vs_baseline is filled on such lines only, against that number; the single-process line's
     metric time is small and positive.  With --ray-chunks 256 the 64 chunks of a step run as four 4,096-ray sets of launches
-    (option merge_chunk_rays): the dominant kernel's launch count over the two profiled steps says so."""
+    (option merge_chunk_rays): the dominant kernel's launch count over the two profiled steps says so.  `--dump-outputs`: the last
+    timed step's losses and weights as float32 .npy files, bit-identical between two runs with the same arguments in deterministic
+    mode (same seeded inputs; the default mode differs only by the order of atomic sums)."""
     import json
     r = _bench(["--config", "ref1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], {})
     assert r.returncode == 0, r.stderr[-3000:]
@@ -556,6 +558,20 @@ def test_bench_line_of_the_references_own_command_line_and_of_small_chunks():
     assert r.returncode == 0, r.stderr[-3000:]
     head = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
     assert head["vs_baseline"] is None and "baseline" not in head        # nothing is published for the headline configuration
+    n_params = sum(p.size for p in O.init_params(O.NerfConfig(), 0))
+    dumps = []
+    for k in range(2):
+        r = _bench(["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-profile", "--deterministic", "1",
+                    "--dump-outputs", str(tmp_path / f"run{k}")], {})
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / f"run{k}")) == ["coarse_loss.npy", "coarse_weights.npy", "fine_loss.npy", "fine_weights.npy"]
+        dumps.append({f[:-4]: np.load(tmp_path / f"run{k}" / f) for f in os.listdir(tmp_path / f"run{k}")})
+    for name, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.isfinite(a).all() and a.tobytes() == dumps[1][name].tobytes(), name
+    assert dumps[0]["coarse_weights"].shape == dumps[0]["fine_weights"].shape == (n_params,)
+    assert 0 < float(dumps[0]["coarse_loss"]) < 1 and 0 < float(dumps[0]["fine_loss"]) < 1
 
 
 def test_one_rank_rccl_rehearsal_of_the_multi_gpu_bench_path():
