@@ -216,6 +216,30 @@ int knerf_inverse_cdf(void* stream, const float* mid_points, const float* weight
 int knerf_profile_enable(knerf_ctx* ctx, int on);
 int knerf_profile_read(knerf_ctx* ctx, double* total_ms, int64_t* launches, int n);
 
+/* ---- The trained field and its surface.  Extension, no reference counterpart (the original NeRF release's mesh-extraction
+ * notebook evaluates the fine network on a dense grid; the reference ships none of this). ---- */
+/* knerf_query_points -- extension, no reference counterpart.  The MLP `net` at n points: xyz [n,3]; dirs NULL (zero direction),
+ * one shared [3] (dir_per_point 0) or [n,3] (dir_per_point 1).  Outputs (any may be NULL, not all): raw [n,4] = (rgb after sigmoid,
+ * sigma after relu), sigma [n], rgb [n,3].  Fused shapes run one fused kernel (csrc/query.hip: the render path's encoding, trunk
+ * and head, bit for bit); other shapes the positional-encoding op and the general-shape MLP in chunks of about 1 GB of workspace. */
+int knerf_query_points(knerf_ctx* ctx, void* stream, int net, const float* xyz, const float* dirs, int dir_per_point, uint64_t n,
+                       float* raw, float* sigma, float* rgb);
+/* knerf_query_grid -- extension, no reference counterpart.  The same at every point of a [R0,R1,R2] grid (C order, z fastest;
+ * n = R0 R1 R2): point (i,j,k) lies at lo + idx * step per axis, step = (hi - lo) / (R - 1) in fp32, the coordinate computed as
+ * __fadd_rn(lo, __fmul_rn((float)idx, step)).  resolution, lo, hi: HOST [3] (R >= 2, hi > lo); dir: device [3] or NULL. */
+int knerf_query_grid(knerf_ctx* ctx, void* stream, int net, const int32_t* resolution, const float* lo, const float* hi,
+                     const float* dir, float* raw, float* sigma, float* rgb);
+/* knerf_marching_cubes -- extension, no reference counterpart.  Context-free.  Iso-surface {sigma = threshold} of a device fp32 grid
+ * [rx,ry,rz] placed as in knerf_query_grid (lo, hi HOST [3]); inside means sigma > threshold.  Indexed mesh: one vertex per crossed
+ * grid edge, ordered by edge id (3 * point + axis); faces by cube, then table order (csrc/mesh_table.h); wound so that normals point
+ * outward (toward lower density); normals = -grad sigma (central differences, one-sided at the border) interpolated along the edge,
+ * normalised.  Three calls on one caller workspace:
+ *   1. workspace NULL: *workspace_bytes = the size needed (rx ry rz <= 2^28);
+ *   2. vertices, faces, normals all NULL: classification and scans; counts[0] = V, counts[1] = F (host; synchronises `stream`);
+ *   3. the same workspace, grid and threshold: writes vertices [V,3], faces [F,3] (int32), normals [V,3] (each may be NULL). */
+int knerf_marching_cubes(void* stream, const float* grid, int rx, int ry, int rz, const float* lo, const float* hi, float threshold,
+                         void* workspace, size_t* workspace_bytes, int64_t* counts, float* vertices, int32_t* faces, float* normals);
+
 /* Diagnostics (layout tables, workspace views, hardware-fact and bandwidth probes) are NOT part of this library: they are
  * declared in include/knerf_debug.h and built into libknerf_probe.so for tests/ and tools/ only. */
 

@@ -64,6 +64,10 @@ SIGNATURES = {
     "knerf_inverse_cdf": (C.c_int, [_P, _F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F]),
     "knerf_profile_enable": (C.c_int, [_P, C.c_int]),
     "knerf_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_int]),
+    "knerf_query_points": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_uint64, _P, _P, _P]),
+    "knerf_query_grid": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, _P]),
+    "knerf_marching_cubes": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _P,
+                                       C.POINTER(C.c_size_t), C.POINTER(C.c_int64), _P, _P, _P]),
 }
 
 _lib = None

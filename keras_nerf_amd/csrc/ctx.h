@@ -86,6 +86,8 @@ struct knerf_ctx {
     knerf::gen::Workspace call_ws;
     knerf::gen::NetDev call_net;
     float* call_raw = nullptr;
+    // knerf_query_points / knerf_query_grid on the general-shape route: per-chunk points, directions, encodings and raw (grow-only)
+    float* query_tmp = nullptr; size_t query_tmp_bytes = 0;
     // run-time options (knerf_set_option)
     bool deterministic = false;         // per-workgroup partial sums + ordered second pass instead of fp32 atomics (wgrad, loss)
     bool skip_dead = true;              // dgrad / wgrad skip 32-sample tiles whose dL/d(rgb, sigma) is exactly zero (exact; +0.3 % when nothing is dead)

@@ -15,6 +15,7 @@
 #include "kernels.h"
 #include "generic.h"
 #include "layout.h"
+#include "query.h"
 
 using namespace knerf;
 
@@ -468,6 +469,88 @@ int merge_factor(int limit_rays, int ray_chunks, int n_chunks) {
 
 }  // namespace
 
+namespace {
+
+// knerf_mlp_call's general-shape plan, packed weights and workspace (grow-only) for n rows; also the general-shape route of the
+// queries (query_general below)
+int ensure_call(knerf_ctx* ctx, long long n, hipStream_t s) {
+    if (!ctx->call_plan_ok) {
+        const knerf_config& c = ctx->cfg;
+        ctx->call_plan = ctx->mlp_only ? gen::build_plan_widths(c.n_layers, c.dense_units, c.skip_layer, c.pos_emb_xyz, c.pos_emb_dir)
+                                       : gen::build_plan(c.n_layers, c.dense_units, c.skip_layer, c.pos_emb_xyz, c.pos_emb_dir);
+        HIPCHK(hipMalloc(&ctx->call_net.packed, ctx->call_plan.packed_elems * sizeof(unsigned short)));
+        HIPCHK(hipMalloc(&ctx->call_net.head, gen::head_floats(ctx->call_plan) * sizeof(float)));
+        ctx->call_plan_ok = true;
+    }
+    const gen::Plan& p = ctx->call_plan;
+    const size_t mp = gen::padded_rows(n);
+    gen::Workspace& w = ctx->call_ws;
+    if (mp > w.mp) {
+        HIPCHK(hipStreamSynchronize(s));
+        free_dev(w.act); free_dev(w.zs); free_dev(w.zc); free_dev(ctx->call_raw);
+        w.mp = 0;
+        const size_t ab = p.act_elems_per_row * mp * sizeof(unsigned short);
+        HIPCHK(hipMalloc(&w.act, ab));
+        HIPCHK(hipMemsetAsync(w.act, 0, ab, s));        // on the stream the consuming kernels run on
+        HIPCHK(hipMalloc(&w.zs, mp * 32 * sizeof(float)));
+        HIPCHK(hipMalloc(&w.zc, mp * 32 * sizeof(float)));
+        w.mp = mp;
+    }
+    return KNERF_OK;
+}
+
+
+// The query entry points on a shape the fused kernels do not cover (or under KNERF_FLAG_FORCE_GENERIC): points and directions of a
+// chunk (query.hip gather), the positional-encoding op, knerf_mlp_call's general-shape forward, raw -> the caller's outputs (query.hip
+// scatter).  Chunks are sized so that the workspaces stay near 1 GB.
+int query_general(knerf_ctx* ctx, hipStream_t s, int net, const QueryArgs& q0) {
+    if (int r = ensure_call(ctx, 1, s)) return r;
+    const gen::Plan& p = ctx->call_plan;
+    const size_t row_floats = 6 + (size_t)p.xyz_dim + (size_t)p.dir_dim + 4;
+    const size_t row_bytes = p.act_elems_per_row * sizeof(unsigned short) + 64 * sizeof(float) + row_floats * sizeof(float);
+    long long chunk = (long long)(((size_t)1 << 30) / row_bytes) / 1024 * 1024;
+    if (chunk < 1024) chunk = 1024;
+    if (chunk > q0.n) chunk = q0.n;
+    if (int r = ensure_call(ctx, chunk, s)) return r;
+    const size_t tmp = (size_t)chunk * row_floats * sizeof(float);
+    if (tmp > ctx->query_tmp_bytes) {
+        HIPCHK(hipStreamSynchronize(s));
+        free_dev(ctx->query_tmp); ctx->query_tmp_bytes = 0;
+        HIPCHK(hipMalloc(&ctx->query_tmp, tmp));
+        ctx->query_tmp_bytes = tmp;
+    }
+    float* xyz = ctx->query_tmp;
+    float* dir = xyz + 3 * chunk;
+    float* xenc = dir + 3 * chunk;
+    float* denc = xenc + (size_t)p.xyz_dim * chunk;
+    float* raw = denc + (size_t)p.dir_dim * chunk;
+    HIPCHK(gen::pack_weights(p, ctx->net[net].w, ctx->call_net, s));       // the weights may have changed since the last call
+    for (long long off = 0; off < q0.n; off += chunk) {
+        const long long m = q0.n - off < chunk ? q0.n - off : chunk;
+        QueryArgs q = q0;
+        q.offset = off;
+        HIPCHK(launch_query_gather(q, m, xyz, dir, s));
+        if (knerf_positional_encoding(s, xyz, m, ctx->cfg.pos_emb_xyz, xenc) != KNERF_OK ||
+            knerf_positional_encoding(s, dir, m, ctx->cfg.pos_emb_dir, denc) != KNERF_OK)
+            return fail(ctx, KNERF_ERR_HIP, "query: positional encoding failed");
+        HIPCHK(gen::forward_encoded(p, ctx->call_ws, ctx->call_net, ctx->net[net].w, xenc, denc, m, raw, s));
+        HIPCHK(launch_query_scatter(q, m, raw, s));
+    }
+    return KNERF_OK;
+}
+
+int run_query(knerf_ctx* ctx, void* stream, int net, QueryArgs& q) {
+    if (!q.raw && !q.sigma && !q.rgb) return fail(ctx, KNERF_ERR_INVALID, "query: no output (raw, sigma and rgb are all NULL)");
+    if (q.n <= 0 || q.n > (1ll << 38)) return fail(ctx, KNERF_ERR_INVALID, "query: need 1 <= number of points <= 2^38");
+    hipStream_t s = (hipStream_t)stream;
+    if (ctx->generic) return query_general(ctx, s, net, q);
+    q.stream = ctx->net[net].fwd_stream; q.bias = ctx->net[net].bias; q.shape = ctx->shape;
+    HIPCHK(launch_query(q, s));
+    return KNERF_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 size_t knerf_param_count(void) { return (size_t)kParamCount; }
@@ -610,7 +693,7 @@ int knerf_destroy(knerf_ctx* ctx) {
     free_dev(ctx->gws.act); free_dev(ctx->gws.dz); free_dev(ctx->gws.zs); free_dev(ctx->gws.zc); free_dev(ctx->gws.mask);
     for (int n = 0; n < 2; ++n) { free_dev(ctx->gnet[n].packed); free_dev(ctx->gnet[n].head); free_dev(ctx->gnet[n].gaux); }
     free_dev(ctx->call_net.head);
-    free_dev(ctx->call_ws.act); free_dev(ctx->call_ws.zs); free_dev(ctx->call_ws.zc); free_dev(ctx->call_net.packed); free_dev(ctx->call_raw);
+    free_dev(ctx->call_ws.act); free_dev(ctx->call_ws.zs); free_dev(ctx->call_ws.zc); free_dev(ctx->call_net.packed); free_dev(ctx->call_raw); free_dev(ctx->query_tmp);
     delete ctx;
     return KNERF_OK;
 }
@@ -666,31 +749,41 @@ int knerf_mlp_call(knerf_ctx* ctx, void* stream, int net, const float* xyz_enc, 
     if (int r = check_net(ctx, net)) return r;
     if (!xyz_enc || !dir_enc || !raw || n == 0) return fail(ctx, KNERF_ERR_INVALID, "mlp_call: null/empty argument");
     hipStream_t s = (hipStream_t)stream;
-    if (!ctx->call_plan_ok) {
-        const knerf_config& c = ctx->cfg;
-        ctx->call_plan = ctx->mlp_only ? gen::build_plan_widths(c.n_layers, c.dense_units, c.skip_layer, c.pos_emb_xyz, c.pos_emb_dir)
-                                       : gen::build_plan(c.n_layers, c.dense_units, c.skip_layer, c.pos_emb_xyz, c.pos_emb_dir);
-        HIPCHK(hipMalloc(&ctx->call_net.packed, ctx->call_plan.packed_elems * sizeof(unsigned short)));
-        HIPCHK(hipMalloc(&ctx->call_net.head, gen::head_floats(ctx->call_plan) * sizeof(float)));
-        ctx->call_plan_ok = true;
-    }
-    const gen::Plan& p = ctx->call_plan;
-    const size_t mp = gen::padded_rows((long long)n);
-    gen::Workspace& w = ctx->call_ws;
-    if (mp > w.mp) {
-        HIPCHK(hipStreamSynchronize(s));
-        free_dev(w.act); free_dev(w.zs); free_dev(w.zc); free_dev(ctx->call_raw);
-        w.mp = 0;
-        const size_t ab = p.act_elems_per_row * mp * sizeof(unsigned short);
-        HIPCHK(hipMalloc(&w.act, ab));
-        HIPCHK(hipMemsetAsync(w.act, 0, ab, s));        // on the stream the consuming kernels run on
-        HIPCHK(hipMalloc(&w.zs, mp * 32 * sizeof(float)));
-        HIPCHK(hipMalloc(&w.zc, mp * 32 * sizeof(float)));
-        w.mp = mp;
-    }
-    HIPCHK(gen::pack_weights(p, ctx->net[net].w, ctx->call_net, s));       // the weights may have changed since the last call
-    HIPCHK(gen::forward_encoded(p, w, ctx->call_net, ctx->net[net].w, xyz_enc, dir_enc, (long long)n, raw, s));
+    if (int r = ensure_call(ctx, (long long)n, s)) return r;
+    HIPCHK(gen::pack_weights(ctx->call_plan, ctx->net[net].w, ctx->call_net, s));       // the weights may have changed since the last call
+    HIPCHK(gen::forward_encoded(ctx->call_plan, ctx->call_ws, ctx->call_net, ctx->net[net].w, xyz_enc, dir_enc, (long long)n, raw, s));
     return KNERF_OK;
+}
+
+int knerf_query_points(knerf_ctx* ctx, void* stream, int net, const float* xyz, const float* dirs, int dir_per_point, uint64_t n,
+                       float* raw, float* sigma, float* rgb) {
+    if (int r = check_net(ctx, net)) return r;
+    if (int r = check_rays(ctx, "query_points")) return r;
+    if (!xyz) return fail(ctx, KNERF_ERR_INVALID, "query_points: null xyz");
+    QueryArgs q{};
+    q.xyz = xyz; q.dir = dirs; q.dir_stride = dir_per_point ? 3 : 0; q.grid = 0;
+    q.raw = raw; q.sigma = sigma; q.rgb = rgb; q.n = (long long)n;
+    return run_query(ctx, stream, net, q);
+}
+
+int knerf_query_grid(knerf_ctx* ctx, void* stream, int net, const int32_t* resolution, const float* lo, const float* hi, const float* dir,
+                     float* raw, float* sigma, float* rgb) {
+    if (int r = check_net(ctx, net)) return r;
+    if (int r = check_rays(ctx, "query_grid")) return r;
+    if (!resolution || !lo || !hi) return fail(ctx, KNERF_ERR_INVALID, "query_grid: null resolution / lo / hi");
+    QueryArgs q{};
+    q.grid = 1; q.dir = dir; q.dir_stride = 0;
+    long long n = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (resolution[a] < 2) return fail(ctx, KNERF_ERR_INVALID, "query_grid: every resolution must be >= 2");
+        if (!(hi[a] > lo[a])) return fail(ctx, KNERF_ERR_INVALID, "query_grid: need hi > lo on every axis");
+        q.gr[a] = resolution[a];
+        q.lo[a] = lo[a];
+        q.step[a] = (hi[a] - lo[a]) / (float)(resolution[a] - 1);      // fp32 subtraction and division, as NumPy's float32
+        n *= resolution[a];
+    }
+    q.raw = raw; q.sigma = sigma; q.rgb = rgb; q.n = n;
+    return run_query(ctx, stream, net, q);
 }
 
 int knerf_sample_fine(knerf_ctx* ctx, void* stream, const float* t_coarse, const float* w_coarse, const float* u,

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from ... import parallel
-from ...runtime import COARSE, FINE, KnerfContext, NonFiniteGradientError  # noqa: F401
+from ...runtime import COARSE, FINE, KnerfContext, NonFiniteGradientError, marching_cubes  # noqa: F401
 from .metrics import Mean, MetricLogs, MetricState
 from .mlp import NeRFMLP
 from .utils import NeRFUtils
@@ -277,6 +277,64 @@ class NeRF:
         out = self._ctx.render_chunk(*ray_chunks, u=u, seed=seed, ray_offset=ray_offset)
         return ({"image": out["c_image"], "depth": out["c_depth"], "weights": out["c_weights"]},
                 {"image": out["f_image"], "depth": out["f_depth"], "weights": out["f_weights"]})
+
+    # ------------------------------------------------------------------ the trained field (extension, no reference counterpart)
+    def _field_net(self, net) -> int:
+        if self._ctx is None:
+            raise RuntimeError("the model is not compiled: call compile(...) before query / density_grid / extract_mesh")
+        if net not in ("coarse", "fine"):
+            raise ValueError(f"net must be 'coarse' or 'fine', got {net!r}")
+        return COARSE if net == "coarse" else FINE
+
+    @staticmethod
+    def _grid_spec(resolution, bounds):
+        res = (resolution,) * 3 if isinstance(resolution, (int, np.integer)) else tuple(resolution)
+        if len(res) != 3 or any(int(r) != r or int(r) < 2 for r in res):
+            raise ValueError(f"resolution must be an int or three ints, each >= 2; got {resolution!r}")
+        lo, hi = (tuple(float(v) for v in b) for b in bounds)
+        if len(lo) != 3 or len(hi) != 3 or not all(np.float32(h) > np.float32(l) for l, h in zip(lo, hi)):
+            raise ValueError(f"bounds must be (lo[3], hi[3]) with hi > lo on every axis; got {bounds!r}")
+        return tuple(int(r) for r in res), lo, hi
+
+    def query(self, points, directions=None, net="fine"):
+        """The trained MLP at points [..., 3] (any leading shape), viewed along directions None (zero vector), [3] or [..., 3]:
+        (rgb [..., 3] after sigmoid, sigma [..., 1] after relu) -- NeRFMLP.__call__'s contract on raw coordinates.  Fused shapes
+        run one fused kernel (the render path's encoding, trunk and head, bit for bit)."""
+        n = self._field_net(net)
+        p = self._ctx.f32(points)
+        if p.dim() < 1 or p.shape[-1] != 3:
+            raise ValueError(f"points must have a last dimension of 3, got {tuple(p.shape)}")
+        lead = tuple(p.shape[:-1])
+        d = None
+        if directions is not None:
+            d = self._ctx.f32(directions)
+            if d.shape[-1] != 3:
+                raise ValueError(f"directions must have a last dimension of 3, got {tuple(d.shape)}")
+            if d.numel() != 3:
+                d = torch.broadcast_to(d, p.shape).contiguous()
+        sigma, rgb = self._ctx.query_points(n, p.reshape(-1, 3), None if d is None else d.reshape(-1, 3), raw=False, rgb=True)
+        return rgb.reshape(lead + (3,)), sigma.reshape(lead + (1,))
+
+    def density_grid(self, resolution, bounds=((-1.5,) * 3, (1.5,) * 3), net="fine", direction=None):
+        """sigma [Rx, Ry, Rz] of the trained MLP on the grid lo + idx * (hi - lo) / (R - 1) (C order, z fastest); resolution an int
+        or a 3-tuple.  With `direction` ([3]): (sigma, rgb [Rx, Ry, Rz, 3]) seen along it."""
+        n = self._field_net(net)
+        res, lo, hi = self._grid_spec(resolution, bounds)
+        sigma, rgb = self._ctx.query_grid(n, res, lo, hi, direction, rgb=direction is not None)
+        return sigma if direction is None else (sigma, rgb)
+
+    def extract_mesh(self, threshold, resolution=256, bounds=((-1.5,) * 3, (1.5,) * 3), net="fine", vertex_colors=False):
+        """Marching cubes on density_grid(resolution, bounds, net) at sigma = threshold (inside: sigma > threshold): (vertices [V,3]
+        f32, faces [F,3] int32, normals [V,3]), torch tensors on the model's device; normals point outward (toward lower density).
+        vertex_colors: also rgb [V,3] queried at each vertex along -normal.  An empty surface gives empty arrays.
+        keras_nerf_amd.io.ply.save_ply writes the result."""
+        res, lo, hi = self._grid_spec(resolution, bounds)
+        sigma = self.density_grid(res, (lo, hi), net)
+        verts, faces, normals = marching_cubes(sigma, float(threshold), lo, hi)
+        if not vertex_colors:
+            return verts, faces, normals
+        colors = self.query(verts, -normals, net)[0]
+        return verts, faces, normals, colors
 
     def predict_and_render_images(self, rays, u=None, outputs=None):
         """nerf.py:229-304: returns (coarse_results, fine_results), each {image [B,H,W,3], depth [B,H,W], weights [B,H,W,S]}.

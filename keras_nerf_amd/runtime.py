@@ -437,6 +437,42 @@ class KnerfContext:
         self._check(self.lib.knerf_mlp_call(self._ctx, self._stream(), int(net), _ptr(x), _ptr(dd), n, _ptr(raw)))
         return raw
 
+    # ---- the trained field and its surface (extension: knerf_query_points / knerf_query_grid / knerf_marching_cubes)
+    def query_points(self, net: int, xyz, dirs=None, raw=True, rgb=True):
+        """the MLP at points xyz [n,3]; dirs None, [3] (shared) or [n,3].  raw=True: raw [n,4]; else (sigma [n], rgb [n,3] or None)"""
+        x = self.f32(xyz).reshape(-1, 3)
+        n = x.shape[0]
+        dd, per_point = None, 0
+        if dirs is not None:
+            dd = self.f32(dirs)
+            if dd.numel() == 3:
+                dd = dd.reshape(3)
+            else:
+                dd, per_point = dd.reshape(-1, 3), 1
+                if dd.shape[0] != n:
+                    raise ValueError(f"query: {dd.shape[0]} directions for {n} points")
+        e = lambda *s: torch.empty(s, device=self.device, dtype=torch.float32)
+        if n == 0:
+            return e(0, 4) if raw else (e(0), e(0, 3) if rgb else None)
+        out_raw = e(n, 4) if raw else None
+        sig = None if raw else e(n)
+        col = e(n, 3) if (rgb and not raw) else None
+        self._check(self.lib.knerf_query_points(self._ctx, self._stream(), int(net), _ptr(x), _ptr(dd), per_point, n, _ptr(out_raw),
+                                                _ptr(sig), _ptr(col)))
+        return out_raw if raw else (sig, col)
+
+    def query_grid(self, net: int, resolution, lo, hi, direction=None, rgb=False):
+        """sigma [R0,R1,R2] (and rgb [R0,R1,R2,3] when rgb) on the grid lo + idx * (hi - lo) / (R - 1) (include/knerf.h)"""
+        res = (C.c_int32 * 3)(*[int(r) for r in resolution])
+        lo3, hi3 = (C.c_float * 3)(*[float(v) for v in lo]), (C.c_float * 3)(*[float(v) for v in hi])
+        dd = None if direction is None else self.f32(direction).reshape(3)
+        shape = tuple(int(r) for r in resolution)
+        sig = torch.empty(shape, device=self.device, dtype=torch.float32)
+        col = torch.empty(shape + (3,), device=self.device, dtype=torch.float32) if rgb else None
+        self._check(self.lib.knerf_query_grid(self._ctx, self._stream(), int(net), res, lo3, hi3, _ptr(dd), None, _ptr(sig), _ptr(col)))
+        return sig, col
+
+
     def zero_grads(self):
         self._check(self.lib.knerf_zero_grads(self._ctx, self._stream()))
 
@@ -472,3 +508,38 @@ class KnerfContext:
         ms = (C.c_double * n)(); cnt = (C.c_int64 * n)()
         self._check(self.lib.knerf_profile_read(self._ctx, ms, cnt, n))
         return {k: (ms[i], int(cnt[i])) for i, k in enumerate(self.PROFILE_CLASSES)}
+
+
+def marching_cubes(grid: torch.Tensor, threshold: float, lo, hi, normals: bool = True):
+    """knerf_marching_cubes on a device fp32 grid [Rx,Ry,Rz] (contiguous): (vertices [V,3] f32, faces [F,3] int32, normals [V,3] or
+    None), all on the grid's device.  Inside means sigma > threshold; an empty surface gives empty arrays."""
+    lib = _lib.load()
+    if not isinstance(grid, torch.Tensor) or grid.dtype != torch.float32 or grid.dim() != 3 or not grid.is_contiguous():
+        raise ValueError("marching_cubes: the grid must be a contiguous float32 torch tensor [Rx, Ry, Rz]")
+    if min(grid.shape) < 2:
+        raise ValueError(f"marching_cubes: every resolution must be >= 2, got {tuple(grid.shape)}")
+    lo, hi = [float(v) for v in lo], [float(v) for v in hi]
+    if len(lo) != 3 or len(hi) != 3 or not all(np.float32(h) > np.float32(l) for l, h in zip(lo, hi)):
+        raise ValueError(f"marching_cubes: need hi > lo on every axis, got {lo} / {hi}")
+    dev = grid.device
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    rx, ry, rz = (int(r) for r in grid.shape)
+    lo3, hi3 = (C.c_float * 3)(*lo), (C.c_float * 3)(*hi)
+    nbytes, counts = C.c_size_t(0), (C.c_int64 * 2)()
+
+    def chk(rc):
+        if rc != 0:
+            raise ValueError(f"knerf_marching_cubes failed ({rc}) on a [{rx},{ry},{rz}] grid") if rc == _lib.KNERF_ERR_INVALID else \
+                KnerfError(f"knerf_marching_cubes failed ({rc})")
+    chk(lib.knerf_marching_cubes(stream, None, rx, ry, rz, lo3, hi3, float(threshold), None, C.byref(nbytes), counts, None, None, None))
+    ws = torch.empty((nbytes.value,), device=dev, dtype=torch.uint8)
+    chk(lib.knerf_marching_cubes(stream, _ptr(grid), rx, ry, rz, lo3, hi3, float(threshold), _ptr(ws), C.byref(nbytes), counts, None, None,
+                                 None))
+    V, F = int(counts[0]), int(counts[1])
+    verts = torch.empty((V, 3), device=dev, dtype=torch.float32)
+    faces = torch.empty((F, 3), device=dev, dtype=torch.int32)
+    nrm = torch.empty((V, 3), device=dev, dtype=torch.float32) if normals else None
+    if V or F:
+        chk(lib.knerf_marching_cubes(stream, _ptr(grid), rx, ry, rz, lo3, hi3, float(threshold), _ptr(ws), C.byref(nbytes), counts,
+                                     _ptr(verts), _ptr(faces), _ptr(nrm)))
+    return verts, faces, nrm
