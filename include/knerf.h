@@ -240,6 +240,38 @@ int knerf_query_grid(knerf_ctx* ctx, void* stream, int net, const int32_t* resol
 int knerf_marching_cubes(void* stream, const float* grid, int rx, int ry, int rz, const float* lo, const float* hi, float threshold,
                          void* workspace, size_t* workspace_bytes, int64_t* counts, float* vertices, int32_t* faces, float* normals);
 
+/* ---- Empty-space skipping for rendering.  Extension, no reference counterpart (occupancy grids as in Instant-NGP and Plenoxels). ----
+ * Each net may carry one occupancy grid: cells[0] x cells[1] x cells[2] bits over the box [lo, hi].  With a grid attached to net n,
+ * every RENDER pass of n runs the MLP only on samples whose cell is occupied (the coarse pass uses the coarse grid, the fine pass the
+ * fine grid); every other sample gets raw = (0, 0, 0, 0): sigma = 0, alpha = 0, compositing weight exactly 0.  Compositing, the sampler
+ * and the outputs work as before; the fine sampler takes the coarse weights that come out of this, so t_fine may differ from the dense
+ * render.  A sample that is evaluated gets the bits the dense render (and knerf_query_points) gives it.
+ *   Applies to:     knerf_render_chunk, knerf_render_batch.
+ *   Never applies:  knerf_train_chunk, knerf_train_batch, knerf_forward_chunk, knerf_query_points, knerf_query_grid (training never skips).
+ * Cell lookup of sample p = __fadd_rn(o, __fmul_rn(d, t)) (the render path's two roundings), per axis:
+ *   u = __fmul_rn(__fsub_rn(p, lo), scale), scale = fp32(cells / (hi - lo)) computed in double on the host; i = floor(u).
+ *   Outside the box: u < 0, i >= cells or u NaN on any axis; then the `outside` policy decides (occupied, or empty).
+ *   Inside: bit (i cy + j) cz + k, i.e. bit b % 32 of little-endian uint32 word b / 32.
+ * Fused shapes compact the live samples (an ordered scan) and run the fused MLP on that list only; the general-shape path
+ * (shapes without fused kernels, KNERF_FLAG_FORCE_GENERIC) runs its MLP over every sample and zeroes the dead ones: the same outputs
+ * without the speed-up.  The compaction runs under the net's forward profile class (knerf_profile_read classes 0 / 1).
+ * The grid is the caller's: training does not update it. */
+/* knerf_set_occupancy -- extension, no reference counterpart.  bits: DEVICE uint32 [ceil(cx cy cz / 32)], copied into a buffer the
+ * context owns (on `stream`); NULL detaches the net's grid.  cells, lo, hi: HOST [3]; 1 <= cells <= 1024 and finite hi > lo per axis.
+ * outside_empty: 0 = a sample outside the box is occupied, 1 = empty.  KNERF_ERR_INVALID on bad arguments and on a
+ * KNERF_FLAG_ENCODED_WIDTHS context. */
+int knerf_set_occupancy(knerf_ctx* ctx, void* stream, int net, const uint32_t* bits, const int32_t* cells, const float* lo, const float* hi,
+                        int outside_empty);
+/* knerf_occupancy_from_grid -- extension, no reference counterpart.  Context-free.  sigma: DEVICE fp32 lattice [rx,ry,rz] (e.g.
+ * knerf_query_grid on [lo, hi]; 2 <= r <= 1025), so the grid has (rx-1) x (ry-1) x (rz-1) cells.  A cell is occupied if any of its 8
+ * corners has sigma > threshold; then the occupied set is dilated by `dilation` cells (0..8, Chebyshev distance).  A heuristic: density
+ * between lattice points can be missed, the dilation is the margin.  bits: DEVICE uint32 [ceil(cells / 32)] (padding bits 0). */
+int knerf_occupancy_from_grid(void* stream, const float* sigma, int rx, int ry, int rz, float threshold, int dilation, uint32_t* bits);
+/* knerf_occupancy_stats -- extension, no reference counterpart.  Per net since the last reset: live[n] = samples of render passes whose
+ * MLP output is kept (occupied), total[n] = samples those passes considered (passes without a grid are not counted).
+ * Synchronises `stream`. */
+int knerf_occupancy_stats(knerf_ctx* ctx, void* stream, int64_t* live, int64_t* total, int reset);
+
 /* Diagnostics (layout tables, workspace views, hardware-fact and bandwidth probes) are NOT part of this library: they are
  * declared in include/knerf_debug.h and built into libknerf_probe.so for tests/ and tools/ only. */
 

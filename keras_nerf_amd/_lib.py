@@ -68,6 +68,9 @@ SIGNATURES = {
     "knerf_query_grid": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, _P]),
     "knerf_marching_cubes": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, _P,
                                        C.POINTER(C.c_size_t), C.POINTER(C.c_int64), _P, _P, _P]),
+    "knerf_set_occupancy": (C.c_int, [_P, _P, C.c_int, _P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]),
+    "knerf_occupancy_from_grid": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
+    "knerf_occupancy_stats": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
 }
 
 _lib = None

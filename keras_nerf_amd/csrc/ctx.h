@@ -88,6 +88,13 @@ struct knerf_ctx {
     float* call_raw = nullptr;
     // knerf_query_points / knerf_query_grid on the general-shape route: per-chunk points, directions, encodings and raw (grow-only)
     float* query_tmp = nullptr; size_t query_tmp_bytes = 0;
+    // occupancy grids of the render passes (knerf_set_occupancy; occupancy.h): per net, bits owned by the context (null: none), and the
+    // compaction workspace of the fused path (ballots, per-workgroup counts / offsets, the list of live samples and its length), sized
+    // with the render workspace while a grid is attached (ws_occ_rays)
+    struct Occ { unsigned* bits = nullptr; size_t words = 0; int cells[3] = {0, 0, 0}; float lo[3] = {0, 0, 0}, scale[3] = {0, 0, 0}; int outside_empty = 0; };
+    Occ occ[2];
+    char* occ_ws = nullptr; int ws_occ_rays = 0;
+    long long* occ_stats = nullptr;     // [net][2]: samples whose MLP output is live (occupied), samples considered
     // run-time options (knerf_set_option)
     bool deterministic = false;         // per-workgroup partial sums + ordered second pass instead of fp32 atomics (wgrad, loss)
     bool skip_dead = true;              // dgrad / wgrad skip 32-sample tiles whose dL/d(rgb, sigma) is exactly zero (exact; +0.3 % when nothing is dead)

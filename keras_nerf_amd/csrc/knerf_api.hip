@@ -15,6 +15,7 @@
 #include "kernels.h"
 #include "generic.h"
 #include "layout.h"
+#include "occupancy.h"
 #include "query.h"
 
 using namespace knerf;
@@ -127,6 +128,21 @@ int over_limit(knerf_ctx* ctx, double bytes) {
     return KNERF_OK;
 }
 
+// the occupancy compaction workspace of a pass of n samples (fused path): ballots [ceil(n / 64)] u64, list [n], per-workgroup counts and
+// offsets [occ_blocks(n)] each, the list's length
+struct OccWs { unsigned long long* masks; int *list, *blk_cnt, *blk_off, *count; };
+size_t occ_ws_bytes(long long n) { return (size_t)((n + 63) / 64) * 8 + (size_t)n * 4 + (size_t)occ_blocks(n) * 8 + 4; }
+OccWs occ_ws_view(char* base, long long n) {
+    OccWs w;
+    w.masks = reinterpret_cast<unsigned long long*>(base);
+    w.list = reinterpret_cast<int*>(base + (size_t)((n + 63) / 64) * 8);
+    w.blk_cnt = w.list + n;
+    w.blk_off = w.blk_cnt + occ_blocks(n);
+    w.count = w.blk_off + occ_blocks(n);
+    return w;
+}
+bool occ_attached(const knerf_ctx* ctx) { return ctx->occ[0].bits || ctx->occ[1].bits; }
+
 int ensure_ws_impl(knerf_ctx* ctx, int n_rays, bool train, hipStream_t s, int group) {
     const int Na = ctx->cfg.n_coarse + ctx->cfg.n_fine;
     if (ctx->generic) {          // general-shape path: one size for everything (its activations are forward buffers too)
@@ -176,14 +192,17 @@ int ensure_ws_impl(knerf_ctx* ctx, int n_rays, bool train, hipStream_t s, int gr
     }
     const bool grow_base = n_rays > ctx->ws_rays;
     const bool grow_train = train && (!ctx->ws_train || n_rays > ctx->ws_train_rays || group > ctx->ws_group);
-    if (!grow_base && !grow_train) return KNERF_OK;
+    // renders behind an occupancy grid: the compaction workspace (4 B + 1 bit per sample), only while a grid is attached
+    const bool grow_occ = !train && occ_attached(ctx) && n_rays > ctx->ws_occ_rays;
+    if (!grow_base && !grow_train && !grow_occ) return KNERF_OK;
     if (ctx->ws_limit_gb > 0) {
         const int Rt = n_rays > ctx->ws_train_rays ? n_rays : ctx->ws_train_rays;
         const size_t tl = group == 1 ? tiles_for((long long)Rt * Na) : (size_t)group * tiles_for((long long)Rt * ctx->cfg.n_coarse) + tiles_for((long long)Rt * Na);
         const double base_b = grow_base ? (double)n_rays * Na * 20 + (double)n_rays * (ctx->cfg.n_coarse * 4 + 32) : 0.0;
         const double train_b = grow_train ? (double)Rt * Na * 16 + (double)saved_region_bytes(tl, ctx->si.act_blocks) +
                                                 (double)saved_region_bytes(tl, ctx->si.mask_blocks) + (double)saved_region_bytes(tl, ctx->si.dz_blocks) : 0.0;
-        if (int r = over_limit(ctx, base_b + train_b)) return r;
+        const double occ_b = grow_occ ? (double)occ_ws_bytes((long long)n_rays * Na) : 0.0;
+        if (int r = over_limit(ctx, base_b + train_b + occ_b)) return r;
     }
     HIPCHK(hipStreamSynchronize(s));               // nothing enqueued earlier may still use the buffers that are freed below
     if (grow_base) {
@@ -196,6 +215,12 @@ int ensure_ws_impl(knerf_ctx* ctx, int n_rays, bool train, hipStream_t s, int gr
         HIPCHK(hipMalloc(&ctx->t_f, ns * sizeof(float)));
         HIPCHK(hipMalloc(&ctx->img_tmp, (size_t)n_rays * 8 * sizeof(float)));
         ctx->ws_rays = n_rays;
+    }
+    if (grow_occ) {
+        free_dev(ctx->occ_ws);
+        ctx->ws_occ_rays = 0;
+        HIPCHK(hipMalloc(&ctx->occ_ws, occ_ws_bytes((long long)n_rays * Na)));
+        ctx->ws_occ_rays = n_rays;
     }
     if (grow_train) {
         const int R = n_rays > ctx->ws_train_rays ? n_rays : ctx->ws_train_rays;
@@ -333,10 +358,21 @@ int launch_wgrad_tiles(knerf_ctx* ctx, hipStream_t s, int net, size_t tile0, siz
 // (false: the caller launches it later over several passes, launch_wgrad_tiles)
 // group_count: (default-mode skipping, coarse pass of a grouped launch) the group's counter: the pass's live tiles are appended to
 // ctx->tile_list_g as well, as indices relative to the group's first region (+ tile0)
+// render: a pass of knerf_render_chunk -- the net's occupancy grid, if one is attached, applies (never to training, forward_chunk or queries)
 int run_pass(knerf_ctx* ctx, hipStream_t s, int net, const float* o, const float* d, const float* t, int R, int S,
              float* image, float* depth, float* weights, const float* target, float inv_chunks, float* loss,
-             size_t tile0 = 0, bool wgrad_now = true, int* group_count = nullptr) {
+             size_t tile0 = 0, bool wgrad_now = true, int* group_count = nullptr, bool render = false) {
     const bool train = target != nullptr;
+    const knerf_ctx::Occ* og = render && !train && ctx->occ[net].bits ? &ctx->occ[net] : nullptr;
+    OccArgs oa{};
+    if (og) {
+        oa.grid.bits = og->bits; oa.grid.outside_empty = og->outside_empty;
+        for (int c = 0; c < 3; ++c) { oa.grid.cells[c] = og->cells[c]; oa.grid.lo[c] = og->lo[c]; oa.grid.scale[c] = og->scale[c]; }
+        oa.o = o; oa.d = d; oa.t = t; oa.n = (long long)R * S; oa.S = S; oa.raw = ctx->raw;
+        oa.stats = ctx->occ_stats + 2 * (net == KNERF_COARSE ? 0 : 1);
+        if (!ctx->generic && oa.n >= (1ll << 31))       // the list holds int32 sample indices
+            return fail(ctx, KNERF_ERR_INVALID, "render behind an occupancy grid: a pass of 2^31 samples or more (use a smaller ray_chunks)");
+    }
     FwdArgs fa{};
     fa.stream = ctx->net[net].fwd_stream; fa.bias = ctx->net[net].bias;
     fa.o = o; fa.d = d; fa.t = t; fa.raw = ctx->raw;
@@ -346,6 +382,18 @@ int run_pass(knerf_ctx* ctx, hipStream_t s, int net, const float* o, const float
     if (ctx->generic) {
         ProfScope ps(ctx, s, net == KNERF_COARSE ? P_FWD_C : P_FWD_F);
         HIPCHK(gen::forward(ctx->gplan, ctx->gws, ctx->gnet[net], ctx->net[net].w, o, d, t, fa.n_samples, S, ctx->raw, s));
+        // general-shape path: the MLP ran on every sample; the dead ones are zeroed behind it (same outputs, no speed-up)
+        if (og) HIPCHK(launch_occupancy_mark(oa, s));
+    } else if (og) {
+        // fused path: ordered compaction of the live samples, then the fused MLP on the list alone (query.hip list mode)
+        ProfScope ps(ctx, s, net == KNERF_COARSE ? P_FWD_C : P_FWD_F);
+        const OccWs w = occ_ws_view(ctx->occ_ws, oa.n);
+        oa.masks = w.masks; oa.blk_cnt = w.blk_cnt; oa.blk_off = w.blk_off; oa.list = w.list; oa.count = w.count;
+        HIPCHK(launch_occupancy_mark(oa, s));
+        QueryArgs q{};
+        q.stream = ctx->net[net].fwd_stream; q.bias = ctx->net[net].bias; q.shape = ctx->shape;
+        q.raw = ctx->raw; q.n = oa.n; q.list = w.list; q.count = w.count; q.o = o; q.d = d; q.t = t; q.S = S;
+        HIPCHK(launch_query_list(q, s));
     } else {
         ProfScope ps(ctx, s, net == KNERF_COARSE ? P_FWD_C : P_FWD_F);
         HIPCHK(launch_mlp_fwd(fa, train, s));
@@ -629,6 +677,8 @@ int knerf_create(const knerf_config* cfg, knerf_ctx** out) {
     CREATECHK(hipMemset(ctx->tile_count, 0, (size_t)ctx->tile_counters * sizeof(int)));
     CREATECHK(hipMalloc(&ctx->tile_stats, 8 * sizeof(long long)));       // per net: live, total, [2], [3]: out-of-range list entries (diagnostic builds)
     CREATECHK(hipMemset(ctx->tile_stats, 0, 8 * sizeof(long long)));
+    CREATECHK(hipMalloc(&ctx->occ_stats, 4 * sizeof(long long)));
+    CREATECHK(hipMemset(ctx->occ_stats, 0, 4 * sizeof(long long)));
     CREATECHK(hipMalloc(&ctx->d_diag, 2 * sizeof(unsigned long long)));
     CREATECHK(hipHostMalloc(&ctx->h_diag, 4 * sizeof(long long), hipHostMallocDefault));
     ctx->h_diag[0] = ctx->h_diag[1] = ctx->h_diag[2] = ctx->h_diag[3] = 0;
@@ -690,6 +740,7 @@ int knerf_destroy(knerf_ctx* ctx) {
     free_dev(ctx->act); free_dev(ctx->mask); free_dev(ctx->dz);
     free_dev(ctx->tile_flags); free_dev(ctx->tile_list); free_dev(ctx->tile_list_g); free_dev(ctx->tile_count); free_dev(ctx->tile_stats);
     free_dev(ctx->partial); free_dev(ctx->loss_partial); free_dev(ctx->d_job_wg0);
+    free_dev(ctx->occ[0].bits); free_dev(ctx->occ[1].bits); free_dev(ctx->occ_ws); free_dev(ctx->occ_stats);
     free_dev(ctx->gws.act); free_dev(ctx->gws.dz); free_dev(ctx->gws.zs); free_dev(ctx->gws.zc); free_dev(ctx->gws.mask);
     for (int n = 0; n < 2; ++n) { free_dev(ctx->gnet[n].packed); free_dev(ctx->gnet[n].head); free_dev(ctx->gnet[n].gaux); }
     free_dev(ctx->call_net.head);
@@ -786,6 +837,51 @@ int knerf_query_grid(knerf_ctx* ctx, void* stream, int net, const int32_t* resol
     return run_query(ctx, stream, net, q);
 }
 
+int knerf_set_occupancy(knerf_ctx* ctx, void* stream, int net, const uint32_t* bits, const int32_t* cells, const float* lo, const float* hi,
+                        int outside_empty) {
+    if (int r = check_net(ctx, net)) return r;
+    if (int r = check_rays(ctx, "set_occupancy")) return r;
+    hipStream_t s = (hipStream_t)stream;
+    knerf_ctx::Occ& G = ctx->occ[net];
+    if (!bits) {                                        // detach: passes enqueued earlier may still read the old bits
+        HIPCHK(hipStreamSynchronize(s));
+        free_dev(G.bits);
+        G = knerf_ctx::Occ{};
+        return KNERF_OK;
+    }
+    if (!cells || !lo || !hi) return fail(ctx, KNERF_ERR_INVALID, "set_occupancy: null cells / lo / hi");
+    float scale[3];
+    long long n = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (cells[a] < 1 || cells[a] > 1024) return fail(ctx, KNERF_ERR_INVALID, "set_occupancy: need 1 <= cells <= 1024 on every axis");
+        if (!(hi[a] > lo[a]) || !std::isfinite(lo[a]) || !std::isfinite(hi[a])) return fail(ctx, KNERF_ERR_INVALID, "set_occupancy: need finite hi > lo on every axis");
+        scale[a] = (float)((double)cells[a] / ((double)hi[a] - (double)lo[a]));
+        if (!std::isfinite(scale[a])) return fail(ctx, KNERF_ERR_INVALID, "set_occupancy: the box is too thin for its cells");
+        n *= cells[a];
+    }
+    const size_t words = (size_t)((n + 31) / 32);
+    if (words > G.words) {
+        HIPCHK(hipStreamSynchronize(s));
+        free_dev(G.bits); G.words = 0;
+        HIPCHK(hipMalloc(&G.bits, words * sizeof(uint32_t)));
+        G.words = words;
+    }
+    HIPCHK(hipMemcpyAsync(G.bits, bits, words * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));     // behind every pass enqueued earlier
+    for (int a = 0; a < 3; ++a) { G.cells[a] = cells[a]; G.lo[a] = lo[a]; G.scale[a] = scale[a]; }
+    G.outside_empty = outside_empty ? 1 : 0;
+    return KNERF_OK;
+}
+
+int knerf_occupancy_stats(knerf_ctx* ctx, void* stream, int64_t* live, int64_t* total, int reset) {
+    if (!ctx || !live || !total) return KNERF_ERR_INVALID;
+    long long h[4] = {0, 0, 0, 0};
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    HIPCHK(hipMemcpy(h, ctx->occ_stats, sizeof(h), hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(ctx->occ_stats, 0, sizeof(h)));
+    for (int n = 0; n < 2; ++n) { live[n] = h[2 * n]; total[n] = h[2 * n + 1]; }
+    return KNERF_OK;
+}
+
 int knerf_sample_fine(knerf_ctx* ctx, void* stream, const float* t_coarse, const float* w_coarse, const float* u,
                       uint64_t seed, uint64_t stream_id, uint64_t ray_offset, int n_rays, float* t_out) {
     if (int r = check_rays(ctx, "sample_fine")) return r;
@@ -808,9 +904,9 @@ int knerf_render_chunk(knerf_ctx* ctx, void* stream, const float* o, const float
     const int Nc = ctx->cfg.n_coarse, Na = Nc + ctx->cfg.n_fine;
     float* wc = c_weights ? c_weights : ctx->w_c;
     float* tf = t_fine ? t_fine : ctx->t_f;
-    if (int r = run_pass(ctx, s, KNERF_COARSE, o, d, t, n_rays, Nc, c_image, c_depth, wc, nullptr, 1.f, nullptr)) return r;
+    if (int r = run_pass(ctx, s, KNERF_COARSE, o, d, t, n_rays, Nc, c_image, c_depth, wc, nullptr, 1.f, nullptr, 0, true, nullptr, true)) return r;
     if (int r = knerf_sample_fine(ctx, stream, t, wc, u, seed, 0, ray_offset, n_rays, tf)) return r;
-    return run_pass(ctx, s, KNERF_FINE, o, d, tf, n_rays, Na, f_image, f_depth, f_weights, nullptr, 1.f, nullptr);
+    return run_pass(ctx, s, KNERF_FINE, o, d, tf, n_rays, Na, f_image, f_depth, f_weights, nullptr, 1.f, nullptr, 0, true, nullptr, true);
 }
 
 int knerf_render_batch(knerf_ctx* ctx, void* stream, const float* o, const float* d, const float* t, const float* u, uint64_t seed,

@@ -19,9 +19,20 @@ struct QueryArgs {
     long long n;
     long long offset;       // first point of this launch (grid and points mode alike)
     int shape;              // layout.h fused_shape_id
+    // list mode (launch_query_list, the render pass behind an occupancy grid, csrc/occupancy.hip): sample gi = list[g] of a pass of
+    // n = R*S samples, g < *count (device); ray gi / S, p = o + d * t[gi] as mlp_fwd.hip, direction d of the ray; writes raw[gi]
+    const int* list;
+    const int* count;
+    const float* o;         // [R,3]
+    const float* d;         // [R,3]
+    const float* t;         // [R,S]
+    int S;
 };
 hipError_t launch_query(const QueryArgs& a, hipStream_t stream);
 template <class S> hipError_t launch_query_t(const QueryArgs& a, hipStream_t stream);
+// list mode: a grid sized for all n samples; workgroups whose first list entry lies at or beyond *count exit at once (no host sync)
+hipError_t launch_query_list(const QueryArgs& a, hipStream_t stream);
+template <class S> hipError_t launch_query_list_t(const QueryArgs& a, hipStream_t stream);
 
 // the general-shape route's prologue / epilogue (query.hip): points [n,3] and directions [n,3] of points offset .. offset+n-1,
 // and raw [n,4] -> the caller's outputs at offset

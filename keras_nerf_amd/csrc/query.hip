@@ -7,6 +7,8 @@
 //   prologue  points: xyz [n,3]; grid: point g = (i,j,k) of a [R0,R1,R2] grid (C order, z fastest) at
 //             __fadd_rn(lo, __fmul_rn((float)idx, step)) per axis (csrc/mesh.hip places vertices on the same lattice).
 //             Direction: none (zero vector), one shared [3], or per point [n,3].
+//             List mode (query_list_kernel): sample list[g] of a render pass, p and direction exactly as mlp_fwd.hip computes them
+//             (the occupancy grid's live samples, csrc/occupancy.hip); the list's length is read on the device.
 //   epilogue  raw [n,4] (rgb after sigmoid, sigma after relu), and / or sigma [n], rgb [n,3].
 // Compiled once per trunk shape like the other sliced kernels (build.py SLICED); slice 0 also holds the dispatcher and the
 // general-shape route's gather / scatter kernels.
@@ -81,8 +83,9 @@ __device__ __forceinline__ void query_store(const QueryArgs& a, long long gi, co
     if (a.rgb) { a.rgb[gi * 3 + 0] = r[0]; a.rgb[gi * 3 + 1] = r[1]; a.rgb[gi * 3 + 2] = r[2]; }
 }
 
-template <class S>
-__global__ __launch_bounds__(kThreads, 2) void query_kernel(QueryArgs a) {
+// LIST = false: points / grid prologue (query_kernel); true: the render pass's live samples (query_list_kernel, below)
+template <class S, bool LIST>
+__device__ __forceinline__ void query_body(const QueryArgs& a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* bias_lds = reinterpret_cast<float*>(smem + kRingBytes);
     const int tid = threadIdx.x, lane = tid & 63;
@@ -90,15 +93,35 @@ __global__ __launch_bounds__(kThreads, 2) void query_kernel(QueryArgs a) {
     const int grp = wave >> 2;
     const int col = lane & 31, h = lane >> 5;
 
+    long long n = a.n;
+    if constexpr (LIST) {
+        // the list's length is known on the device only: a workgroup with nothing to do leaves before it touches LDS or the ring.
+        // The test depends on blockIdx alone, so all 8 waves (which share the ring's barriers) leave together.
+        n = *a.count;
+        if ((long long)blockIdx.x * kWaves * kTile >= n) return;
+    }
+
     for (int i = tid; i < S::kFwdBiasTiles * 32; i += kThreads) bias_lds[i] = a.bias[i];
 
     const long long tile = (long long)blockIdx.x * kWaves + wave;
     long long g = tile * kTile + col;
-    const bool valid = g < a.n;
-    if (!valid) g = a.n - 1;
-    const long long gi = a.offset + g;
+    const bool valid = g < n;
+    if (!valid) g = n - 1;
+    long long gi;
     float p[3], dv[3];
-    query_point(a, gi, p, dv);
+    if constexpr (LIST) {
+        gi = a.list[g];
+        const long long ray = gi / a.S;
+        const float t = a.t[gi];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            dv[c] = a.d[ray * 3 + c];
+            p[c] = __fadd_rn(a.o[ray * 3 + c], __fmul_rn(dv[c], t));     // mlp_fwd.hip: two roundings
+        }
+    } else {
+        gi = a.offset + g;
+        query_point(a, gi, p, dv);
+    }
     const float px = p[0], py = p[1], pz = p[2], dx = dv[0], dy = dv[1], dz = dv[2];
     __syncthreads();
 
@@ -167,6 +190,13 @@ __global__ __launch_bounds__(kThreads, 2) void query_kernel(QueryArgs a) {
 }
 
 template <class S>
+__global__ __launch_bounds__(kThreads, 2) void query_kernel(QueryArgs a) { query_body<S, false>(a); }
+
+// the third prologue: raw of the live samples of a render pass (csrc/occupancy.hip builds the list)
+template <class S>
+__global__ __launch_bounds__(kThreads, 2) void query_list_kernel(QueryArgs a) { query_body<S, true>(a); }
+
+template <class S>
 hipError_t launch_query_t(const QueryArgs& a, hipStream_t stream) {
     const long long tiles = (a.n + kTile - 1) / kTile;
     const int grid = (int)((tiles + kWaves - 1) / kWaves);
@@ -180,7 +210,22 @@ hipError_t launch_query_t(const QueryArgs& a, hipStream_t stream) {
     return hipGetLastError();
 }
 
-#define KNERF_X(I, ...) KNERF_PICK(I, template, extern template) hipError_t launch_query_t<KNERF_SHAPE_T(__VA_ARGS__)>(const QueryArgs&, hipStream_t);
+template <class S>
+hipError_t launch_query_list_t(const QueryArgs& a, hipStream_t stream) {
+    const long long tiles = (a.n + kTile - 1) / kTile;           // sized for every sample of the pass; the count decides on the device
+    const int grid = (int)((tiles + kWaves - 1) / kWaves);
+    const size_t lds = kRingBytes + S::kFwdBiasTiles * 32 * sizeof(float);
+    static AttrOnce once;
+    hipError_t ae = once([&]() -> hipError_t {
+        return hipFuncSetAttribute(reinterpret_cast<const void*>(query_list_kernel<S>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    });
+    if (ae != hipSuccess) return ae;
+    hipLaunchKernelGGL((query_list_kernel<S>), dim3(grid), dim3(kThreads), lds, stream, a);
+    return hipGetLastError();
+}
+
+#define KNERF_X(I, ...) KNERF_PICK(I, template, extern template) hipError_t launch_query_t<KNERF_SHAPE_T(__VA_ARGS__)>(const QueryArgs&, hipStream_t); \
+    KNERF_PICK(I, template, extern template) hipError_t launch_query_list_t<KNERF_SHAPE_T(__VA_ARGS__)>(const QueryArgs&, hipStream_t);
 KNERF_FUSED_SHAPES(KNERF_X)
 #undef KNERF_X
 
@@ -188,6 +233,15 @@ KNERF_FUSED_SHAPES(KNERF_X)
 hipError_t launch_query(const QueryArgs& a, hipStream_t stream) {
     switch (a.shape) {
 #define KNERF_X(I, ...) case I: return launch_query_t<KNERF_SHAPE_T(__VA_ARGS__)>(a, stream);
+        KNERF_FUSED_SHAPES(KNERF_X)
+#undef KNERF_X
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_query_list(const QueryArgs& a, hipStream_t stream) {
+    switch (a.shape) {
+#define KNERF_X(I, ...) case I: return launch_query_list_t<KNERF_SHAPE_T(__VA_ARGS__)>(a, stream);
         KNERF_FUSED_SHAPES(KNERF_X)
 #undef KNERF_X
         default: return hipErrorInvalidValue;

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from ... import parallel
-from ...runtime import COARSE, FINE, KnerfContext, NonFiniteGradientError, marching_cubes  # noqa: F401
+from ...runtime import COARSE, FINE, OCCUPANCY_OUTSIDE, KnerfContext, NonFiniteGradientError, marching_cubes, occupancy_from_grid, occupancy_spec  # noqa: F401
 from .metrics import Mean, MetricLogs, MetricState
 from .mlp import NeRFMLP
 from .utils import NeRFUtils
@@ -335,6 +335,60 @@ class NeRF:
             return verts, faces, normals
         colors = self.query(verts, -normals, net)[0]
         return verts, faces, normals, colors
+
+    # ------------------------------------------------------------------ empty-space skipping for rendering (extension)
+    def build_occupancy_grid(self, resolution=128, bounds=((-1.5,) * 3, (1.5,) * 3), threshold=0.0, dilation=1, outside="occupied"):
+        """An occupancy grid for each net from its own density_grid(resolution + 1, bounds): a cell is occupied if one of its 8 corners
+        has sigma > threshold, then dilated by `dilation` cells (0..8).  Both grids are attached (set_occupancy_grid) and returned as
+        {"coarse": bool [cx, cy, cz], "fine": ...} NumPy arrays.  From then on every render (predict_and_render_images,
+        predict_and_render_chunk, test_step / evaluate) runs each MLP only on samples in its occupied cells; training never skips.
+        A heuristic: density between lattice points can be missed, the dilation is the margin.  The grids hold the weights as they
+        are now (training does not update them) and are not saved by save_model."""
+        cells = (resolution,) * 3 if isinstance(resolution, (int, np.integer)) else \
+            (tuple(resolution) if isinstance(resolution, (tuple, list)) else ())
+        if len(cells) != 3 or any(isinstance(c, bool) or int(c) != c or not 1 <= int(c) <= 1024 for c in cells):
+            raise ValueError(f"resolution must be an int or three ints, each 1..1024 cells; got {resolution!r}")
+        if outside not in OCCUPANCY_OUTSIDE:
+            raise ValueError(f"outside must be 'occupied' or 'empty', got {outside!r}")
+        if isinstance(dilation, bool) or not isinstance(dilation, (int, np.integer)) or not 0 <= dilation <= 8:
+            raise ValueError(f"dilation must be an integer 0..8, got {dilation!r}")
+        if not np.isfinite(float(threshold)):
+            raise ValueError(f"threshold must be finite, got {threshold!r}")
+        res, lo, hi = self._grid_spec(tuple(int(c) + 1 for c in cells), bounds)
+        self._field_net("fine")
+        grids = {}
+        for name in ("coarse", "fine"):
+            grids[name] = occupancy_from_grid(self.density_grid(res, (lo, hi), name), float(threshold), int(dilation))
+        for name in ("coarse", "fine"):
+            self.set_occupancy_grid(name, grids[name], (lo, hi), outside=outside)
+        return grids
+
+    def set_occupancy_grid(self, net, occupied, bounds=((-1.5,) * 3, (1.5,) * 3), outside="occupied"):
+        """Attach a boolean occupancy grid [cx, cy, cz] (1..1024 cells per axis) over bounds = (lo[3], hi[3]) to net "coarse" or
+        "fine"; None detaches it.  outside: "occupied" or "empty" for samples outside the box (include/knerf.h knerf_set_occupancy)."""
+        if occupied is not None:
+            try:
+                lo, hi = bounds
+            except (TypeError, ValueError):
+                raise ValueError(f"bounds must be (lo[3], hi[3]); got {bounds!r}") from None
+            occupancy_spec(occupied, lo, hi, outside)            # ValueError on a bad grid, box or policy (before the compile check)
+        n = self._field_net(net)
+        if occupied is None:
+            self._ctx.set_occupancy(n, None)
+        else:
+            self._ctx.set_occupancy(n, occupied, lo, hi, outside)
+
+    def clear_occupancy_grid(self):
+        """Detach both nets' grids: renders are dense again"""
+        for name in ("coarse", "fine"):
+            self.set_occupancy_grid(name, None)
+
+    def occupancy_stats(self, reset=True):
+        """{"coarse": (live, total), "fine": (live, total)}: samples of the render passes in occupied cells / samples those passes
+        considered, since the last reset"""
+        self._field_net("fine")
+        c, f = self._ctx.occupancy_stats(reset)
+        return {"coarse": c, "fine": f}
 
     def predict_and_render_images(self, rays, u=None, outputs=None):
         """nerf.py:229-304: returns (coarse_results, fine_results), each {image [B,H,W,3], depth [B,H,W], weights [B,H,W,S]}.

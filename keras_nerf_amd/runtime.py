@@ -473,6 +473,28 @@ class KnerfContext:
         return sig, col
 
 
+    # ---- empty-space skipping for rendering (extension: knerf_set_occupancy / knerf_occupancy_stats)
+    def set_occupancy(self, net: int, occupied, lo=None, hi=None, outside: str = "occupied"):
+        """Attach an occupancy grid to net `net`'s render passes: occupied = bool [cx, cy, cz] (NumPy or torch; 1..1024 cells per axis)
+        over the box [lo, hi]; outside = "occupied" or "empty" (samples outside the box).  None detaches the net's grid.  Render passes
+        of that net then run the MLP only on samples in occupied cells (include/knerf.h); training is not affected."""
+        if net not in (COARSE, FINE):
+            raise ValueError(f"net must be {COARSE} (coarse) or {FINE} (fine), got {net!r}")
+        if occupied is None:
+            self._check(self.lib.knerf_set_occupancy(self._ctx, self._stream(), int(net), None, None, None, None, 0))
+            return
+        words, cells, lo3, hi3, out_empty = occupancy_spec(occupied, lo, hi, outside)
+        bits = torch.as_tensor(words.view(np.int32)).to(self.device)
+        self._check(self.lib.knerf_set_occupancy(self._ctx, self._stream(), int(net), _ptr(bits), (C.c_int32 * 3)(*cells),
+                                                 (C.c_float * 3)(*lo3), (C.c_float * 3)(*hi3), out_empty))
+
+    def occupancy_stats(self, reset: bool = True):
+        """((live, total) samples of the coarse render passes, (live, total) of the fine ones) since the last reset: live = samples in
+        occupied cells (their MLP output is kept), total = samples of passes that had a grid"""
+        a, b = (C.c_int64 * 2)(), (C.c_int64 * 2)()
+        self._check(self.lib.knerf_occupancy_stats(self._ctx, self._stream(), a, b, int(reset)))
+        return (a[0], b[0]), (a[1], b[1])
+
     def zero_grads(self):
         self._check(self.lib.knerf_zero_grads(self._ctx, self._stream()))
 
@@ -543,3 +565,66 @@ def marching_cubes(grid: torch.Tensor, threshold: float, lo, hi, normals: bool =
         chk(lib.knerf_marching_cubes(stream, _ptr(grid), rx, ry, rz, lo3, hi3, float(threshold), _ptr(ws), C.byref(nbytes), counts,
                                      _ptr(verts), _ptr(faces), _ptr(nrm)))
     return verts, faces, nrm
+
+
+OCCUPANCY_OUTSIDE = ("occupied", "empty")
+
+
+def pack_occupancy(occupied: np.ndarray) -> np.ndarray:
+    """bool [cx, cy, cz] -> little-endian uint32 words: bit (i cy + j) cz + k is bit b % 32 of word b // 32 (padding bits 0)"""
+    flat = np.ascontiguousarray(occupied, dtype=bool).reshape(-1)
+    pad = -flat.size % 32
+    if pad:
+        flat = np.concatenate([flat, np.zeros(pad, dtype=bool)])
+    return np.packbits(flat, bitorder="little").view("<u4").astype(np.uint32)
+
+
+def unpack_occupancy(words, cells) -> np.ndarray:
+    """the inverse of pack_occupancy: uint32 words -> bool [cx, cy, cz]"""
+    w = np.ascontiguousarray(np.asarray(words).astype("<u4"))
+    n = int(np.prod(cells))
+    return np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool).reshape(tuple(int(c) for c in cells))
+
+
+def occupancy_spec(occupied, lo, hi, outside="occupied"):
+    """validated (words uint32, cells, lo[3], hi[3], outside_empty) of a grid for knerf_set_occupancy; ValueError on bad arguments"""
+    if isinstance(occupied, torch.Tensor):
+        occupied = occupied.detach().cpu().numpy()
+    occ = np.asarray(occupied)
+    if occ.dtype != np.bool_:
+        raise ValueError(f"occupancy: the grid must be boolean, got dtype {occ.dtype}")
+    if occ.ndim != 3 or not all(1 <= c <= 1024 for c in occ.shape):
+        raise ValueError(f"occupancy: the grid must be [cx, cy, cz] with 1..1024 cells per axis, got shape {occ.shape}")
+    if outside not in OCCUPANCY_OUTSIDE:
+        raise ValueError(f"occupancy: outside must be 'occupied' or 'empty', got {outside!r}")
+    try:
+        lo3, hi3 = [float(v) for v in lo], [float(v) for v in hi]
+    except TypeError:
+        raise ValueError(f"occupancy: lo and hi must be three numbers each, got {lo!r} / {hi!r}") from None
+    if len(lo3) != 3 or len(hi3) != 3 or not all(np.isfinite(np.float32(v)) for v in lo3 + hi3) or \
+            not all(np.float32(h) > np.float32(l) for l, h in zip(lo3, hi3)):
+        raise ValueError(f"occupancy: need finite lo[3] < hi[3] on every axis, got {lo!r} / {hi!r}")
+    return pack_occupancy(occ), tuple(int(c) for c in occ.shape), lo3, hi3, int(outside == "empty")
+
+
+def occupancy_from_grid(sigma: torch.Tensor, threshold: float = 0.0, dilation: int = 1) -> np.ndarray:
+    """knerf_occupancy_from_grid on a device fp32 lattice sigma [rx, ry, rz] (contiguous; 2..1025 per axis): bool [rx-1, ry-1, rz-1],
+    a cell occupied if one of its 8 corners has sigma > threshold, then dilated by `dilation` cells (0..8, Chebyshev distance).  A
+    heuristic: density between lattice points can be missed; the dilation is the margin."""
+    if not isinstance(sigma, torch.Tensor) or sigma.dtype != torch.float32 or sigma.dim() != 3 or not sigma.is_cuda:
+        raise ValueError("occupancy_from_grid: sigma must be a float32 device tensor [rx, ry, rz]")
+    if not all(2 <= r <= 1025 for r in sigma.shape):
+        raise ValueError(f"occupancy_from_grid: need 2 <= resolution <= 1025 per axis (1..1024 cells), got {tuple(sigma.shape)}")
+    if isinstance(dilation, bool) or int(dilation) != dilation or not 0 <= int(dilation) <= 8:
+        raise ValueError(f"occupancy_from_grid: dilation must be an integer 0..8, got {dilation!r}")
+    if not np.isfinite(float(threshold)):
+        raise ValueError(f"occupancy_from_grid: threshold must be finite, got {threshold!r}")
+    sigma = sigma.contiguous()
+    cells = tuple(int(r) - 1 for r in sigma.shape)
+    words = torch.zeros(((int(np.prod(cells)) + 31) // 32,), device=sigma.device, dtype=torch.int32)
+    lib = _lib.load()
+    stream = C.c_void_p(torch.cuda.current_stream(sigma.device).cuda_stream)
+    rc = lib.knerf_occupancy_from_grid(stream, _ptr(sigma), *(int(r) for r in sigma.shape), float(threshold), int(dilation), _ptr(words))
+    if rc != 0:
+        raise KnerfError(f"knerf_occupancy_from_grid failed ({rc})")
+    return unpack_occupancy(words.cpu().numpy().view(np.uint32), cells)
