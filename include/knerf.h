@@ -157,6 +157,8 @@ int knerf_zero_grads(knerf_ctx* ctx, void* stream);
  *                            failing hipMalloc -- so that the two fall-backs above can be exercised without filling the memory.
  *   "wgrad_group_max"   1..64, "wgrad_group_gb" >= 0: chunks per coarse weight-gradient launch of knerf_train_batch and the memory
  *                            budget of the workspaces that takes (defaults 4 and 40 GB; 1 or 0 = one launch per chunk).
+ *   "occupancy_train"   0/1  (default 0) train passes of a net that has an occupancy grid attached skip its empty cells exactly as
+ *                            render passes do (see "Empty-space skipping" below); 0, or no grid: training is unchanged, bit for bit.
  *   "wgrad_cost0".."wgrad_cost<n_layers>": relative cost per sample tile of the n_layers + 1 weight-gradient jobs (nine for the default shape) (workgroups are dealt out in that
  *                            proportion; tuning sweeps).
  * knerf_get_option also answers "skip_dead_tiles_active", "wgrad_group" (of the current workspaces), "general_shape_path" and
@@ -246,8 +248,9 @@ int knerf_marching_cubes(void* stream, const float* grid, int rx, int ry, int rz
  * fine grid); every other sample gets raw = (0, 0, 0, 0): sigma = 0, alpha = 0, compositing weight exactly 0.  Compositing, the sampler
  * and the outputs work as before; the fine sampler takes the coarse weights that come out of this, so t_fine may differ from the dense
  * render.  A sample that is evaluated gets the bits the dense render (and knerf_query_points) gives it.
- *   Applies to:     knerf_render_chunk, knerf_render_batch.
- *   Never applies:  knerf_train_chunk, knerf_train_batch, knerf_forward_chunk, knerf_query_points, knerf_query_grid (training never skips).
+ *   Applies to:     knerf_render_chunk, knerf_render_batch; and, while option "occupancy_train" is 1, knerf_train_chunk and
+ *                   knerf_train_batch.
+ *   Never applies:  knerf_forward_chunk, knerf_query_points, knerf_query_grid; nor training while "occupancy_train" is 0 (the default).
  * Cell lookup of sample p = __fadd_rn(o, __fmul_rn(d, t)) (the render path's two roundings), per axis:
  *   u = __fmul_rn(__fsub_rn(p, lo), scale), scale = fp32(cells / (hi - lo)) computed in double on the host; i = floor(u).
  *   Outside the box: u < 0, i >= cells or u NaN on any axis; then the `outside` policy decides (occupied, or empty).
@@ -255,7 +258,14 @@ int knerf_marching_cubes(void* stream, const float* grid, int rx, int ry, int rz
  * Fused shapes compact the live samples (an ordered scan) and run the fused MLP on that list only; the general-shape path
  * (shapes without fused kernels, KNERF_FLAG_FORCE_GENERIC) runs its MLP over every sample and zeroes the dead ones: the same outputs
  * without the speed-up.  The compaction runs under the net's forward profile class (knerf_profile_read classes 0 / 1).
- * The grid is the caller's: training does not update it. */
+ * Training behind a grid ("occupancy_train" = 1): every train pass of net n treats the samples in n's empty cells exactly as a render
+ * does: raw = (0, 0, 0, 0) and the MLP is not evaluated there.  Their raw is a constant, so no gradient reaches the MLP from them; loss
+ * and gradients are those of this masked field.  Fused shapes run the training forward, dgrad and weight gradients on the compacted
+ * list of live samples (in 32-sample tiles that may straddle rays); the general-shape path runs densely, zeroes raw and dL/draw at the
+ * dead samples and gives the same results without the speed-up.  With every cell occupied and "deterministic" on, losses, images and
+ * gradients are bit-identical to training without a grid.  knerf_occupancy_train_stats counts these passes.
+ * The grid is the caller's: training does not update it (knerf_occupancy_decay_max and knerf_occupancy_from_grid build the next one from
+ * the field on the device; the Python package's OccupancyGridUpdater does so during fit). */
 /* knerf_set_occupancy -- extension, no reference counterpart.  bits: DEVICE uint32 [ceil(cx cy cz / 32)], copied into a buffer the
  * context owns (on `stream`); NULL detaches the net's grid.  cells, lo, hi: HOST [3]; 1 <= cells <= 1024 and finite hi > lo per axis.
  * outside_empty: 0 = a sample outside the box is occupied, 1 = empty.  KNERF_ERR_INVALID on bad arguments and on a
@@ -271,6 +281,13 @@ int knerf_occupancy_from_grid(void* stream, const float* sigma, int rx, int ry, 
  * MLP output is kept (occupied), total[n] = samples those passes considered (passes without a grid are not counted).
  * Synchronises `stream`. */
 int knerf_occupancy_stats(knerf_ctx* ctx, void* stream, int64_t* live, int64_t* total, int reset);
+/* knerf_occupancy_train_stats -- extension, no reference counterpart.  As knerf_occupancy_stats, for the TRAIN passes that ran behind a
+ * grid ("occupancy_train" = 1): live[n] = samples whose MLP was evaluated, total[n] = samples those passes considered.  Render passes
+ * are not counted here, train passes not in knerf_occupancy_stats.  Synchronises `stream`. */
+int knerf_occupancy_train_stats(knerf_ctx* ctx, void* stream, int64_t* live, int64_t* total, int reset);
+/* knerf_occupancy_decay_max -- extension, no reference counterpart (Instant-NGP's density EMA).  Context-free.  state, sigma: DEVICE fp32
+ * [n]; state[i] = max(decay * state[i], sigma[i]) (one rounding for the product), on `stream`.  Needs 0 <= decay <= 1. */
+int knerf_occupancy_decay_max(void* stream, float* state, const float* sigma, uint64_t n, float decay);
 
 /* Diagnostics (layout tables, workspace views, hardware-fact and bandwidth probes) are NOT part of this library: they are
  * declared in include/knerf_debug.h and built into libknerf_probe.so for tests/ and tools/ only. */

@@ -71,6 +71,8 @@ SIGNATURES = {
     "knerf_set_occupancy": (C.c_int, [_P, _P, C.c_int, _P, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]),
     "knerf_occupancy_from_grid": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
     "knerf_occupancy_stats": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
+    "knerf_occupancy_train_stats": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
+    "knerf_occupancy_decay_max": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_float]),
 }
 
 _lib = None

@@ -8,7 +8,7 @@ libknerf_probe.so  diagnostics for tests/ and tools/ (include/knerf_debug.h): la
 
 --add-shape (or KNERF_ADD_SHAPES="NL,SK,U;NL,SK,U,LX,LD" in the environment): further NeRF(n_layers, skip_layer, dense_units [, pos_emb_xyz,
 pos_emb_dir]) shapes for the fused kernels beside the built-in list of csrc/layout.h (dense_units 256, 128 or 64; encodings: the reference's
-10 / 4 unless given, pos_emb_dir <= 8; since round 6 also trunks that end in a concat, e.g. 9,4,256); four more hipcc runs (the three training kernels and the query kernel) and about 1 MB of library each.  Shapes not in the list still work: they run on the general-shape kernels.
+10 / 4 unless given, pos_emb_dir <= 8; since round 6 also trunks that end in a concat, e.g. 9,4,256); five more hipcc runs (the three training kernels, the query kernel and the list-mode training forward) and about 1 MB of library each.  Shapes not in the list still work: they run on the general-shape kernels.
 """
 from __future__ import annotations
 
@@ -21,11 +21,12 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libknerf_hip.so")
 PROBE_LIB = os.path.join(HERE, "libknerf_probe.so")
 SOURCES = ["knerf_api.hip", "mlp_fwd.hip", "mlp_bwd.hip", "wgrad.hip", "generic.hip", "composite.hip", "sampler.hip", "optim.hip",
-           "raygen.hip", "utils_ops.hip", "query.hip", "mesh.hip", "occupancy.hip"]
+           "raygen.hip", "utils_ops.hip", "query.hip", "mesh.hip", "occupancy.hip", "train_list.hip"]
 # The three big kernels are templates on the trunk shape (csrc/layout.h KNERF_FUSED_SHAPES): each of these sources is compiled once
 # per shape with -DKNERF_SHAPE_SLICE=<index> (that translation unit then defines the kernels of its shape only; slice 0 also holds
 # the run-time dispatchers), so the shapes build in parallel and the default shape's object is what it was before the others existed.
-SLICED = {"mlp_fwd.hip", "mlp_bwd.hip", "wgrad.hip", "query.hip"}     # query.hip: the inference chain behind point / grid queries
+SLICED = {"mlp_fwd.hip", "mlp_bwd.hip", "wgrad.hip", "query.hip", "train_list.hip"}     # query.hip: the inference chain behind point / grid queries;
+# train_list.hip: the training forward on the list of live samples behind an occupancy grid
 N_BUILTIN_SHAPES = 14   # = kNumBuiltinShapes (csrc/layout.h static_asserts it); knerf_api.hip checks the total against KNERF_N_SHAPE_SLICES
 MAX_EXTRA_SHAPES = 36   # a build-time budget, not a limit of csrc/layout.h (one more instantiation of the three big kernels each)
 PROBE_SOURCES = ["debug_api.hip", "probe.hip"]
@@ -34,7 +35,7 @@ PROBE_SOURCES = ["debug_api.hip", "probe.hip"]
 # round 6: a concat behind the LAST trunk layer ((n_layers - 1) % skip_layer == 0): the head takes [h ; xyz_enc ; dir_enc]
 XSHAPES = ["6,3,128", "8,2,128", "8,4,256,6,2", "8,4,256,12,4", "8,4,128,5,1", "4,2,256,16,3",
            "6,3,64", "8,4,64,6,2", "8,4,256,10,8", "8,4,128,10,6", "9,4,256", "5,2,128", "5,4,64,6,2"]
-HEADERS = ["chain.h", "ctx.h", "kernels.h", "layout.h", "bwd_body.h", "wgrad_body.h", "generic.h", "query.h", "mesh_table.h", "occupancy.h", os.path.join("..", "..", "include", "knerf.h"),
+HEADERS = ["chain.h", "ctx.h", "kernels.h", "layout.h", "bwd_body.h", "wgrad_body.h", "generic.h", "query.h", "mesh_table.h", "occupancy.h", "train_list.h", os.path.join("..", "..", "include", "knerf.h"),
            os.path.join("..", "..", "include", "knerf_debug.h")]
 # -ffp-contract=off: the parity-critical fp32 arithmetic (ray points, sampler, compositing) must round like the
 # reference's separate mul/add ops; fused multiply-adds are written explicitly (__builtin_fmaf) where wanted.

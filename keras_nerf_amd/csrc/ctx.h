@@ -95,6 +95,12 @@ struct knerf_ctx {
     Occ occ[2];
     char* occ_ws = nullptr; int ws_occ_rays = 0;
     long long* occ_stats = nullptr;     // [net][2]: samples whose MLP output is live (occupied), samples considered
+    // training behind the grids (option "occupancy_train"; train_list.h): the compacted raw / dL/draw of a training pass and their size in
+    // rays, allocated only while the option is on and a grid is attached (the compaction workspace occ_ws then covers the training size too);
+    // occ_train_stats as occ_stats, for the train passes
+    bool occ_train = false;
+    float *occ_raw_c = nullptr, *occ_draw_c = nullptr; int ws_occ_train_rays = 0;
+    long long* occ_train_stats = nullptr;
     // run-time options (knerf_set_option)
     bool deterministic = false;         // per-workgroup partial sums + ordered second pass instead of fp32 atomics (wgrad, loss)
     bool skip_dead = true;              // dgrad / wgrad skip 32-sample tiles whose dL/d(rgb, sigma) is exactly zero (exact; +0.3 % when nothing is dead)

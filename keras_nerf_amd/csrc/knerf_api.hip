@@ -17,6 +17,7 @@
 #include "layout.h"
 #include "occupancy.h"
 #include "query.h"
+#include "train_list.h"
 
 using namespace knerf;
 
@@ -142,6 +143,9 @@ OccWs occ_ws_view(char* base, long long n) {
     return w;
 }
 bool occ_attached(const knerf_ctx* ctx) { return ctx->occ[0].bits || ctx->occ[1].bits; }
+// training behind the grids (option "occupancy_train"): for one net / for either net
+bool occ_train_on(const knerf_ctx* ctx, int net) { return ctx->occ_train && ctx->occ[net].bits; }
+bool occ_train_any(const knerf_ctx* ctx) { return ctx->occ_train && occ_attached(ctx); }
 
 int ensure_ws_impl(knerf_ctx* ctx, int n_rays, bool train, hipStream_t s, int group) {
     const int Na = ctx->cfg.n_coarse + ctx->cfg.n_fine;
@@ -192,16 +196,19 @@ int ensure_ws_impl(knerf_ctx* ctx, int n_rays, bool train, hipStream_t s, int gr
     }
     const bool grow_base = n_rays > ctx->ws_rays;
     const bool grow_train = train && (!ctx->ws_train || n_rays > ctx->ws_train_rays || group > ctx->ws_group);
-    // renders behind an occupancy grid: the compaction workspace (4 B + 1 bit per sample), only while a grid is attached
-    const bool grow_occ = !train && occ_attached(ctx) && n_rays > ctx->ws_occ_rays;
-    if (!grow_base && !grow_train && !grow_occ) return KNERF_OK;
+    // renders behind an occupancy grid: the compaction workspace (4 B + 1 bit per sample), only while a grid is attached; training
+    // behind one ("occupancy_train"): the same at the training size, and the compacted raw / dL/draw (32 B per sample)
+    const bool occ_tr = train && occ_train_any(ctx);
+    const bool grow_occ = (train ? occ_tr : occ_attached(ctx)) && n_rays > ctx->ws_occ_rays;
+    const bool grow_occ_train = occ_tr && n_rays > ctx->ws_occ_train_rays;
+    if (!grow_base && !grow_train && !grow_occ && !grow_occ_train) return KNERF_OK;
     if (ctx->ws_limit_gb > 0) {
         const int Rt = n_rays > ctx->ws_train_rays ? n_rays : ctx->ws_train_rays;
         const size_t tl = group == 1 ? tiles_for((long long)Rt * Na) : (size_t)group * tiles_for((long long)Rt * ctx->cfg.n_coarse) + tiles_for((long long)Rt * Na);
         const double base_b = grow_base ? (double)n_rays * Na * 20 + (double)n_rays * (ctx->cfg.n_coarse * 4 + 32) : 0.0;
         const double train_b = grow_train ? (double)Rt * Na * 16 + (double)saved_region_bytes(tl, ctx->si.act_blocks) +
                                                 (double)saved_region_bytes(tl, ctx->si.mask_blocks) + (double)saved_region_bytes(tl, ctx->si.dz_blocks) : 0.0;
-        const double occ_b = grow_occ ? (double)occ_ws_bytes((long long)n_rays * Na) : 0.0;
+        const double occ_b = (grow_occ ? (double)occ_ws_bytes((long long)n_rays * Na) : 0.0) + (grow_occ_train ? (double)n_rays * Na * 32 : 0.0);
         if (int r = over_limit(ctx, base_b + train_b + occ_b)) return r;
     }
     HIPCHK(hipStreamSynchronize(s));               // nothing enqueued earlier may still use the buffers that are freed below
@@ -221,6 +228,13 @@ int ensure_ws_impl(knerf_ctx* ctx, int n_rays, bool train, hipStream_t s, int gr
         ctx->ws_occ_rays = 0;
         HIPCHK(hipMalloc(&ctx->occ_ws, occ_ws_bytes((long long)n_rays * Na)));
         ctx->ws_occ_rays = n_rays;
+    }
+    if (grow_occ_train) {
+        free_dev(ctx->occ_raw_c); free_dev(ctx->occ_draw_c);
+        ctx->ws_occ_train_rays = 0;
+        HIPCHK(hipMalloc(&ctx->occ_raw_c, (size_t)n_rays * Na * 4 * sizeof(float)));
+        HIPCHK(hipMalloc(&ctx->occ_draw_c, (size_t)n_rays * Na * 4 * sizeof(float)));
+        ctx->ws_occ_train_rays = n_rays;
     }
     if (grow_train) {
         const int R = n_rays > ctx->ws_train_rays ? n_rays : ctx->ws_train_rays;
@@ -358,20 +372,23 @@ int launch_wgrad_tiles(knerf_ctx* ctx, hipStream_t s, int net, size_t tile0, siz
 // (false: the caller launches it later over several passes, launch_wgrad_tiles)
 // group_count: (default-mode skipping, coarse pass of a grouped launch) the group's counter: the pass's live tiles are appended to
 // ctx->tile_list_g as well, as indices relative to the group's first region (+ tile0)
-// render: a pass of knerf_render_chunk -- the net's occupancy grid, if one is attached, applies (never to training, forward_chunk or queries)
+// render: a pass of knerf_render_chunk -- the net's occupancy grid, if one is attached, applies; to training passes only under option
+// "occupancy_train" (never to forward_chunk or queries)
 int run_pass(knerf_ctx* ctx, hipStream_t s, int net, const float* o, const float* d, const float* t, int R, int S,
              float* image, float* depth, float* weights, const float* target, float inv_chunks, float* loss,
              size_t tile0 = 0, bool wgrad_now = true, int* group_count = nullptr, bool render = false) {
     const bool train = target != nullptr;
-    const knerf_ctx::Occ* og = render && !train && ctx->occ[net].bits ? &ctx->occ[net] : nullptr;
+    const knerf_ctx::Occ* og = ((render && !train) || (train && occ_train_on(ctx, net))) && ctx->occ[net].bits ? &ctx->occ[net] : nullptr;
+    // fused training behind a grid: forward, dgrad and weight gradients on the compacted list of live samples (train_list.h)
+    const bool compact = og && train && !ctx->generic;
     OccArgs oa{};
     if (og) {
         oa.grid.bits = og->bits; oa.grid.outside_empty = og->outside_empty;
         for (int c = 0; c < 3; ++c) { oa.grid.cells[c] = og->cells[c]; oa.grid.lo[c] = og->lo[c]; oa.grid.scale[c] = og->scale[c]; }
         oa.o = o; oa.d = d; oa.t = t; oa.n = (long long)R * S; oa.S = S; oa.raw = ctx->raw;
-        oa.stats = ctx->occ_stats + 2 * (net == KNERF_COARSE ? 0 : 1);
+        oa.stats = (train ? ctx->occ_train_stats : ctx->occ_stats) + 2 * (net == KNERF_COARSE ? 0 : 1);
         if (!ctx->generic && oa.n >= (1ll << 31))       // the list holds int32 sample indices
-            return fail(ctx, KNERF_ERR_INVALID, "render behind an occupancy grid: a pass of 2^31 samples or more (use a smaller ray_chunks)");
+            return fail(ctx, KNERF_ERR_INVALID, "pass behind an occupancy grid: a pass of 2^31 samples or more (use a smaller ray_chunks)");
     }
     FwdArgs fa{};
     fa.stream = ctx->net[net].fwd_stream; fa.bias = ctx->net[net].bias;
@@ -384,6 +401,16 @@ int run_pass(knerf_ctx* ctx, hipStream_t s, int net, const float* o, const float
         HIPCHK(gen::forward(ctx->gplan, ctx->gws, ctx->gnet[net], ctx->net[net].w, o, d, t, fa.n_samples, S, ctx->raw, s));
         // general-shape path: the MLP ran on every sample; the dead ones are zeroed behind it (same outputs, no speed-up)
         if (og) HIPCHK(launch_occupancy_mark(oa, s));
+    } else if (compact) {
+        // fused training: ordered compaction of the live samples, then the SAVE forward on the list alone; saved tensors of compacted
+        // tile i / 32, raw to raw[list[i]]
+        ProfScope ps(ctx, s, net == KNERF_COARSE ? P_FWD_C : P_FWD_F);
+        const OccWs w = occ_ws_view(ctx->occ_ws, oa.n);
+        oa.masks = w.masks; oa.blk_cnt = w.blk_cnt; oa.blk_off = w.blk_off; oa.list = w.list; oa.count = w.count;
+        HIPCHK(launch_occupancy_mark(oa, s));
+        TrainListArgs la{};
+        la.f = fa; la.list = w.list; la.count = w.count;
+        HIPCHK(launch_mlp_fwd_list(la, s));
     } else if (og) {
         // fused path: ordered compaction of the live samples, then the fused MLP on the list alone (query.hip list mode)
         ProfScope ps(ctx, s, net == KNERF_COARSE ? P_FWD_C : P_FWD_F);
@@ -403,7 +430,8 @@ int run_pass(knerf_ctx* ctx, hipStream_t s, int net, const float* o, const float
     ca.draw = train ? ctx->draw : nullptr; ca.loss = loss; ca.R = R; ca.S = S; ca.white = ctx->cfg.white_background;
     ca.grad_scale = 2.0f / (3.0f * (float)R) * inv_chunks;
     ca.loss_scale = inv_chunks / (3.0f * (float)R);
-    const bool skip = train && skipping(ctx);
+    // (the compacted path makes its own list of live tiles behind compositing, below)
+    const bool skip = train && skipping(ctx) && !compact;
     const size_t n_tiles = tiles_for(fa.n_samples);
     int* live_count = nullptr;
     if (skip && ctx->deterministic) {
@@ -421,9 +449,23 @@ int run_pass(knerf_ctx* ctx, hipStream_t s, int net, const float* o, const float
         // deterministic mode: the pass's live tiles (indices relative to tile0) in ascending order; the padding tiles behind the
         // last real one count as dead
         if (ca.tile_flags) { if (int r = compact_tiles(ctx, s, ca.tile_flags, (int)n_tiles, (int)n_tiles, (int)(fa.n_samples / kTile), ctx->tile_list, &live_count)) return r; }
+        if (compact) {
+            // raw and dL/draw of the live samples in list order (the last tile padded with zeros), one flag per compacted tile, then the ascending
+            // list of the flagged tiles -- in both modes.  Compacted tiles straddle rays, so the per-ray tile flags of compositing (which
+            // need S % 32 == 0) do not apply; the flags come from the gathered dL/draw instead, with the same dead-sample rule.
+            const OccWs w = occ_ws_view(ctx->occ_ws, oa.n);
+            HIPCHK(launch_occupancy_train_gather(w.list, w.count, ctx->raw, ctx->draw, ctx->occ_draw_c, ctx->occ_raw_c, ctx->tile_flags + tile0, fa.n_samples,
+                                                 (long long)n_tiles, ctx->skip_dead ? 1 : 0, s));
+            if (int r = compact_tiles(ctx, s, ctx->tile_flags + tile0, (int)n_tiles, (int)n_tiles, (int)n_tiles, ctx->tile_list, &live_count)) return r;
+        }
     }
     if (train && ctx->generic) {
         ProfScope ps(ctx, s, net == KNERF_COARSE ? P_BWD_C : P_BWD_F);
+        if (og) {              // general-shape path behind a grid: no gradient from the dead samples (the mark kernel zeroes dL/draw there)
+            OccArgs od = oa;
+            od.raw = ctx->draw; od.stats = nullptr;
+            HIPCHK(launch_occupancy_mark(od, s));
+        }
         if (ctx->deterministic && !ctx->partial) {       // general-shape path: the slab arena of generic.hip (the fused path's lives in launch_wgrad_tiles)
             HIPCHK(hipStreamSynchronize(s));
             HIPCHK(hipMalloc(&ctx->partial, gen::wgrad_partial_floats(ctx->gplan) * sizeof(float)));
@@ -436,8 +478,12 @@ int run_pass(knerf_ctx* ctx, hipStream_t s, int net, const float* o, const float
         ba.stream = ctx->net[net].bwd_stream; ba.raw = ctx->raw; ba.draw = ctx->draw; ba.mask = fa.mask; ba.dz = ctx->dz + saved_tile_off(tile0, ctx->si.dz_blocks);
         ba.n_samples = fa.n_samples; ba.net = fa.net; ba.shape = ctx->shape;
         if (skip) { ba.live = ctx->tile_list; ba.n_live = live_count; ba.stats = ctx->tile_stats + 4 * fa.net; }
+        if (compact) {
+            ba.raw = ctx->occ_raw_c; ba.draw = ctx->occ_draw_c; ba.live = ctx->tile_list; ba.n_live = live_count;
+            ba.stats = ctx->skip_dead ? ctx->tile_stats + 4 * fa.net : nullptr;
+        }
         { ProfScope ps(ctx, s, net == KNERF_COARSE ? P_BWD_C : P_BWD_F); HIPCHK(launch_mlp_bwd(ba, s)); }
-        if (wgrad_now) { if (int r = launch_wgrad_tiles(ctx, s, net, tile0, n_tiles, skip ? ctx->tile_list : nullptr, live_count)) return r; }
+        if (wgrad_now) { if (int r = launch_wgrad_tiles(ctx, s, net, tile0, n_tiles, skip || compact ? ctx->tile_list : nullptr, live_count)) return r; }
     }
     return KNERF_OK;
 }
@@ -679,6 +725,8 @@ int knerf_create(const knerf_config* cfg, knerf_ctx** out) {
     CREATECHK(hipMemset(ctx->tile_stats, 0, 8 * sizeof(long long)));
     CREATECHK(hipMalloc(&ctx->occ_stats, 4 * sizeof(long long)));
     CREATECHK(hipMemset(ctx->occ_stats, 0, 4 * sizeof(long long)));
+    CREATECHK(hipMalloc(&ctx->occ_train_stats, 4 * sizeof(long long)));
+    CREATECHK(hipMemset(ctx->occ_train_stats, 0, 4 * sizeof(long long)));
     CREATECHK(hipMalloc(&ctx->d_diag, 2 * sizeof(unsigned long long)));
     CREATECHK(hipHostMalloc(&ctx->h_diag, 4 * sizeof(long long), hipHostMallocDefault));
     ctx->h_diag[0] = ctx->h_diag[1] = ctx->h_diag[2] = ctx->h_diag[3] = 0;
@@ -741,6 +789,7 @@ int knerf_destroy(knerf_ctx* ctx) {
     free_dev(ctx->tile_flags); free_dev(ctx->tile_list); free_dev(ctx->tile_list_g); free_dev(ctx->tile_count); free_dev(ctx->tile_stats);
     free_dev(ctx->partial); free_dev(ctx->loss_partial); free_dev(ctx->d_job_wg0);
     free_dev(ctx->occ[0].bits); free_dev(ctx->occ[1].bits); free_dev(ctx->occ_ws); free_dev(ctx->occ_stats);
+    free_dev(ctx->occ_raw_c); free_dev(ctx->occ_draw_c); free_dev(ctx->occ_train_stats);
     free_dev(ctx->gws.act); free_dev(ctx->gws.dz); free_dev(ctx->gws.zs); free_dev(ctx->gws.zc); free_dev(ctx->gws.mask);
     for (int n = 0; n < 2; ++n) { free_dev(ctx->gnet[n].packed); free_dev(ctx->gnet[n].head); free_dev(ctx->gnet[n].gaux); }
     free_dev(ctx->call_net.head);
@@ -882,6 +931,16 @@ int knerf_occupancy_stats(knerf_ctx* ctx, void* stream, int64_t* live, int64_t* 
     return KNERF_OK;
 }
 
+int knerf_occupancy_train_stats(knerf_ctx* ctx, void* stream, int64_t* live, int64_t* total, int reset) {
+    if (!ctx || !live || !total) return KNERF_ERR_INVALID;
+    long long h[4] = {0, 0, 0, 0};
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    HIPCHK(hipMemcpy(h, ctx->occ_train_stats, sizeof(h), hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(ctx->occ_train_stats, 0, sizeof(h)));
+    for (int n = 0; n < 2; ++n) { live[n] = h[2 * n]; total[n] = h[2 * n + 1]; }
+    return KNERF_OK;
+}
+
 int knerf_sample_fine(knerf_ctx* ctx, void* stream, const float* t_coarse, const float* w_coarse, const float* u,
                       uint64_t seed, uint64_t stream_id, uint64_t ray_offset, int n_rays, float* t_out) {
     if (int r = check_rays(ctx, "sample_fine")) return r;
@@ -986,7 +1045,10 @@ int knerf_train_batch(knerf_ctx* ctx, void* stream, const float* o, const float*
     }
     const size_t tc = tiles_for((long long)ray_chunks * Nc);
     const bool skip = skipping(ctx);
-    if (skip) { if (int r = ensure_tile_counters(ctx, s, 2LL * C + (C + G - 1) / G + 8)) return r; }   // two passes per chunk + one per group
+    // coarse passes on the compacted path (occupancy_train): their flags lie at tile_flags + slot tc, a group's list is compacted from them
+    const bool occ_c = !ctx->generic && occ_train_on(ctx, KNERF_COARSE);
+    if (skip || (!ctx->generic && occ_train_any(ctx))) { if (int r = ensure_tile_counters(ctx, s, 2LL * C + (C + G - 1) / G + 8)) return r; }   // two passes per chunk + one per group
+    const bool append_g = G > 1 && skip && !ctx->deterministic && !occ_c;
     int* group_count = nullptr;
     for (int i = 0; i < C; ++i) {
         const size_t r0 = (size_t)i * ray_chunks;
@@ -1002,14 +1064,17 @@ int knerf_train_batch(knerf_ctx* ctx, void* stream, const float* o, const float*
             HIPCHK(hipMemsetAsync(ctx->grads, 0, nb, s));
         }
         // default-mode skipping: the coarse passes of a group append their live tiles to the group's list under one counter
-        if (G > 1 && skip && !ctx->deterministic && slot == 0) { if (int r = next_tile_counter(ctx, s, &group_count)) return r; }
+        if (append_g && slot == 0) { if (int r = next_tile_counter(ctx, s, &group_count)) return r; }
         if (int r = train_chunk_impl(ctx, s, o + r0 * 3, d + r0 * 3, t + r0 * Nc, target + r0 * 3, u ? u + r0 * Nf : nullptr, seed,
                                      (uint64_t)r0, ray_chunks, 1.0f / (float)C, loss, c_image ? c_image + r0 * 3 : nullptr,
-                                     f_image ? f_image + r0 * 3 : nullptr, slot, G, G > 1 && skip && !ctx->deterministic ? group_count : nullptr))
+                                     f_image ? f_image + r0 * 3 : nullptr, slot, G, append_g ? group_count : nullptr))
             return r;
         if (G > 1 && last) {                                        // the group's coarse weight gradients in one launch
             const int* live = nullptr; int* live_count = nullptr;
-            if (skip && ctx->deterministic) {                       // ascending list of the group's live tiles from its flags
+            if (occ_c) {                                            // compacted coarse passes: every flag of each region counts (zero past its list)
+                if (int r = compact_tiles(ctx, s, ctx->tile_flags, (int)((slot + 1) * tc), (int)tc, (int)tc, ctx->tile_list, &live_count)) return r;
+                live = ctx->tile_list;
+            } else if (skip && ctx->deterministic) {                // ascending list of the group's live tiles from its flags
                 if (int r = compact_tiles(ctx, s, ctx->tile_flags, (int)((slot + 1) * tc), (int)tc, ray_chunks * Nc / kTile, ctx->tile_list, &live_count)) return r;
                 live = ctx->tile_list;
             } else if (skip) {
@@ -1079,6 +1144,9 @@ int knerf_set_option(knerf_ctx* ctx, const char* name, double value) {
         ctx->grad_diag = value != 0;
     } else if (n == "skip_dead_tiles") {
         ctx->skip_dead = value != 0;               // ignored where it does not apply (general-shape path, sample counts not multiples of 32)
+    } else if (n == "occupancy_train") {
+        if (value != 0 && value != 1) return fail(ctx, KNERF_ERR_INVALID, "occupancy_train: 0 or 1");
+        ctx->occ_train = value != 0;               // applies to the nets with a grid attached (knerf_set_occupancy)
     } else if (n == "merge_chunk_rays") {
         if (value < 0 || value > 1048576) return fail(ctx, KNERF_ERR_INVALID, "merge_chunk_rays: 0..1048576");
         ctx->merge_rays = (int)value; ctx->merge_fail_rays = 0; if (ctx->generic) ctx->rmerge_fail_rays = 0;
@@ -1109,6 +1177,7 @@ int knerf_get_option(knerf_ctx* ctx, const char* name, double* value) {
     if (n == "deterministic") *value = ctx->deterministic;
     else if (n == "skip_dead_tiles") *value = ctx->skip_dead;
     else if (n == "grad_diagnostics") *value = ctx->grad_diag;
+    else if (n == "occupancy_train") *value = ctx->occ_train;
     else if (n == "skip_dead_tiles_active") *value = skipping(ctx);
     else if (n == "wgrad_group_max") *value = ctx->wgrad_group_max;
     else if (n == "merge_chunk_rays") *value = ctx->merge_rays;

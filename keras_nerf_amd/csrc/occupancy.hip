@@ -9,6 +9,8 @@
 // then the fused MLP on the list only (query.hip query_list_kernel).  The general-shape path runs its MLP over every sample and uses the
 // mark kernel alone to zero the dead ones.  The grid (128^3: 256 KB) stays in L2.
 //
+// Training behind a grid (option "occupancy_train") runs the same mark / scan / emit, then csrc/train_list.hip.
+//
 // occ_build_kernel (knerf_occupancy_from_grid, not on the hot path): a cell is occupied if one of its 8 lattice corners has
 // sigma > threshold, then dilated by `dilation` cells (Chebyshev): i.e. any lattice point of the cell's box grown by `dilation` on every
 // side, clipped to the lattice.  One thread per cell, one ballot per 64 cells = two words.
@@ -171,4 +173,23 @@ extern "C" int knerf_occupancy_from_grid(void* stream, const float* sigma, int r
     if (knerf::launch_occupancy_build(sigma, rx, ry, rz, threshold, dilation, reinterpret_cast<unsigned*>(bits), (hipStream_t)stream) != hipSuccess)
         return KNERF_ERR_HIP;
     return KNERF_OK;
+}
+
+namespace knerf {
+
+// Instant-NGP's density EMA, on the device: state = max(decay * state, sigma) (OccupancyGridUpdater keeps one state per net)
+__global__ __launch_bounds__(256) void occ_decay_max_kernel(float* state, const float* sigma, unsigned long long n, float decay) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    state[i] = fmaxf(__fmul_rn(decay, state[i]), sigma[i]);
+}
+
+}  // namespace knerf
+
+extern "C" int knerf_occupancy_decay_max(void* stream, float* state, const float* sigma, uint64_t n, float decay) {
+    if (!state || !sigma || n == 0 || n > (1ull << 40)) return KNERF_ERR_INVALID;
+    if (!(decay >= 0.f && decay <= 1.f)) return KNERF_ERR_INVALID;
+    hipLaunchKernelGGL(knerf::occ_decay_max_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, state, sigma,
+                       (unsigned long long)n, decay);
+    return hipGetLastError() == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
 }

@@ -10,7 +10,10 @@ replicas hold identical weights and `fit` has already averaged the logs); the ot
 runs ahead of a checkpoint that is still being written.  The barrier is reached even when rank 0's rendering, plotting or
 writing raises (try/finally: the error then surfaces on rank 0 instead of as a collective time-out everywhere else), and the
 "other test images" iterator walks a PRIVATE view of the dataset (own shuffle generator), so that its rank-0-only iteration
-never advances the generator from which every rank derives the shared batch order."""
+never advances the generator from which every rank derives the shared batch order.
+
+OccupancyGridUpdater -- extension, no reference counterpart: empty-space skipping during fit, with occupancy grids kept in step with the
+field as it learns (Instant-NGP's density EMA)."""
 from __future__ import annotations
 
 import logging
@@ -18,8 +21,10 @@ import os
 from csv import DictReader, DictWriter
 
 import numpy as np
+import torch
 
 from ... import parallel
+from ...runtime import COARSE, FINE, check_grid_args, occupancy_box, occupancy_words_from_grid
 
 
 def _np(x):
@@ -127,3 +132,72 @@ class NeRFTrainMonitor:
                 w.writeheader()
             w.writerow(new_logs)
         self.model.save_model(self.log_model_dir, weights_only=(epoch != 0))   # callback.py:220-222
+
+
+class OccupancyGridUpdater:
+    """Keeps one occupancy grid per net in step with the field during `fit` and trains behind them (NeRF.set_occupancy_training).
+
+    After `warmup_steps` training steps, and every `update_every` steps after that, for each net: sigma on the (resolution + 1)^3
+    lattice over `bounds` (NeRF.density_grid), state = max(decay * state, sigma) (the per-net density EMA, knerf_occupancy_decay_max),
+    the grid of `state` (a cell occupied if a corner exceeds `threshold`, dilated by `dilation` cells; knerf_occupancy_from_grid) and
+    attached to the net (KnerfContext.set_occupancy_words).  After the first update the option occupancy_train is on.  Everything is
+    enqueued on the device: the host never waits for the GPU (no read-back, no blocking copy).  The grids stay attached after `fit`, so
+    validation and later renders use them too (NeRF.clear_occupancy_grid detaches them).  Steps before the warm-up are the dense steps.
+
+    With threshold 0 a cell dies only where the EMA of sigma is exactly 0 at all its lattice corners and in the dilation margin (DESIGN.md
+    2.13).  Data parallel: every rank holds the same weights and builds the same grid with the same deterministic query."""
+
+    def __init__(self, update_every=16, warmup_steps=256, resolution=128, bounds=((-1.5,) * 3, (1.5,) * 3), threshold=0.0, dilation=1,
+                 decay=0.95, outside="occupied"):
+        for name, v, lo in (("update_every", update_every, 1), ("warmup_steps", warmup_steps, 0)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+                raise ValueError(f"OccupancyGridUpdater: {name} must be an integer >= {lo}, got {v!r}")
+        if isinstance(resolution, bool) or not isinstance(resolution, (int, np.integer)) or not 1 <= resolution <= 1024:
+            raise ValueError(f"OccupancyGridUpdater: resolution must be an integer 1..1024 (cells per axis), got {resolution!r}")
+        try:
+            lo3, hi3 = bounds
+        except (TypeError, ValueError):
+            raise ValueError(f"OccupancyGridUpdater: bounds must be (lo[3], hi[3]); got {bounds!r}") from None
+        _, self._lo, self._hi, _ = occupancy_box((int(resolution),) * 3, lo3, hi3, outside)
+        check_grid_args(threshold, dilation, "OccupancyGridUpdater")
+        if isinstance(decay, bool) or not isinstance(decay, (int, float, np.floating, np.integer)) or not 0.0 <= float(decay) <= 1.0:
+            raise ValueError(f"OccupancyGridUpdater: decay must be a number in [0, 1], got {decay!r}")
+        self.update_every, self.warmup_steps, self.resolution = int(update_every), int(warmup_steps), int(resolution)
+        self.threshold, self.dilation, self.decay, self.outside = float(threshold), int(dilation), float(decay), outside
+        self.model = None
+        self.steps = 0              # training steps seen (over every fit this callback took part in)
+        self.updates = 0            # grid updates made
+        self._state = {}            # per net: the density EMA on the lattice (device)
+
+    def set_model(self, model):
+        self.model = model
+
+    def due(self, steps: int) -> bool:
+        """whether the grids are rebuilt once `steps` training steps have completed"""
+        return steps >= self.warmup_steps and (steps - self.warmup_steps) % self.update_every == 0
+
+    def on_train_begin(self, logs=None):
+        if self.steps == 0 and self.due(0):         # warmup_steps = 0: a grid from the start
+            self.update()
+
+    def on_train_batch_end(self, batch, logs=None):
+        self.steps += 1
+        if self.due(self.steps):
+            self.update()
+
+    def update(self):
+        """one update of both grids from the current weights (enqueued; nothing waits)"""
+        m = self.model
+        ctx = m._ctx
+        res = self.resolution + 1
+        for name, net in (("coarse", COARSE), ("fine", FINE)):
+            sigma = m.density_grid(res, (self._lo, self._hi), name)
+            state = self._state.get(name)
+            if state is None:
+                state = self._state[name] = torch.zeros_like(sigma)
+            ctx.occupancy_decay_max(state, sigma, self.decay)
+            words = occupancy_words_from_grid(state, self.threshold, self.dilation)
+            ctx.set_occupancy_words(net, words, (self.resolution,) * 3, self._lo, self._hi, self.outside)
+        if self.updates == 0:
+            m.set_occupancy_training(True)
+        self.updates += 1

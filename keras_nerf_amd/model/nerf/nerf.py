@@ -390,6 +390,23 @@ class NeRF:
         c, f = self._ctx.occupancy_stats(reset)
         return {"coarse": c, "fine": f}
 
+    def set_occupancy_training(self, on):
+        """Train behind the attached grids (option occupancy_train, include/knerf.h): with on=True every train pass of a net that has
+        a grid treats the samples in its empty cells as renders do (raw = 0, the MLP not evaluated there, no gradient from them); nets
+        without a grid train as before.  False: training is dense again (the grids stay attached for renders).  OccupancyGridUpdater
+        (callback.py) builds the grids during fit and turns this on."""
+        if not isinstance(on, (bool, np.bool_)) and on not in (0, 1):
+            raise ValueError(f"set_occupancy_training: on must be True / False (or 1 / 0), got {on!r}")
+        self._field_net("fine")
+        self._ctx.set_option("occupancy_train", int(bool(on)))
+
+    def occupancy_train_stats(self, reset=True):
+        """{"coarse": (live, total), "fine": (live, total)}: samples of the TRAIN passes behind a grid whose MLP was evaluated /
+        samples those passes considered, since the last reset (renders are counted by occupancy_stats)"""
+        self._field_net("fine")
+        c, f = self._ctx.occupancy_train_stats(reset)
+        return {"coarse": c, "fine": f}
+
     def predict_and_render_images(self, rays, u=None, outputs=None):
         """nerf.py:229-304: returns (coarse_results, fine_results), each {image [B,H,W,3], depth [B,H,W], weights [B,H,W,S]}.
         outputs (extension): the keys wanted, e.g. ("image", "depth") -- what inference.py:108-114 reads -- or ("image",) (test_step);

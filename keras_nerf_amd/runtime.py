@@ -495,6 +495,34 @@ class KnerfContext:
         self._check(self.lib.knerf_occupancy_stats(self._ctx, self._stream(), a, b, int(reset)))
         return (a[0], b[0]), (a[1], b[1])
 
+    def set_occupancy_words(self, net: int, words: torch.Tensor, cells, lo, hi, outside: str = "occupied"):
+        """Attach a grid that is already on the device: words = int32 / uint32 device tensor of ceil(cx cy cz / 32) packed words (as
+        occupancy_words_from_grid returns them), cells = (cx, cy, cz).  The device-only route of set_occupancy: nothing is copied
+        through the host and nothing waits for the GPU (the words are copied on the context's stream)."""
+        if net not in (COARSE, FINE):
+            raise ValueError(f"net must be {COARSE} (coarse) or {FINE} (fine), got {net!r}")
+        cells3, lo3, hi3, out_empty = occupancy_box(cells, lo, hi, outside)
+        need = (int(np.prod(cells3)) + 31) // 32
+        if not isinstance(words, torch.Tensor) or words.dtype not in (torch.int32, torch.uint32) or words.dim() != 1 or \
+                words.device != torch.device(self.device) or not words.is_contiguous():
+            raise ValueError("set_occupancy_words: words must be a contiguous 1-D int32 tensor on the context's device")
+        if words.numel() != need:
+            raise ValueError(f"set_occupancy_words: {tuple(cells3)} cells need {need} words, got {words.numel()}")
+        self._check(self.lib.knerf_set_occupancy(self._ctx, self._stream(), int(net), _ptr(words), (C.c_int32 * 3)(*cells3),
+                                                 (C.c_float * 3)(*lo3), (C.c_float * 3)(*hi3), out_empty))
+
+    def occupancy_train_stats(self, reset: bool = True):
+        """((live, total) samples of the coarse TRAIN passes behind a grid, (live, total) of the fine ones) since the last reset
+        (option occupancy_train; render passes are counted by occupancy_stats)"""
+        a, b = (C.c_int64 * 2)(), (C.c_int64 * 2)()
+        self._check(self.lib.knerf_occupancy_train_stats(self._ctx, self._stream(), a, b, int(reset)))
+        return (a[0], b[0]), (a[1], b[1])
+
+    def occupancy_decay_max(self, state: torch.Tensor, sigma: torch.Tensor, decay: float):
+        """state = max(decay * state, sigma) in place on the context's stream (Instant-NGP's density EMA); both contiguous float32
+        device tensors of the same size"""
+        occupancy_decay_max(state, sigma, decay, stream=self._stream())
+
     def zero_grads(self):
         self._check(self.lib.knerf_zero_grads(self._ctx, self._stream()))
 
@@ -586,15 +614,14 @@ def unpack_occupancy(words, cells) -> np.ndarray:
     return np.unpackbits(w.view(np.uint8), bitorder="little")[:n].astype(bool).reshape(tuple(int(c) for c in cells))
 
 
-def occupancy_spec(occupied, lo, hi, outside="occupied"):
-    """validated (words uint32, cells, lo[3], hi[3], outside_empty) of a grid for knerf_set_occupancy; ValueError on bad arguments"""
-    if isinstance(occupied, torch.Tensor):
-        occupied = occupied.detach().cpu().numpy()
-    occ = np.asarray(occupied)
-    if occ.dtype != np.bool_:
-        raise ValueError(f"occupancy: the grid must be boolean, got dtype {occ.dtype}")
-    if occ.ndim != 3 or not all(1 <= c <= 1024 for c in occ.shape):
-        raise ValueError(f"occupancy: the grid must be [cx, cy, cz] with 1..1024 cells per axis, got shape {occ.shape}")
+def occupancy_box(cells, lo, hi, outside="occupied"):
+    """validated (cells, lo[3], hi[3], outside_empty) of a grid's box; ValueError on bad arguments"""
+    try:
+        cells3 = tuple(cells)
+    except TypeError:
+        raise ValueError(f"occupancy: cells must be three integers, got {cells!r}") from None
+    if len(cells3) != 3 or any(isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 1 <= int(c) <= 1024 for c in cells3):
+        raise ValueError(f"occupancy: cells must be three integers 1..1024, got {cells!r}")
     if outside not in OCCUPANCY_OUTSIDE:
         raise ValueError(f"occupancy: outside must be 'occupied' or 'empty', got {outside!r}")
     try:
@@ -604,21 +631,50 @@ def occupancy_spec(occupied, lo, hi, outside="occupied"):
     if len(lo3) != 3 or len(hi3) != 3 or not all(np.isfinite(np.float32(v)) for v in lo3 + hi3) or \
             not all(np.float32(h) > np.float32(l) for l, h in zip(lo3, hi3)):
         raise ValueError(f"occupancy: need finite lo[3] < hi[3] on every axis, got {lo!r} / {hi!r}")
-    return pack_occupancy(occ), tuple(int(c) for c in occ.shape), lo3, hi3, int(outside == "empty")
+    return tuple(int(c) for c in cells3), lo3, hi3, int(outside == "empty")
+
+
+def occupancy_spec(occupied, lo, hi, outside="occupied"):
+    """validated (words uint32, cells, lo[3], hi[3], outside_empty) of a grid for knerf_set_occupancy; ValueError on bad arguments"""
+    if isinstance(occupied, torch.Tensor):
+        occupied = occupied.detach().cpu().numpy()
+    occ = np.asarray(occupied)
+    if occ.dtype != np.bool_:
+        raise ValueError(f"occupancy: the grid must be boolean, got dtype {occ.dtype}")
+    if occ.ndim != 3 or not all(1 <= c <= 1024 for c in occ.shape):
+        raise ValueError(f"occupancy: the grid must be [cx, cy, cz] with 1..1024 cells per axis, got shape {occ.shape}")
+    cells, lo3, hi3, out_empty = occupancy_box(occ.shape, lo, hi, outside)
+    return pack_occupancy(occ), cells, lo3, hi3, out_empty
 
 
 def occupancy_from_grid(sigma: torch.Tensor, threshold: float = 0.0, dilation: int = 1) -> np.ndarray:
     """knerf_occupancy_from_grid on a device fp32 lattice sigma [rx, ry, rz] (contiguous; 2..1025 per axis): bool [rx-1, ry-1, rz-1],
     a cell occupied if one of its 8 corners has sigma > threshold, then dilated by `dilation` cells (0..8, Chebyshev distance).  A
     heuristic: density between lattice points can be missed; the dilation is the margin."""
+    words = occupancy_words_from_grid(sigma, threshold, dilation, what="occupancy_from_grid")
+    return unpack_occupancy(words.cpu().numpy().view(np.uint32), tuple(int(r) - 1 for r in sigma.shape))
+
+
+def check_lattice(sigma, threshold, dilation, what="occupancy_from_grid"):
+    """ValueError unless sigma is a float32 device lattice [rx, ry, rz] (2..1025 per axis), dilation an integer 0..8 and threshold finite"""
     if not isinstance(sigma, torch.Tensor) or sigma.dtype != torch.float32 or sigma.dim() != 3 or not sigma.is_cuda:
-        raise ValueError("occupancy_from_grid: sigma must be a float32 device tensor [rx, ry, rz]")
+        raise ValueError(f"{what}: sigma must be a float32 device tensor [rx, ry, rz]")
     if not all(2 <= r <= 1025 for r in sigma.shape):
-        raise ValueError(f"occupancy_from_grid: need 2 <= resolution <= 1025 per axis (1..1024 cells), got {tuple(sigma.shape)}")
+        raise ValueError(f"{what}: need 2 <= resolution <= 1025 per axis (1..1024 cells), got {tuple(sigma.shape)}")
+    check_grid_args(threshold, dilation, what)
+
+
+def check_grid_args(threshold, dilation, what):
     if isinstance(dilation, bool) or int(dilation) != dilation or not 0 <= int(dilation) <= 8:
-        raise ValueError(f"occupancy_from_grid: dilation must be an integer 0..8, got {dilation!r}")
+        raise ValueError(f"{what}: dilation must be an integer 0..8, got {dilation!r}")
     if not np.isfinite(float(threshold)):
-        raise ValueError(f"occupancy_from_grid: threshold must be finite, got {threshold!r}")
+        raise ValueError(f"{what}: threshold must be finite, got {threshold!r}")
+
+
+def occupancy_words_from_grid(sigma: torch.Tensor, threshold: float = 0.0, dilation: int = 1, what="occupancy_words_from_grid") -> torch.Tensor:
+    """occupancy_from_grid without the round trip through the host: the packed grid as a device int32 tensor of ceil(cells / 32)
+    words (KnerfContext.set_occupancy_words takes it), enqueued on the current stream; nothing waits for the GPU"""
+    check_lattice(sigma, threshold, dilation, what)
     sigma = sigma.contiguous()
     cells = tuple(int(r) - 1 for r in sigma.shape)
     words = torch.zeros(((int(np.prod(cells)) + 31) // 32,), device=sigma.device, dtype=torch.int32)
@@ -627,4 +683,34 @@ def occupancy_from_grid(sigma: torch.Tensor, threshold: float = 0.0, dilation: i
     rc = lib.knerf_occupancy_from_grid(stream, _ptr(sigma), *(int(r) for r in sigma.shape), float(threshold), int(dilation), _ptr(words))
     if rc != 0:
         raise KnerfError(f"knerf_occupancy_from_grid failed ({rc})")
-    return unpack_occupancy(words.cpu().numpy().view(np.uint32), cells)
+    return words
+
+
+def occupancy_decay_max_reference(state: np.ndarray, sigma: np.ndarray, decay: float) -> np.ndarray:
+    """NumPy mirror of knerf_occupancy_decay_max: max(fp32(decay * state), sigma)"""
+    st = np.asarray(state, dtype=np.float32)
+    return np.maximum(np.float32(decay) * st, np.asarray(sigma, dtype=np.float32)).astype(np.float32)
+
+
+def _check_decay(state, sigma, decay):
+    for name, x in (("state", state), ("sigma", sigma)):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous():
+            raise ValueError(f"occupancy_decay_max: {name} must be a contiguous float32 device tensor")
+    if state.numel() != sigma.numel() or state.numel() == 0:
+        raise ValueError(f"occupancy_decay_max: state and sigma must have the same non-zero size, got {state.numel()} / {sigma.numel()}")
+    if state.device != sigma.device:
+        raise ValueError("occupancy_decay_max: state and sigma must be on the same device")
+    if isinstance(decay, bool) or not isinstance(decay, (int, float, np.floating, np.integer)) or not 0.0 <= float(decay) <= 1.0:
+        raise ValueError(f"occupancy_decay_max: decay must be a number in [0, 1], got {decay!r}")
+
+
+def occupancy_decay_max(state: torch.Tensor, sigma: torch.Tensor, decay: float, stream=None) -> torch.Tensor:
+    """knerf_occupancy_decay_max: state = max(decay * state, sigma) in place, on `stream` (default: the current stream); returns state"""
+    _check_decay(state, sigma, decay)
+    lib = _lib.load()
+    if stream is None:
+        stream = C.c_void_p(torch.cuda.current_stream(state.device).cuda_stream)
+    rc = lib.knerf_occupancy_decay_max(stream, _ptr(state), _ptr(sigma), int(state.numel()), float(decay))
+    if rc != 0:
+        raise KnerfError(f"knerf_occupancy_decay_max failed ({rc})")
+    return state
