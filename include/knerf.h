@@ -159,6 +159,9 @@ int knerf_zero_grads(knerf_ctx* ctx, void* stream);
  *                            budget of the workspaces that takes (defaults 4 and 40 GB; 1 or 0 = one launch per chunk).
  *   "occupancy_train"   0/1  (default 0) train passes of a net that has an occupancy grid attached skip its empty cells exactly as
  *                            render passes do (see "Empty-space skipping" below); 0, or no grid: training is unchanged, bit for bit.
+ *   "termination_threshold" eps in [0, 1), finite (default 0 = off): early ray termination of the render passes (see "Early ray
+ *                            termination" below); 0: renders allocate, launch and write exactly what they do without the option.
+ *   "termination_segment" 1..1024 (default 32) the segment length L of early ray termination.
  *   "wgrad_cost0".."wgrad_cost<n_layers>": relative cost per sample tile of the n_layers + 1 weight-gradient jobs (nine for the default shape) (workgroups are dealt out in that
  *                            proportion; tuning sweeps).
  * knerf_get_option also answers "skip_dead_tiles_active", "wgrad_group" (of the current workspaces), "general_shape_path" and
@@ -288,6 +291,30 @@ int knerf_occupancy_train_stats(knerf_ctx* ctx, void* stream, int64_t* live, int
 /* knerf_occupancy_decay_max -- extension, no reference counterpart (Instant-NGP's density EMA).  Context-free.  state, sigma: DEVICE fp32
  * [n]; state[i] = max(decay * state[i], sigma[i]) (one rounding for the product), on `stream`.  Needs 0 <= decay <= 1. */
 int knerf_occupancy_decay_max(void* stream, float* state, const float* sigma, uint64_t n, float decay);
+/* ---- Early ray termination for rendering.  Extension, no reference counterpart (as in Instant-NGP and most volume renderers). ----
+ * With option "termination_threshold" eps > 0, every render pass (coarse and fine) of knerf_render_chunk / knerf_render_batch works in
+ * segments: segment k of a ray is samples [k L, min((k+1) L, S)), L = option "termination_segment" (a segment longer than the pass is
+ * the whole pass).  Segment 0 is evaluated as without the option (behind the grid, if one is attached).
+ *   Transmittance: T = 1 in front of segment 0; after each segment T <- T * x_i for each of its samples in ascending order, one fp32
+ *   product each, x_i = 1 - alpha_i + 1e-10, alpha_i = 1 - exp(-sigma_i delta_i), delta_i = t_{i+1} - t_i (the last 1e-10): the
+ *   arithmetic of compositing, on the raw the pass has produced so far (0 at dead samples: x = 1 exactly).
+ *   Cut: every sample of a later segment whose ray has T < fp32(eps) in front of that segment is TERMINATED: raw = (0, 0, 0, 0) and the
+ *   MLP does not run on it.  A sample's MLP runs iff it is occupied (when a grid is attached) and not terminated.
+ * Compositing, the sampler and the outputs work as before; the fine sampler takes the coarse weights that come out of this.  So:
+ * terminated samples are a suffix of each ray that starts at a segment boundary; every sample in front of the cut has the bits of the
+ * render without termination (dense, or grid-only with a grid); per ray the image moves by at most T_cut < eps per channel (with a
+ * white background too: it moves by the change of sum w) and the depth by at most eps * t_max, up to fp32 summation order.
+ *   Applies to:     knerf_render_chunk, knerf_render_batch.
+ *   Never applies:  training, knerf_forward_chunk, knerf_query_points, knerf_query_grid (whatever eps is).
+ * Fused shapes run one round per segment without host synchronisation: fold, cut, grid and an ordered compaction of the segment's live
+ * samples, then the fused MLP on that list only (under the net's forward profile class).  Workspace, only while eps > 0: about 4 L + 8
+ * bytes per ray.  The general-shape path runs its dense forward, then zeroes the terminated samples with the same rule: the same
+ * outputs without the speed-up.  knerf_termination_stats counts these passes; knerf_occupancy_stats keeps counting the grid's verdict
+ * on every sample. */
+/* knerf_termination_stats -- extension, no reference counterpart.  Per net since the last reset: live[n] = samples of render passes with
+ * eps > 0 whose MLP output is kept (occupied and not terminated; the fused path evaluates only those), total[n] = all samples of those
+ * passes.  Synchronises `stream`. */
+int knerf_termination_stats(knerf_ctx* ctx, void* stream, int64_t* live, int64_t* total, int reset);
 
 /* Diagnostics (layout tables, workspace views, hardware-fact and bandwidth probes) are NOT part of this library: they are
  * declared in include/knerf_debug.h and built into libknerf_probe.so for tests/ and tools/ only. */

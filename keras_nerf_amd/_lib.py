@@ -73,6 +73,7 @@ SIGNATURES = {
     "knerf_occupancy_stats": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
     "knerf_occupancy_train_stats": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
     "knerf_occupancy_decay_max": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_float]),
+    "knerf_termination_stats": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
 }
 
 _lib = None

@@ -101,6 +101,12 @@ struct knerf_ctx {
     bool occ_train = false;
     float *occ_raw_c = nullptr, *occ_draw_c = nullptr; int ws_occ_train_rays = 0;
     long long* occ_train_stats = nullptr;
+    // early ray termination of the render passes (options "termination_threshold" / "termination_segment"; termination.h): eps (0 = off),
+    // the segment length, the fused path's workspace (T, ballots, per-workgroup counts / offsets, the segment's list and its length),
+    // sized only while eps > 0 (grow-only, term_ws_bytes), and [net][2]: samples whose MLP output is kept, samples of those passes
+    double term_eps = 0.0; int term_L = 32;
+    char* term_ws = nullptr; size_t term_ws_bytes = 0;
+    long long* term_stats = nullptr;
     // run-time options (knerf_set_option)
     bool deterministic = false;         // per-workgroup partial sums + ordered second pass instead of fp32 atomics (wgrad, loss)
     bool skip_dead = true;              // dgrad / wgrad skip 32-sample tiles whose dL/d(rgb, sigma) is exactly zero (exact; +0.3 % when nothing is dead)

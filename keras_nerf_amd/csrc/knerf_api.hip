@@ -17,6 +17,7 @@
 #include "layout.h"
 #include "occupancy.h"
 #include "query.h"
+#include "termination.h"
 #include "train_list.h"
 
 using namespace knerf;
@@ -143,6 +144,30 @@ OccWs occ_ws_view(char* base, long long n) {
     return w;
 }
 bool occ_attached(const knerf_ctx* ctx) { return ctx->occ[0].bits || ctx->occ[1].bits; }
+
+// early ray termination (options "termination_threshold" / "termination_segment"): the segment length of a pass of S samples (a
+// segment longer than the pass is the whole pass), and the fused path's workspace of a pass of R rays: ballots [term_blocks * 32]
+// u64, T [R], the segment's list [R * L], per-workgroup counts / offsets, the list's length
+int term_segment(const knerf_ctx* ctx, int S) { return ctx->term_L < S ? ctx->term_L : S; }
+struct TermWs { unsigned long long* masks; float* T; int *list, *blk_cnt, *blk_off, *count; };
+size_t term_ws_bytes(long long R, int L) { return (size_t)term_blocks(R, L) * (kTermWords * 8 + 8) + (size_t)R * 4 + (size_t)R * L * 4 + 4; }
+TermWs term_ws_view(char* base, long long R, int L) {
+    TermWs w;
+    const long long nb = term_blocks(R, L);
+    w.masks = reinterpret_cast<unsigned long long*>(base);
+    w.T = reinterpret_cast<float*>(base + (size_t)nb * kTermWords * 8);
+    w.list = reinterpret_cast<int*>(w.T + R);
+    w.blk_cnt = w.list + R * L;
+    w.blk_off = w.blk_cnt + nb;
+    w.count = w.blk_off + nb;
+    return w;
+}
+// the workspace for passes of up to n_rays rays with up to Na samples: the largest of the coarse and the fine pass's needs
+size_t term_ws_need(const knerf_ctx* ctx, int n_rays) {
+    const size_t c = term_ws_bytes(n_rays, term_segment(ctx, ctx->cfg.n_coarse));
+    const size_t f = term_ws_bytes(n_rays, term_segment(ctx, ctx->cfg.n_coarse + ctx->cfg.n_fine));
+    return c > f ? c : f;
+}
 // training behind the grids (option "occupancy_train"): for one net / for either net
 bool occ_train_on(const knerf_ctx* ctx, int net) { return ctx->occ_train && ctx->occ[net].bits; }
 bool occ_train_any(const knerf_ctx* ctx) { return ctx->occ_train && occ_attached(ctx); }
@@ -201,7 +226,10 @@ int ensure_ws_impl(knerf_ctx* ctx, int n_rays, bool train, hipStream_t s, int gr
     const bool occ_tr = train && occ_train_any(ctx);
     const bool grow_occ = (train ? occ_tr : occ_attached(ctx)) && n_rays > ctx->ws_occ_rays;
     const bool grow_occ_train = occ_tr && n_rays > ctx->ws_occ_train_rays;
-    if (!grow_base && !grow_train && !grow_occ && !grow_occ_train) return KNERF_OK;
+    // renders with early ray termination ("termination_threshold" > 0): T, the segment's ballots, counts and list (about 4 L + 8 bytes per ray)
+    const size_t term_b = !train && ctx->term_eps > 0 ? term_ws_need(ctx, n_rays) : 0;
+    const bool grow_term = term_b > ctx->term_ws_bytes;
+    if (!grow_base && !grow_train && !grow_occ && !grow_occ_train && !grow_term) return KNERF_OK;
     if (ctx->ws_limit_gb > 0) {
         const int Rt = n_rays > ctx->ws_train_rays ? n_rays : ctx->ws_train_rays;
         const size_t tl = group == 1 ? tiles_for((long long)Rt * Na) : (size_t)group * tiles_for((long long)Rt * ctx->cfg.n_coarse) + tiles_for((long long)Rt * Na);
@@ -209,7 +237,7 @@ int ensure_ws_impl(knerf_ctx* ctx, int n_rays, bool train, hipStream_t s, int gr
         const double train_b = grow_train ? (double)Rt * Na * 16 + (double)saved_region_bytes(tl, ctx->si.act_blocks) +
                                                 (double)saved_region_bytes(tl, ctx->si.mask_blocks) + (double)saved_region_bytes(tl, ctx->si.dz_blocks) : 0.0;
         const double occ_b = (grow_occ ? (double)occ_ws_bytes((long long)n_rays * Na) : 0.0) + (grow_occ_train ? (double)n_rays * Na * 32 : 0.0);
-        if (int r = over_limit(ctx, base_b + train_b + occ_b)) return r;
+        if (int r = over_limit(ctx, base_b + train_b + occ_b + (grow_term ? (double)term_b : 0.0))) return r;
     }
     HIPCHK(hipStreamSynchronize(s));               // nothing enqueued earlier may still use the buffers that are freed below
     if (grow_base) {
@@ -228,6 +256,12 @@ int ensure_ws_impl(knerf_ctx* ctx, int n_rays, bool train, hipStream_t s, int gr
         ctx->ws_occ_rays = 0;
         HIPCHK(hipMalloc(&ctx->occ_ws, occ_ws_bytes((long long)n_rays * Na)));
         ctx->ws_occ_rays = n_rays;
+    }
+    if (grow_term) {
+        free_dev(ctx->term_ws);
+        ctx->term_ws_bytes = 0;
+        HIPCHK(hipMalloc(&ctx->term_ws, term_b));
+        ctx->term_ws_bytes = term_b;
     }
     if (grow_occ_train) {
         free_dev(ctx->occ_raw_c); free_dev(ctx->occ_draw_c);
@@ -381,6 +415,8 @@ int run_pass(knerf_ctx* ctx, hipStream_t s, int net, const float* o, const float
     const knerf_ctx::Occ* og = ((render && !train) || (train && occ_train_on(ctx, net))) && ctx->occ[net].bits ? &ctx->occ[net] : nullptr;
     // fused training behind a grid: forward, dgrad and weight gradients on the compacted list of live samples (train_list.h)
     const bool compact = og && train && !ctx->generic;
+    // early ray termination: render passes only, while "termination_threshold" > 0 (termination.h)
+    const bool term = render && !train && ctx->term_eps > 0;
     OccArgs oa{};
     if (og) {
         oa.grid.bits = og->bits; oa.grid.outside_empty = og->outside_empty;
@@ -389,6 +425,14 @@ int run_pass(knerf_ctx* ctx, hipStream_t s, int net, const float* o, const float
         oa.stats = (train ? ctx->occ_train_stats : ctx->occ_stats) + 2 * (net == KNERF_COARSE ? 0 : 1);
         if (!ctx->generic && oa.n >= (1ll << 31))       // the list holds int32 sample indices
             return fail(ctx, KNERF_ERR_INVALID, "pass behind an occupancy grid: a pass of 2^31 samples or more (use a smaller ray_chunks)");
+    }
+    TermArgs ta{};
+    if (term) {
+        if (og) { ta.grid = oa.grid; ta.has_grid = 1; ta.occ_stats = oa.stats; }
+        ta.o = o; ta.d = d; ta.t = t; ta.raw = ctx->raw; ta.R = R; ta.S = S; ta.L = term_segment(ctx, S); ta.eps = (float)ctx->term_eps;
+        ta.stats = ctx->term_stats + 2 * (net == KNERF_COARSE ? 0 : 1);
+        if (!ctx->generic && (long long)R * S >= (1ll << 31))       // the list holds int32 sample indices
+            return fail(ctx, KNERF_ERR_INVALID, "pass with early ray termination: a pass of 2^31 samples or more (use a smaller ray_chunks)");
     }
     FwdArgs fa{};
     fa.stream = ctx->net[net].fwd_stream; fa.bias = ctx->net[net].bias;
@@ -401,6 +445,8 @@ int run_pass(knerf_ctx* ctx, hipStream_t s, int net, const float* o, const float
         HIPCHK(gen::forward(ctx->gplan, ctx->gws, ctx->gnet[net], ctx->net[net].w, o, d, t, fa.n_samples, S, ctx->raw, s));
         // general-shape path: the MLP ran on every sample; the dead ones are zeroed behind it (same outputs, no speed-up)
         if (og) HIPCHK(launch_occupancy_mark(oa, s));
+        // ... and the terminated ones behind the dead ones, by the same cut rule
+        if (term) HIPCHK(launch_termination_walk(ta, s));
     } else if (compact) {
         // fused training: ordered compaction of the live samples, then the SAVE forward on the list alone; saved tensors of compacted
         // tile i / 32, raw to raw[list[i]]
@@ -411,6 +457,22 @@ int run_pass(knerf_ctx* ctx, hipStream_t s, int net, const float* o, const float
         TrainListArgs la{};
         la.f = fa; la.list = w.list; la.count = w.count;
         HIPCHK(launch_mlp_fwd_list(la, s));
+    } else if (term) {
+        // fused path with early ray termination: one round per segment -- fold the previous segment into T, cut, grid, ordered
+        // compaction of the segment's live samples -- then the fused MLP on that list; no host synchronisation between rounds
+        ProfScope ps(ctx, s, net == KNERF_COARSE ? P_FWD_C : P_FWD_F);
+        const TermWs w = term_ws_view(ctx->term_ws, R, ta.L);
+        ta.T = w.T; ta.masks = w.masks; ta.blk_cnt = w.blk_cnt; ta.blk_off = w.blk_off; ta.list = w.list; ta.count = w.count;
+        QueryArgs q{};
+        q.stream = ctx->net[net].fwd_stream; q.bias = ctx->net[net].bias; q.shape = ctx->shape;
+        q.raw = ctx->raw; q.list = w.list; q.count = w.count; q.o = o; q.d = d; q.t = t; q.S = S;
+        for (int k = 0; k * ta.L < S; ++k) {
+            ta.k = k;
+            HIPCHK(launch_termination_round(ta, s));
+            const int Lk = S - k * ta.L < ta.L ? S - k * ta.L : ta.L;
+            q.n = (long long)R * Lk;
+            HIPCHK(launch_query_list(q, s));
+        }
     } else if (og) {
         // fused path: ordered compaction of the live samples, then the fused MLP on the list alone (query.hip list mode)
         ProfScope ps(ctx, s, net == KNERF_COARSE ? P_FWD_C : P_FWD_F);
@@ -727,6 +789,8 @@ int knerf_create(const knerf_config* cfg, knerf_ctx** out) {
     CREATECHK(hipMemset(ctx->occ_stats, 0, 4 * sizeof(long long)));
     CREATECHK(hipMalloc(&ctx->occ_train_stats, 4 * sizeof(long long)));
     CREATECHK(hipMemset(ctx->occ_train_stats, 0, 4 * sizeof(long long)));
+    CREATECHK(hipMalloc(&ctx->term_stats, 4 * sizeof(long long)));
+    CREATECHK(hipMemset(ctx->term_stats, 0, 4 * sizeof(long long)));
     CREATECHK(hipMalloc(&ctx->d_diag, 2 * sizeof(unsigned long long)));
     CREATECHK(hipHostMalloc(&ctx->h_diag, 4 * sizeof(long long), hipHostMallocDefault));
     ctx->h_diag[0] = ctx->h_diag[1] = ctx->h_diag[2] = ctx->h_diag[3] = 0;
@@ -790,6 +854,7 @@ int knerf_destroy(knerf_ctx* ctx) {
     free_dev(ctx->partial); free_dev(ctx->loss_partial); free_dev(ctx->d_job_wg0);
     free_dev(ctx->occ[0].bits); free_dev(ctx->occ[1].bits); free_dev(ctx->occ_ws); free_dev(ctx->occ_stats);
     free_dev(ctx->occ_raw_c); free_dev(ctx->occ_draw_c); free_dev(ctx->occ_train_stats);
+    free_dev(ctx->term_ws); free_dev(ctx->term_stats);
     free_dev(ctx->gws.act); free_dev(ctx->gws.dz); free_dev(ctx->gws.zs); free_dev(ctx->gws.zc); free_dev(ctx->gws.mask);
     for (int n = 0; n < 2; ++n) { free_dev(ctx->gnet[n].packed); free_dev(ctx->gnet[n].head); free_dev(ctx->gnet[n].gaux); }
     free_dev(ctx->call_net.head);
@@ -937,6 +1002,16 @@ int knerf_occupancy_train_stats(knerf_ctx* ctx, void* stream, int64_t* live, int
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     HIPCHK(hipMemcpy(h, ctx->occ_train_stats, sizeof(h), hipMemcpyDeviceToHost));
     if (reset) HIPCHK(hipMemset(ctx->occ_train_stats, 0, sizeof(h)));
+    for (int n = 0; n < 2; ++n) { live[n] = h[2 * n]; total[n] = h[2 * n + 1]; }
+    return KNERF_OK;
+}
+
+int knerf_termination_stats(knerf_ctx* ctx, void* stream, int64_t* live, int64_t* total, int reset) {
+    if (!ctx || !live || !total) return KNERF_ERR_INVALID;
+    long long h[4] = {0, 0, 0, 0};
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    HIPCHK(hipMemcpy(h, ctx->term_stats, sizeof(h), hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(ctx->term_stats, 0, sizeof(h)));
     for (int n = 0; n < 2; ++n) { live[n] = h[2 * n]; total[n] = h[2 * n + 1]; }
     return KNERF_OK;
 }
@@ -1147,6 +1222,12 @@ int knerf_set_option(knerf_ctx* ctx, const char* name, double value) {
     } else if (n == "occupancy_train") {
         if (value != 0 && value != 1) return fail(ctx, KNERF_ERR_INVALID, "occupancy_train: 0 or 1");
         ctx->occ_train = value != 0;               // applies to the nets with a grid attached (knerf_set_occupancy)
+    } else if (n == "termination_threshold") {
+        if (!std::isfinite(value) || value < 0 || value >= 1) return fail(ctx, KNERF_ERR_INVALID, "termination_threshold: a finite eps in [0, 1)");
+        ctx->term_eps = value;                     // 0: off (render passes as without the option, bit for bit)
+    } else if (n == "termination_segment") {
+        if (!(value >= 1 && value <= 1024) || value != std::floor(value)) return fail(ctx, KNERF_ERR_INVALID, "termination_segment: an integer 1..1024");
+        ctx->term_L = (int)value;
     } else if (n == "merge_chunk_rays") {
         if (value < 0 || value > 1048576) return fail(ctx, KNERF_ERR_INVALID, "merge_chunk_rays: 0..1048576");
         ctx->merge_rays = (int)value; ctx->merge_fail_rays = 0; if (ctx->generic) ctx->rmerge_fail_rays = 0;
@@ -1178,6 +1259,8 @@ int knerf_get_option(knerf_ctx* ctx, const char* name, double* value) {
     else if (n == "skip_dead_tiles") *value = ctx->skip_dead;
     else if (n == "grad_diagnostics") *value = ctx->grad_diag;
     else if (n == "occupancy_train") *value = ctx->occ_train;
+    else if (n == "termination_threshold") *value = ctx->term_eps;
+    else if (n == "termination_segment") *value = ctx->term_L;
     else if (n == "skip_dead_tiles_active") *value = skipping(ctx);
     else if (n == "wgrad_group_max") *value = ctx->wgrad_group_max;
     else if (n == "merge_chunk_rays") *value = ctx->merge_rays;

@@ -13,6 +13,21 @@ struct OccGrid {
     int outside_empty;      // a sample outside the box: 0 = occupied, 1 = empty
 };
 
+// the cell lookup (include/knerf.h; occupancy.hip and termination.hip): outside if u < 0, floor(u) >= c or u is NaN on any axis.  floor(u) >= c <=> u >= c for an
+// integer c, so no out-of-range float -> int conversion happens.
+__device__ __forceinline__ bool occ_lookup(const OccGrid& G, float px, float py, float pz) {
+    const float p[3] = {px, py, pz};
+    int idx[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float u = __fmul_rn(__fsub_rn(p[c], G.lo[c]), G.scale[c]);
+        if (!(u >= 0.f) || u >= (float)G.cells[c]) return !G.outside_empty;
+        idx[c] = (int)__builtin_floorf(u);
+    }
+    const unsigned b = ((unsigned)idx[0] * (unsigned)G.cells[1] + (unsigned)idx[1]) * (unsigned)G.cells[2] + (unsigned)idx[2];
+    return (G.bits[b >> 5] >> (b & 31u)) & 1u;
+}
+
 constexpr int kOccBlock = 256, kOccPer = 8, kOccSpan = kOccBlock * kOccPer;     // samples per workgroup of the mark / emit kernels
 
 inline long long occ_blocks(long long n) { return (n + kOccSpan - 1) / kOccSpan; }
@@ -36,6 +51,8 @@ struct OccArgs {
 // mark: cell lookup of every sample, raw = 0 at the dead ones, ballots and per-workgroup counts, stats.  With masks set, also the
 // ordered compaction (scan of the counts, then the list) into list / count.
 hipError_t launch_occupancy_mark(const OccArgs& a, hipStream_t stream);
+// the one-workgroup exclusive scan of the mark step alone: off[b] = sum of cnt[< b], *count = the total (csrc/termination.hip)
+hipError_t launch_occupancy_scan(const int* cnt, int nblk, int* off, int* count, hipStream_t stream);
 // lattice sigma [rx,ry,rz] -> bits of the (rx-1) x (ry-1) x (rz-1) cells: occupied if a corner has sigma > threshold, then dilated
 hipError_t launch_occupancy_build(const float* sigma, int rx, int ry, int rz, float threshold, int dilation, unsigned* bits, hipStream_t stream);
 

@@ -22,21 +22,6 @@
 
 namespace knerf {
 
-// the cell lookup (include/knerf.h): outside if u < 0, floor(u) >= c or u is NaN on any axis.  floor(u) >= c <=> u >= c for an
-// integer c, so no out-of-range float -> int conversion happens.
-__device__ __forceinline__ bool occ_lookup(const OccGrid& G, float px, float py, float pz) {
-    const float p[3] = {px, py, pz};
-    int idx[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float u = __fmul_rn(__fsub_rn(p[c], G.lo[c]), G.scale[c]);
-        if (!(u >= 0.f) || u >= (float)G.cells[c]) return !G.outside_empty;
-        idx[c] = (int)__builtin_floorf(u);
-    }
-    const unsigned b = ((unsigned)idx[0] * (unsigned)G.cells[1] + (unsigned)idx[1]) * (unsigned)G.cells[2] + (unsigned)idx[2];
-    return (G.bits[b >> 5] >> (b & 31u)) & 1u;
-}
-
 __global__ __launch_bounds__(kOccBlock) void occ_mark_kernel(OccArgs a) {
     __shared__ int s_cnt[kOccBlock / 64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -156,6 +141,11 @@ __global__ __launch_bounds__(256) void occ_build_kernel(const float* sigma, int 
     }
     const unsigned long long m = __ballot(occ);               // b of lane 0 is a multiple of 64: lanes 0-31 / 32-63 are two words
     if ((lane == 0 || lane == 32) && b < ncell) bits[b >> 5] = (unsigned)(lane == 0 ? m : m >> 32);
+}
+
+hipError_t launch_occupancy_scan(const int* cnt, int nblk, int* off, int* count, hipStream_t stream) {
+    hipLaunchKernelGGL(occ_scan_kernel, dim3(1), dim3(1024), 0, stream, cnt, nblk, off, count);
+    return hipGetLastError();
 }
 
 hipError_t launch_occupancy_build(const float* sigma, int rx, int ry, int rz, float threshold, int dilation, unsigned* bits, hipStream_t stream) {

@@ -407,11 +407,38 @@ class NeRF:
         c, f = self._ctx.occupancy_train_stats(reset)
         return {"coarse": c, "fine": f}
 
+    # ------------------------------------------------------------------ early ray termination for rendering (extension)
+    def set_ray_termination(self, threshold=1e-4, segment=None):
+        """Early ray termination of every render (options termination_threshold / termination_segment, include/knerf.h): each render
+        pass works in segments of `segment` samples (1..1024; None keeps the current length, 32 by default), and once a ray's
+        transmittance T has dropped below `threshold` in front of a segment, the MLP no longer runs on that segment and the ones behind
+        it (raw = 0 there).  Samples in front of the cut keep their exact values; per ray the image moves by at most `threshold` and the
+        depth by at most threshold * far.  threshold = 0 turns it off: renders are then bit-identical to renders without it.  While it
+        is on, predict_and_render_images, predict_and_render_chunk, test_step and evaluate are affected; training never terminates."""
+        if isinstance(threshold, (bool, np.bool_)) or not isinstance(threshold, (int, float, np.integer, np.floating)) or \
+                not np.isfinite(float(threshold)) or not 0.0 <= float(threshold) < 1.0:
+            raise ValueError(f"threshold must be a finite number in [0, 1), got {threshold!r}")
+        if segment is not None and (isinstance(segment, (bool, np.bool_)) or not isinstance(segment, (int, np.integer)) or
+                                    not 1 <= int(segment) <= 1024):
+            raise ValueError(f"segment must be None or an integer 1..1024, got {segment!r}")
+        self._field_net("fine")
+        if segment is not None:
+            self._ctx.set_option("termination_segment", int(segment))
+        self._ctx.set_option("termination_threshold", float(threshold))
+
+    def termination_stats(self, reset=True):
+        """{"coarse": (evaluated, total), "fine": (evaluated, total)}: samples of the render passes with early ray termination on whose
+        MLP output was kept (occupied, when a grid is attached, and not terminated) / every sample of those passes, since the last reset"""
+        self._field_net("fine")
+        c, f = self._ctx.termination_stats(reset)
+        return {"coarse": c, "fine": f}
+
     def predict_and_render_images(self, rays, u=None, outputs=None):
         """nerf.py:229-304: returns (coarse_results, fine_results), each {image [B,H,W,3], depth [B,H,W], weights [B,H,W,S]}.
         outputs (extension): the keys wanted, e.g. ("image", "depth") -- what inference.py:108-114 reads -- or ("image",) (test_step);
         the others are neither allocated nor written (knerf_render_batch takes NULL for them: at 256 x 256 the two `weights` arrays
-        are 67 MB per frame).  Default: the reference's full dictionaries."""
+        are 67 MB per frame).  Default: the reference's full dictionaries.  Behind an occupancy grid (build_occupancy_grid) or with early
+        ray termination on (set_ray_termination) the MLPs skip samples, and the outputs follow include/knerf.h."""
         keys = ("image", "depth", "weights") if outputs is None else tuple(outputs)
         if "image" not in keys or any(k not in ("image", "depth", "weights") for k in keys):
             raise ValueError("outputs must contain 'image' and may contain 'depth' and 'weights'")
@@ -487,7 +514,8 @@ class NeRF:
         return logs
 
     def test_step(self, inputs, u=None):
-        """nerf.py:475-497"""
+        """nerf.py:475-497 (renders through predict_and_render_images: behind the occupancy grids and with early ray termination
+        when those are on)"""
         images, rays = inputs
         images = self._ctx.f32(images)[..., :3].contiguous()
         coarse, fine = self.predict_and_render_images(rays, u, outputs=("image",))     # nerf.py:489-497 reads the two images only

@@ -518,6 +518,15 @@ class KnerfContext:
         self._check(self.lib.knerf_occupancy_train_stats(self._ctx, self._stream(), a, b, int(reset)))
         return (a[0], b[0]), (a[1], b[1])
 
+    # ---- early ray termination for rendering (extension: options termination_threshold / termination_segment)
+    def termination_stats(self, reset: bool = True):
+        """((evaluated, total) samples of the coarse render passes with termination_threshold > 0, (evaluated, total) of the fine ones)
+        since the last reset: evaluated = samples whose MLP output is kept (occupied and not terminated), total = every sample of those
+        passes (include/knerf.h knerf_termination_stats)"""
+        a, b = (C.c_int64 * 2)(), (C.c_int64 * 2)()
+        self._check(self.lib.knerf_termination_stats(self._ctx, self._stream(), a, b, int(reset)))
+        return (a[0], b[0]), (a[1], b[1])
+
     def occupancy_decay_max(self, state: torch.Tensor, sigma: torch.Tensor, decay: float):
         """state = max(decay * state, sigma) in place on the context's stream (Instant-NGP's density EMA); both contiguous float32
         device tensors of the same size"""
