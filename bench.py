@@ -12,10 +12,14 @@ reference's train.py semantics: global batch = batch_size x replicas).
 
     python bench.py --mode fit [--config cfg2|cfg4]     what NeRF.fit delivers (loader -> train_step with metrics -> monitor), see bench_fit
     python bench.py ... --dump-outputs DIR               also writes what the last timed step computed to DIR/<name>.npy (dump_outputs)
+    python bench.py ... --full                           also everything beyond the headline figure (below)
 
-One JSON line is printed by rank 0; see the task contract for the fields.  `roofline` is measured live with HIP events
-around the dominant kernel (knerf_profile_*), `cpu_baseline` times the op-for-op torch-CPU restatement of the reference
-path (oracle/torch_ref.py, kind "port") on a bounded sample of the same workload.
+One JSON line is printed by rank 0; see the task contract for the fields.  A plain run sets up, warms up, times the steps, writes
+--dump-outputs and prints the line; whatever needs runs of its own is left out (null or absent on the line) unless --full is given:
+`roofline`, measured live with HIP events around the dominant kernel (knerf_profile_*), the metrics' cost, the dead-tile share,
+`cpu_baseline`, which times the op-for-op torch-CPU restatement of the reference path (oracle/torch_ref.py, kind "port") on a
+bounded sample of the same workload, with N > 1 the stand-alone all-reduce self-test and the replica check, and in --mode fit the
+plain train_step loop it is compared against and the epoch with dead-tile skipping on.
 """
 from __future__ import annotations
 
@@ -250,7 +254,7 @@ def bench_render(args, world, rank, wh, chunks, desc, backend="nccl"):
     fps = world * n_frames / elapsed
     rs = fps * wh * wh * 256
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         nerf._ctx.profile_enable(True); nerf._ctx.profile_read()
         frame(0, 0); collect(0)
         prof = nerf._ctx.profile_read(); nerf._ctx.profile_enable(False)
@@ -264,6 +268,7 @@ def bench_render(args, world, rank, wh, chunks, desc, backend="nccl"):
                     "launches": cnt, "kernel_ms_per_frame": {k: round(v[0], 4) for k, v in prof.items() if v[1]},
                     "frame_tflops": rs * FWD_FLOP / 1e12, "frame_frac_of_mfma_peak": rs * FWD_FLOP / 1e12 / MFMA_PEAK_TFLOPS,
                     "frame_executed_tflops": rs * FWD_FLOP_EXEC / 1e12}
+    if rank == 0:
         emit(json.dumps({"metric": "frames/sec (360-degree render 256^2, coarse64+fine128, forward only)", "value": fps,
                           "unit": "frames/s", "n_gpus": world, "steps": n_frames, "warmup": args.warmup,
                           "ms_per_step": elapsed / n_frames * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -374,11 +379,11 @@ def write_synthetic_dataset(root, wh, n=(100, 4, 4)):
 def bench_fit(args, world, rank, wh, batch, chunks, desc, backend):
     """`--mode fit`: the rate of the thing train_single.py:137-143 calls -- DatasetLoader (PNG decode, device-resident views,
     on-device rays) -> NeRF.fit -> train_step WITH its six metrics -> NeRFTrainMonitor (panels off; CSV, checkpoint and the two
-    monitor renders at every epoch end) -- against the plain `train_step(with_metrics=False)` loop on one resident batch (the
-    default mode's loop), both with dead-tile skipping off so that the two loops do the same work.  One warm-up epoch (decodes the PNGs, fills the device cache), then `--epochs` timed epochs of 100
+    monitor renders at every epoch end) -- with --full against the plain `train_step(with_metrics=False)` loop on one resident batch
+    (the default mode's loop), both with dead-tile skipping off so that the two loops do the same work.  One warm-up epoch (decodes the PNGs, fills the device cache), then `--epochs` timed epochs of 100
     training views.  value = rays*samples of the training batches / time of the train loops (from an epoch's first batch to the
-    read-back of its logs, GPU drained); `fit_wall_*` adds validation and the monitor.  One further epoch with skipping on (the
-    library default) is timed and reported with its dead-tile share."""
+    read-back of its logs, GPU drained); `fit_wall_*` adds validation and the monitor.  With --full, the plain loop and one further
+    epoch with skipping on (the library default) are timed after that and reported, the latter with its dead-tile share."""
     import tempfile
     from keras_nerf_amd.data.loader import DatasetLoader
     from keras_nerf_amd.model.nerf.callback import NeRFTrainMonitor
@@ -433,34 +438,35 @@ def bench_fit(args, world, rank, wh, batch, chunks, desc, backend):
     wall = t["end"][-1] - t["begin"][1]
     per_step = wh * wh * batch * 256
     value = world * per_step * steps * args.epochs / loop
-    # the plain train_step loop in the same process on one resident batch of the same dataset: no loader, no metrics, no callbacks
-    data = next(iter(train))
-    for _ in range(3):
-        nerf.train_step(data, with_metrics=False)
-    sync(world); t0 = time.perf_counter()
-    for _ in range(20):
-        nerf.train_step(data, with_metrics=False)
-    sync(world); ts = (time.perf_counter() - t0) / 20
-    for _ in range(3):
-        nerf.train_step(data, sync=False)
-    nerf._metric_state.events = []               # HIP events around the three metric launches of every step (metrics.py)
-    sync(world); t0 = time.perf_counter()
-    for _ in range(20):
-        nerf.train_step(data, sync=False)
-    sync(world); tm = (time.perf_counter() - t0) / 20
-    ev, nerf._metric_state.events = nerf._metric_state.events, None
-    metrics_ms = sum(a_.elapsed_time(b_) for a_, b_ in ev) / max(len(ev), 1)
-    # ... and what fit delivers with skipping on (the default), at this point of the training
-    nerf._ctx.set_option("skip_dead_tiles", 1)
-    skip_ms = dead_fit = None
-    if nerf._ctx.get_option("skip_dead_tiles_active"):
-        marks.clear()
-        nerf.fit(train, epochs=epochs + 1, initial_epoch=epochs, validation_data=val, callbacks=[Clock(), monitor], verbose=0)
-        torch.cuda.synchronize()
-        b = [m[1] for m in marks if m[0] == "begin"]; e = [m[1] for m in marks if m[0] == "train_end"]
-        skip_ms = (e[0] - b[0]) / steps * 1e3
-        live, total = nerf._ctx.tile_stats(reset=True)
-        dead_fit = 1.0 - live / max(total, 1) if total else None
+    ts = tm = metrics_ms = skip_ms = dead_fit = None
+    if args.full:
+        # the plain train_step loop in the same process on one resident batch of the same dataset: no loader, no metrics, no callbacks
+        data = next(iter(train))
+        for _ in range(3):
+            nerf.train_step(data, with_metrics=False)
+        sync(world); t0 = time.perf_counter()
+        for _ in range(20):
+            nerf.train_step(data, with_metrics=False)
+        sync(world); ts = (time.perf_counter() - t0) / 20
+        for _ in range(3):
+            nerf.train_step(data, sync=False)
+        nerf._metric_state.events = []               # HIP events around the three metric launches of every step (metrics.py)
+        sync(world); t0 = time.perf_counter()
+        for _ in range(20):
+            nerf.train_step(data, sync=False)
+        sync(world); tm = (time.perf_counter() - t0) / 20
+        ev, nerf._metric_state.events = nerf._metric_state.events, None
+        metrics_ms = sum(a_.elapsed_time(b_) for a_, b_ in ev) / max(len(ev), 1)
+        # ... and what fit delivers with skipping on (the default), at this point of the training
+        nerf._ctx.set_option("skip_dead_tiles", 1)
+        if nerf._ctx.get_option("skip_dead_tiles_active"):
+            marks.clear()
+            nerf.fit(train, epochs=epochs + 1, initial_epoch=epochs, validation_data=val, callbacks=[Clock(), monitor], verbose=0)
+            torch.cuda.synchronize()
+            b = [m[1] for m in marks if m[0] == "begin"]; e = [m[1] for m in marks if m[0] == "train_end"]
+            skip_ms = (e[0] - b[0]) / steps * 1e3
+            live, total = nerf._ctx.tile_stats(reset=True)
+            dead_fit = 1.0 - live / max(total, 1) if total else None
     nerf._ctx.set_option("skip_dead_tiles", int(skip_default))
     drift = {}
     if args.check_replicas:
@@ -471,9 +477,9 @@ def bench_fit(args, world, rank, wh, batch, chunks, desc, backend):
                           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
                           "config": {"workload": f"{args.config} through NeRF.fit: {desc}; 100 procedural training views in nerf_synthetic layout, "
                                                  f"{steps} steps per epoch, {args.epochs} timed epochs after one warm-up epoch", "parallelism": f"dp{world}"},
-                          "train_step_ms": ts * 1e3, "train_step_with_metrics_ms": tm * 1e3, "metrics_ms_per_step": metrics_ms,
+                          "train_step_ms": ts and ts * 1e3, "train_step_with_metrics_ms": tm and tm * 1e3, "metrics_ms_per_step": metrics_ms,
                           "metrics_clock": "hip events around the 3 metric launches, mean of 20 steps",
-                          "fit_vs_train_step": (loop / (steps * args.epochs)) and ts / (loop / (steps * args.epochs)),
+                          "fit_vs_train_step": ts and ts / (loop / (steps * args.epochs)),
                           "options_during_comparison": {"skip_dead_tiles": False, "deterministic": False},
                           "fit_ms_per_step_with_skip_dead_tiles": skip_ms, "dead_tile_frac_that_epoch": dead_fit,
                           "fit_wall_s": wall, "fit_wall_rays_samples_per_s": world * per_step * steps * args.epochs / wall,
@@ -555,8 +561,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--ray-chunks", type=int, default=None, help="override the configuration's ray_chunks (sensitivity sweeps; the line's workload says so)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need (roofline, "
+                    "metrics cost, dead-tile share, cpu_baseline; N > 1: all-reduce self-test and replica check; --mode fit: the "
+                    "train_step comparison and the skipping epoch), all outside the timed region")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: leave out the roofline's profiled steps")
     ap.add_argument("--mode", default="step", choices=["step", "fit"], help="step: the train_step loop on one resident batch (the contract's line); "
                                                                             "fit: NeRF.fit through the loader, the metrics and the monitor")
     ap.add_argument("--epochs", type=int, default=2, help="--mode fit: timed epochs")
@@ -565,8 +574,8 @@ def main():
     ap.add_argument("--ignore-nonfinite", action="store_true", help="TIMING EXPERIMENTS with ablation builds only (their gradients are garbage): "
                     "a step skipped for a non-finite gradient is not reported -- it costs the same launches, the Adam kernels are predicated off")
     ap.add_argument("--check-replicas", type=int, default=None, help="after the timed region: exact weight checksum of every rank reduced "
-                    "with MAX and MIN; `replica_drift` (must be 0.0) goes on the line.  Default: on for N > 1 (two one-word collectives, "
-                    "outside every timed region), off for N = 1")
+                    "with MAX and MIN; `replica_drift` (must be 0.0) goes on the line.  Default: on with --full for N > 1 (two one-word "
+                    "collectives, outside every timed region), off otherwise")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed region: write what the last timed step computed "
                     "(train step: both losses and both nets' weights after Adam; cfg5: the last frame's fine image and depth; --mode fit: "
                     "the per-epoch logs and the weights) to DIR/<name>.npy, float32 / float64, at most 64 MB")
@@ -575,7 +584,7 @@ def main():
         raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     from keras_nerf_amd import parallel
     if args.check_replicas is None:
-        args.check_replicas = int(args.gpus > 1 or parallel.single_rank_rehearsal())
+        args.check_replicas = int(args.full and (args.gpus > 1 or parallel.single_rank_rehearsal()))
     # the same environment for self-spawned ranks and for ranks of an external launcher (MASTER_ADDR, dmabuf IPC; N > 1: RCCL's
     # warnings to one file per rank, printed by a rank that fails)
     parallel.dist_env(args.gpus)
@@ -648,8 +657,9 @@ def run(args, world, rank, device_index, backend):
         raise
     selftest = {}
     if dist_on(world):
-        selftest = allreduce_selftest(nerf, world, backend)
-        sync(world)
+        if args.full:
+            selftest = allreduce_selftest(nerf, world, backend)
+            sync(world)
         nerf._allreduce_events = []            # HIP events on the compute stream around the gradient all-reduce of every timed step
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -680,15 +690,18 @@ def run(args, world, rank, device_index, backend):
     # image-metric launches and the update of the device-side means (MetricState.update), in NeRF.fit's asynchronous form.  (Rounds
     # 3-4 took the difference of two ~3 s loops, which does not resolve three small launches: -0.14 ms on the r04 line.)
     # Every rank runs the same number of steps (each holds an all-reduce).
-    nerf._metric_state.events = []
-    for _ in range(6):
-        nerf.train_step(data, sync=False)
-    sync(world)
-    ev, nerf._metric_state.events = nerf._metric_state.events[1:], None      # the first step's launches include one-time set-up
-    metrics_ms = sum(a_.elapsed_time(b_) for a_, b_ in ev) / max(len(ev), 1)
+    metrics_ms = None
+    if args.full:
+        nerf._metric_state.events = []
+        for _ in range(6):
+            nerf.train_step(data, sync=False)
+        sync(world)
+        ev, nerf._metric_state.events = nerf._metric_state.events[1:], None      # the first step's launches include one-time set-up
+        metrics_ms = sum(a_.elapsed_time(b_) for a_, b_ in ev) / max(len(ev), 1)
 
     roofline = None
-    if not args.no_profile:
+    profile = args.full and not args.no_profile
+    if profile:
         # every rank takes the two extra steps (train_step all-reduces); only rank 0 records HIP events around its kernels
         if rank == 0:
             nerf._ctx.profile_enable(True)
@@ -696,7 +709,7 @@ def run(args, world, rank, device_index, backend):
         for _ in range(2):
             nerf.train_step(data, with_metrics=False)
         sync(world)
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and profile:
         prof = nerf._ctx.profile_read()
         nerf._ctx.profile_enable(False)
         total = sum(ms for ms, _ in prof.values())
@@ -760,7 +773,7 @@ def run(args, world, rank, device_index, backend):
     # not a measurement of skipped work.
     opts = {k: bool(nerf._ctx.get_option(k)) for k in ("skip_dead_tiles", "deterministic")}
     dead_frac = None
-    if nerf._ctx.get_option("general_shape_path") == 0:
+    if args.full and nerf._ctx.get_option("general_shape_path") == 0:
         nerf._ctx.set_option("skip_dead_tiles", 1)
         if nerf._ctx.get_option("skip_dead_tiles_active"):
             nerf._ctx.tile_stats(reset=True)
@@ -771,7 +784,7 @@ def run(args, world, rank, device_index, backend):
     sync(world)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline()
 
     # vs_baseline: null on the headline (nothing is published for cfg2); on a ref* line the reference's own stated seconds per step

@@ -536,12 +536,13 @@ def _bench(args, env_extra, timeout=420):
 def test_bench_line_of_the_references_own_command_line_and_of_small_chunks(tmp_path):
     """`bench.py --config ref1` = train_single.py:16-17 (--img_wh 128 --ray_chunks 2048, batch 1), the command line the reference's
     comment quotes 3 s per step for: vs_baseline is filled on such lines only, against that number; the single-process line's
-    metric time is small and positive.  With --ray-chunks 256 the 64 chunks of a step run as four 4,096-ray sets of launches
+    metric time is small and positive (--full).  A plain run of the headline leaves roofline, metrics, dead-tile share and
+    cpu_baseline out.  With --ray-chunks 256 the 64 chunks of a step run as four 4,096-ray sets of launches
     (option merge_chunk_rays): the dominant kernel's launch count over the two profiled steps says so.  `--dump-outputs`: the last
     timed step's losses and weights as float32 .npy files, bit-identical between two runs with the same arguments in deterministic
     mode (same seeded inputs; the default mode differs only by the order of atomic sums)."""
     import json
-    r = _bench(["--config", "ref1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], {})
+    r = _bench(["--config", "ref1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"], {})
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
     assert "train_single.py:16-17" in line["config"]["workload"] and line["config"]["rays_per_step_per_gpu"] == 128 * 128
@@ -549,15 +550,17 @@ def test_bench_line_of_the_references_own_command_line_and_of_small_chunks(tmp_p
     assert "3 s/step" in line["baseline"] and "V100" in line["baseline"]
     assert 0 < line["metrics_ms_per_step"] < 5 and "hip events" in line["metrics_clock"]
     assert line["roofline"]["launches"] == 2 * 4                      # 8 chunks of 2,048 -> four launches of 4,096 rays per step
-    r = _bench(["--config", "ref1", "--ray-chunks", "256", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], {})
+    r = _bench(["--config", "ref1", "--ray-chunks", "256", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"], {})
     assert r.returncode == 0, r.stderr[-3000:]
     small = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
     assert "ray_chunks overridden: 256" in small["config"]["workload"] and small["roofline"]["launches"] == 2 * 4
     assert small["config"]["ray_chunks"] == 256 and small["config"]["launch_rays"] == 4096 and line["config"]["launch_rays"] == 4096
-    r = _bench(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-profile"], {})
+    r = _bench(["--steps", "2", "--warmup", "1"], {})
     assert r.returncode == 0, r.stderr[-3000:]
     head = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
     assert head["vs_baseline"] is None and "baseline" not in head        # nothing is published for the headline configuration
+    # a plain run (no --full) leaves out everything that needs runs of its own
+    assert head["roofline"] is None and head["cpu_baseline"] is None and head["metrics_ms_per_step"] is None and head["dead_tile_frac"] is None
     n_params = sum(p.size for p in O.init_params(O.NerfConfig(), 0))
     dumps = []
     for k in range(2):
@@ -583,7 +586,7 @@ def test_one_rank_rccl_rehearsal_of_the_multi_gpu_bench_path():
     the peers.  Both bench bodies (step and fit)."""
     import json
     env = {"KNERF_DIST_SINGLE": "1", "KNERF_DIST_BACKEND": "nccl"}
-    r = _bench(["--steps", "3", "--warmup", "1", "--config", "cfg4", "--no-cpu-baseline"], env)
+    r = _bench(["--steps", "3", "--warmup", "1", "--config", "cfg4", "--full", "--no-cpu-baseline"], env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["dist_backend"] == "nccl" and line["rccl_ranks"] == 1
@@ -616,7 +619,7 @@ def test_one_rank_rccl_rehearsal_of_the_multi_gpu_bench_path():
     base = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     t = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", "29517", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "cfg4",
-                        "--no-cpu-baseline", "--no-profile"], capture_output=True, text=True, timeout=300, env=dict(base, **env))
+                        "--full", "--no-cpu-baseline", "--no-profile"], capture_output=True, text=True, timeout=300, env=dict(base, **env))
     assert t.returncode == 0, t.stderr[-3000:]
     assert t.stdout.strip().count("\n") == 0, t.stdout[:2000]
     tl = json.loads(t.stdout)
@@ -637,7 +640,7 @@ def test_cfg4_rehearsal_three_ranks_on_one_gpu_replicas_stay_identical():
     ranks (train.py:75-93, 130-157); rank 0's line carries the collective's time and size; every rank says which device it sits on
     and how much of it is free; the launch environment (MASTER_ADDR, HSA_ENABLE_IPC_MODE_LEGACY) is NOT provided by the caller."""
     import json
-    r = _bench(["--gpus", "3", "--steps", "3", "--warmup", "1", "--config", "cfg4", "--no-cpu-baseline"], {"KNERF_DIST_BACKEND": "gloo"})
+    r = _bench(["--gpus", "3", "--steps", "3", "--warmup", "1", "--config", "cfg4", "--full", "--no-cpu-baseline"], {"KNERF_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
     assert line["n_gpus"] == 3 and line["dist_backend"] == "gloo" and line["config"]["parallelism"] == "dp3" and line["config"]["global_batch_images"] == 3
@@ -661,7 +664,7 @@ def test_cfg4_rehearsal_three_ranks_on_one_gpu_replicas_stay_identical():
         assert f"[bench rank {k}/3] local_rank {k} -> cuda:0" in r.stderr, r.stderr[-3000:]
         assert f"[bench rank {k}/3] device memory free" in r.stderr
     # the same through NeRF.fit (loader slices of the global batch, metrics, monitor on rank 0, barrier at epoch end)
-    r = _bench(["--gpus", "3", "--mode", "fit", "--config", "cfg4", "--epochs", "1"], {"KNERF_DIST_BACKEND": "gloo"})
+    r = _bench(["--gpus", "3", "--mode", "fit", "--config", "cfg4", "--epochs", "1", "--full"], {"KNERF_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
     assert line["n_gpus"] == 3 and line["replica_drift"] == 0.0 and line["steps"] == 33 and line["value"] > 0      # 100 views = 33 global batches of 3
@@ -671,7 +674,7 @@ def test_bench_line_after_the_launchers_second_attempt():
     """`bench.py --gpus 2` spawns its own ranks; both ranks of the FIRST set fail in the first all-reduce (injected, attempt 1 only):
     the launcher -- which never touched the GPU -- starts one fresh set with HSA_ENABLE_IPC_MODE_LEGACY absent, and the ONE JSON
     line of the run says so (train.py:75-93: the N > 1 job nobody will be there to restart; tests/test_dp_gloo.py has the CPU half)"""
-    r = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "cfg4", "--no-cpu-baseline", "--no-profile"],
+    r = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "cfg4", "--full", "--no-cpu-baseline", "--no-profile"],
                {"KNERF_DIST_BACKEND": "gloo", "KNERF_BENCH_INJECT_FAILURE": "*:first_all_reduce@1"}, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
