@@ -188,6 +188,20 @@ int knerf_generate_rays(knerf_ctx* ctx, void* stream, const float* c2w, const fl
                         uint64_t stream_id, int batch, int height, int width, int n_samples, float focal,
                         float near_plane, float far_plane, float* o, float* d, float* t);
 
+/* One training batch of rays drawn at random over ALL pixels of ALL views, in one launch: with P = n_views x height x width, slot i
+ * holds pixel perm(seed, epoch)(first + i), where perm is a keyed bijection of [0, P) evaluated per slot with no table (a six-round
+ * Feistel network over bit_length(P - 1) bits, round keys from Philox-4x32-10 under (seed, epoch), cycle-walked below P): the
+ * positions [0, P) of one epoch visit every pixel exactly once, another epoch is another permutation, and any caller can draw any
+ * slice.  Writes the pixel's ray o, d [n_rays,3] bit-identical to knerf_generate_rays for that pixel of that view, sample positions
+ * t [n_rays,n_samples] jittered like knerf_generate_rays (noise [n_rays,n_samples] in [0,1), or NULL: Philox with counter
+ * (n >> 2, slot, noise_stream, 2) under `seed`), target [n_rays,3] = images[v, y, x, 0:3] and, unless NULL, index [n_rays] = the
+ * flat pixel index v x H x W + y x W + x.  images [V,H,W,C] with C = 3 or 4, c2w [V,4,4].  KNERF_ERR_INVALID unless
+ * first + n_rays <= P, P < 2^40 and height x width < 2^31.  ctx may be NULL (stand-alone op). */
+int knerf_draw_ray_batch(knerf_ctx* ctx, void* stream, const float* images, const float* c2w, int n_views, int height, int width,
+                         int channels, float focal, float near_plane, float far_plane, int n_samples, uint64_t seed,
+                         uint64_t epoch, uint64_t first, int n_rays, const float* noise, uint64_t noise_stream, float* o, float* d,
+                         float* t, float* target, int64_t* index);
+
 /* ---- NeRFUtils as stand-alone ops (no context needed; the train/render path fuses the same arithmetic) ----
  * positional_encoding (utils.py:176-186): x [n_rows,3] -> out [n_rows, 3+6L].
  * composite = render_image_depth_chunk (utils.py:16-58): raw [R,S,4] = (r,g,b,sigma), t [R,S] -> image [R,3], depth [R]

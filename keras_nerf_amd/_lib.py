@@ -59,6 +59,8 @@ SIGNATURES = {
     "knerf_set_step_count": (C.c_int, [_P, C.c_int]),
     "knerf_generate_rays": (C.c_int, [_P, _P, _F, _F, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_float, C.c_float, C.c_float, _F, _F, _F]),
+    "knerf_draw_ray_batch": (C.c_int, [_P, _P, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int,
+                                       C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _F, C.c_uint64, _F, _F, _F, _F, _P]),
     "knerf_positional_encoding": (C.c_int, [_P, _F, C.c_longlong, C.c_int, _F]),
     "knerf_composite": (C.c_int, [_P, _F, _F, C.c_int, C.c_int, C.c_int, _F, _F, _F]),
     "knerf_inverse_cdf": (C.c_int, [_P, _F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F]),

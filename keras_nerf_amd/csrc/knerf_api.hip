@@ -17,6 +17,7 @@
 #include "layout.h"
 #include "occupancy.h"
 #include "query.h"
+#include "rays.h"
 #include "termination.h"
 #include "train_list.h"
 
@@ -1334,6 +1335,31 @@ int knerf_generate_rays(knerf_ctx* ctx, void* stream, const float* c2w, const fl
     a.c2w = c2w; a.noise = noise; a.o = o; a.d = d; a.t = t; a.B = batch; a.H = height; a.W = width; a.N = n_samples;
     a.focal = focal; a.near_ = near_plane; a.far_ = far_plane; a.seed = seed; a.stream_id = stream_id;
     if (launch_raygen(a, (hipStream_t)stream) != hipSuccess) return fail(ctx, KNERF_ERR_HIP, "generate_rays: launch failed");
+    return KNERF_OK;
+}
+
+int knerf_draw_ray_batch(knerf_ctx* ctx, void* stream, const float* images, const float* c2w, int n_views, int height, int width,
+                         int channels, float focal, float near_plane, float far_plane, int n_samples, uint64_t seed, uint64_t epoch,
+                         uint64_t first, int n_rays, const float* noise, uint64_t noise_stream, float* o, float* d, float* t,
+                         float* target, int64_t* index) {
+    if (!images || !c2w || !o || !d || !t || !target || n_views <= 0 || height <= 0 || width <= 0 || n_samples <= 0 || n_rays <= 0)
+        return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch: null/empty argument");
+    if (channels != 3 && channels != 4) return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch: channels must be 3 or 4");
+    const unsigned long long hw = (unsigned long long)height * (unsigned long long)width;
+    if (hw >= (1ull << 31) || hw * (unsigned long long)n_views >= (1ull << 40))
+        return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch: the dataset must hold fewer than 2^40 pixels (2^31 per view)");
+    const unsigned long long P = hw * (unsigned long long)n_views;
+    if (first > P || (unsigned long long)n_rays > P - first)
+        return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch: first + n_rays exceeds the pixels of the dataset");
+    if ((unsigned long long)n_rays * (unsigned long long)n_samples >= (1ull << 39))
+        return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch: n_rays x n_samples is too large for one launch");
+    RayBatchArgs a{};
+    a.images = images; a.c2w = c2w; a.noise = noise; a.o = o; a.d = d; a.t = t; a.target = target; a.index = (long long*)index;
+    a.perm = make_pixel_perm(P, seed, epoch);
+    a.first = first; a.seed = seed; a.noise_stream = noise_stream;
+    a.n_rays = n_rays; a.H = height; a.W = width; a.C = channels; a.N = n_samples;
+    a.focal = focal; a.near_ = near_plane; a.far_ = far_plane;
+    if (launch_raybatch(a, (hipStream_t)stream) != hipSuccess) return fail(ctx, KNERF_ERR_HIP, "draw_ray_batch: launch failed");
     return KNERF_OK;
 }
 

@@ -1,0 +1,1 @@
+from .raybatch import RayBatchDataset, ray_batch_permutation  # noqa: F401

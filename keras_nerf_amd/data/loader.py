@@ -20,7 +20,10 @@ dataset are kept RESIDENT ON THE DEVICE (100 views of 800 x 800 x 4 floats are 1
 them, so from the second epoch on a batch is one gather on the device plus the ray-generation kernel -- no host-to-device copy
 and, above all, no pageable copy that would make the host wait for the previous train step.  The few indices a batch needs
 travel through pinned memory with a non-blocking copy.  A dataset larger than `device_cache_gb` (default 64) is staged through
-two pinned buffers on a side stream instead, one batch ahead of the step that consumes it."""
+two pinned buffers on a side stream instead, one batch ahead of the step that consumes it.
+
+`RayImageDataset.ray_batches(rays_per_step)` gives the same data as batches of rays drawn at random over all pixels of all images
+(raybatch.py): the usual way to train a NeRF, which the reference does not have."""
 from __future__ import annotations
 
 import json
@@ -120,6 +123,13 @@ class RayImageDataset:
         return RayImageDataset(self.image_paths, self.camera_params, self.image_loader, self._rg_factory, self.batch_size,
                                seed=seed, limit=self._limit if limit is None else limit, rank=self._rank, world=self._world,
                                device_cache_gb=self.device_cache_gb, _shared=self._shared)
+
+    def ray_batches(self, rays_per_step, seed=0, steps_per_epoch=None):
+        """the same data as batches of `rays_per_step` rays drawn at random over all pixels of all images, one permutation of the
+        pixels per epoch (raybatch.RayBatchDataset; needs the whole dataset within `device_cache_gb`).  Data parallel:
+        `rays_per_step` is the GLOBAL count, every rank draws its 1/world slice of the same permutation."""
+        from .raybatch import RayBatchDataset
+        return RayBatchDataset(self, rays_per_step, seed=seed, steps_per_epoch=steps_per_epoch)
 
     def _image(self, i):
         if i not in self._cache:

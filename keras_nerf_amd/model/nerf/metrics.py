@@ -12,6 +12,7 @@ import math
 import torch
 
 NAMES = ("coarse_loss", "coarse_psnr", "coarse_ssim", "fine_loss", "fine_psnr", "fine_ssim")
+RAY_NAMES = ("coarse_loss", "coarse_psnr", "fine_loss", "fine_psnr")      # a batch of scattered rays has no SSIM
 
 
 def _check_cuda(a):
@@ -82,21 +83,33 @@ class MetricState:
             e1.record(torch.cuda.current_stream(self.device))
             self.events.append((e0, e1))
 
-    def snapshot(self) -> "MetricLogs":
-        return MetricLogs(self.state.clone())
+    def update_rays(self, losses):
+        """one step's contribution when the batch is scattered rays: `losses` = device tensor [2], the batch's coarse and fine mean
+        squared errors; they feed the two loss rows, and -10 log10 of them the two PSNR rows.  Device arithmetic, no synchronisation."""
+        if getattr(self, "_ray_rows", None) is None:
+            self._ray_rows = torch.tensor([NAMES.index(n) for n in ("coarse_loss", "fine_loss", "coarse_psnr", "fine_psnr")],
+                                          device=self.device)
+            self._ray_ones = torch.ones(4, device=self.device, dtype=torch.float64)
+        mse = losses.to(device=self.device, dtype=torch.float64).reshape(2)
+        self.state[:, 0].index_add_(0, self._ray_rows, torch.cat([mse, -10.0 * torch.log10(mse)]))
+        self.state[:, 1].index_add_(0, self._ray_rows, self._ray_ones)
+
+    def snapshot(self, names=NAMES) -> "MetricLogs":
+        return MetricLogs(self.state.clone(), names)
 
 
 class MetricLogs(collections.abc.Mapping):
-    """What train_step / test_step return: the six running means AS OF that step.  The values sit in a device-side snapshot and
-    come to the host (one copy, one synchronisation) the first time one of them is read."""
+    """What train_step / test_step return: the running means AS OF that step -- all six, or the subset `names` a step on scattered
+    rays carries.  The values sit in a device-side snapshot and come to the host (one copy, one synchronisation) the first time
+    one of them is read."""
 
-    def __init__(self, snapshot: torch.Tensor):
-        self._snap, self._host = snapshot, None
+    def __init__(self, snapshot: torch.Tensor, names=NAMES):
+        self._snap, self._host, self._names = snapshot, None, tuple(names)
 
     def _values(self):
         if self._host is None:
             s = self._snap.cpu()
-            self._host = {n: (float(s[i, 0] / s[i, 1]) if float(s[i, 1]) else 0.0) for i, n in enumerate(NAMES)}
+            self._host = {n: (float(s[i, 0] / s[i, 1]) if float(s[i, 1]) else 0.0) for i, n in enumerate(NAMES) if n in self._names}
             self._snap = None
         return self._host
 
@@ -104,10 +117,10 @@ class MetricLogs(collections.abc.Mapping):
         return self._values()[k]
 
     def __iter__(self):
-        return iter(NAMES)
+        return iter(self._names)
 
     def __len__(self):
-        return len(NAMES)
+        return len(self._names)
 
     def __repr__(self):
         return f"MetricLogs({self._values()!r})"

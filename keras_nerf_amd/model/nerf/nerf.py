@@ -18,7 +18,7 @@ import torch
 
 from ... import parallel
 from ...runtime import COARSE, FINE, OCCUPANCY_OUTSIDE, KnerfContext, NonFiniteGradientError, marching_cubes, occupancy_from_grid, occupancy_spec  # noqa: F401
-from .metrics import Mean, MetricLogs, MetricState
+from .metrics import RAY_NAMES, Mean, MetricLogs, MetricState
 from .mlp import NeRFMLP
 from .utils import NeRFUtils
 
@@ -475,14 +475,25 @@ class NeRF:
     # ------------------------------------------------------------------ train / test step
     def train_step(self, inputs, u=None, with_metrics=True, sync=True):
         """nerf.py:332-473.  inputs = (images [B,H,W,3|4], (o, d, t)).  Returns the six running means (read back lazily).
+        A 2-D first element makes it a step on scattered rays (data.RayBatchDataset): inputs = (target [n,3], (o [n,3], d [n,3],
+        t [n,n_coarse])) with n a multiple of ray_chunks; its logs carry the losses and PSNRs, no SSIM.
         sync=True (a direct call): waits for the step, so a non-finite gradient raises from THIS call as in the reference
         (nerf.py:381-382).  sync=False (what `fit` uses): nothing waits for the GPU; a skipped step raises from the first later
         poll (fit polls at every epoch end, save_model and get_weights poll before they read weights)."""
         images, rays = inputs
-        images = self._ctx.f32(images)[..., :3].contiguous()                      # nerf.py:335
-        o, d, t = self._flat_rays(rays)
-        N, R, C = self.num_rays, self.ray_chunks, self.sequential_chunks
-        tgt = images.reshape(N, 3)
+        ray_mode = getattr(images, "ndim", None) == 2          # a batch of scattered rays: (target [n,3], (o [n,3], d [n,3], t [n,Nc]))
+        if ray_mode:
+            tgt = self._ctx.f32(images)[:, :3].contiguous()
+            N, R = tgt.shape[0], self.ray_chunks
+            if N % R:
+                raise ValueError(f"a batch of {N} rays is not a multiple of ray_chunks = {R}")
+            f = self._ctx.f32
+            o, d, t = f(rays[0]).reshape(N, 3), f(rays[1]).reshape(N, 3), f(rays[2]).reshape(N, self.n_coarse)
+        else:
+            images = self._ctx.f32(images)[..., :3].contiguous()                  # nerf.py:335
+            o, d, t = self._flat_rays(rays)
+            N, R = self.num_rays, self.ray_chunks
+            tgt = images.reshape(N, 3)
         uf = None if u is None else self._ctx.f32(u).reshape(N, self.n_fine)
         ci = torch.empty((N, 3), device=self.device); fi = torch.empty((N, 3), device=self.device)
         self._loss_acc.zero_()
@@ -507,9 +518,14 @@ class NeRF:
             # first later call that finds it completed
             self._ctx.poll_nonfinite(wait=False)
             return {"coarse_loss": self._loss_acc[0], "fine_loss": self._loss_acc[1]}
-        B, H, W = self.batch_size, self.image_height, self.image_width
-        self._metric_state.update(images, ci.reshape(B, H, W, 3), fi.reshape(B, H, W, 3), self._loss_acc)
-        logs = self._metric_state.snapshot()
+        if ray_mode:
+            # the chunks are equally sized, so the accumulated losses are the batch's mean squared errors: losses and PSNR, no SSIM
+            self._metric_state.update_rays(self._loss_acc)
+            logs = self._metric_state.snapshot(RAY_NAMES)
+        else:
+            B, H, W = self.batch_size, self.image_height, self.image_width
+            self._metric_state.update(images, ci.reshape(B, H, W, 3), fi.reshape(B, H, W, 3), self._loss_acc)
+            logs = self._metric_state.snapshot()
         self._ctx.poll_nonfinite(wait=bool(sync))      # sync: as the reference, the failing batch raises from its own train_step
         return logs
 

@@ -555,6 +555,12 @@ class KnerfContext:
                                                  _ptr(t)))
         return o, d, t
 
+    def draw_ray_batch(self, images, c2w, focal, near, far, n_samples, seed, epoch, first, n_rays, noise=None, noise_stream=0,
+                       want_index=False):
+        """one batch of rays drawn over all pixels of `images` [V,H,W,3|4] (module-level draw_ray_batch, on this context)"""
+        return draw_ray_batch(images, c2w, focal, near, far, n_samples, seed, epoch, first, n_rays, noise, noise_stream, want_index,
+                              ctx=self)
+
     PROFILE_CLASSES = ("mlp_fwd_coarse", "mlp_fwd_fine", "composite", "sample_fine", "mlp_bwd_coarse", "mlp_bwd_fine",
                        "wgrad_coarse", "wgrad_fine", "adam_repack")
 
@@ -567,6 +573,41 @@ class KnerfContext:
         ms = (C.c_double * n)(); cnt = (C.c_int64 * n)()
         self._check(self.lib.knerf_profile_read(self._ctx, ms, cnt, n))
         return {k: (ms[i], int(cnt[i])) for i, k in enumerate(self.PROFILE_CLASSES)}
+
+
+def draw_ray_batch(images, c2w, focal, near, far, n_samples, seed, epoch, first, n_rays, noise=None, noise_stream=0,
+                   want_index=False, ctx=None):
+    """knerf_draw_ray_batch: slot i = pixel perm(seed, epoch)(first + i) of images [V,H,W,3|4] (float32, on the device) with camera
+    matrices c2w [V,4,4].  Returns (o [n,3], d [n,3], t [n,n_samples], target [n,3]) and, with want_index, the flat pixel indices
+    [n] (int64).  One launch on the current stream, nothing waits.  ctx: a KnerfContext, or None (the op needs none)."""
+    if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype == torch.float32 and images.dim() == 4):
+        raise KnerfError("draw_ray_batch wants the images as one float32 [V,H,W,C] tensor on the device; there is no CPU path")
+    dev = images.device
+    images = images.contiguous()
+    c2w = _f32(c2w, dev).reshape(-1, 4, 4)
+    V, H, W, C = images.shape
+    if c2w.shape[0] != V:
+        raise ValueError(f"{V} images but {c2w.shape[0]} camera matrices")
+    n = int(n_rays)
+    if n <= 0:
+        raise ValueError("n_rays must be positive")
+    if noise is not None:
+        noise = _f32(noise, dev)
+        if tuple(noise.shape) != (n, n_samples):
+            raise ValueError(f"noise must be [{n}, {n_samples}]")
+    o = torch.empty((n, 3), device=dev); d = torch.empty_like(o); target = torch.empty_like(o)
+    t = torch.empty((n, n_samples), device=dev)
+    index = torch.empty((n,), device=dev, dtype=torch.int64) if want_index else None
+    lib = ctx.lib if ctx is not None else _lib.load()
+    rc = lib.knerf_draw_ray_batch(None if ctx is None else ctx._ctx, torch.cuda.current_stream(dev).cuda_stream, _ptr(images),
+                                  _ptr(c2w), V, H, W, C, float(focal), float(near), float(far), int(n_samples), int(seed), int(epoch),
+                                  int(first), n, _ptr(noise), int(noise_stream), _ptr(o), _ptr(d), _ptr(t), _ptr(target), _ptr(index))
+    if ctx is not None:
+        ctx._check(rc)
+    elif rc != 0:
+        msg = f"knerf_draw_ray_batch failed ({rc}): {lib.knerf_last_error(None).decode(errors='replace')}"
+        raise ValueError(msg) if rc == _lib.KNERF_ERR_INVALID else KnerfError(msg)
+    return (o, d, t, target, index) if want_index else (o, d, t, target)
 
 
 def marching_cubes(grid: torch.Tensor, threshold: float, lo, hi, normals: bool = True):
