@@ -2,7 +2,9 @@
 
 Gradients: compared per tensor against the oracle in the kernels' arithmetic (emulate_bf16: bf16 matmul operands, fp32
 accumulate) to 2.5e-2 of the tensor's max |g|, and against the fp32 oracle (the reference's arithmetic) to 8e-2 (about
-twice the measured 1.1e-2 / 5e-2); the measured values are logged.  Adam: weights after several steps against the oracle's Keras-form Adam."""
+twice the measured 1.1e-2 / 5e-2); the measured values are logged.  Adam: weights after several steps with the training kernels' own
+gradients against the oracle's Keras-form Adam -- loosely (direction and 3 % of the movement: the gradients carry 1 % bf16 noise); the
+exact comparison of the update, the step count and the re-packing, with injected gradients against float64, is tests/test_gpu_optimizer.py."""
 import numpy as np
 import pytest
 from keras_nerf_amd.debug import debug_buffer
