@@ -180,7 +180,66 @@ int knerf_tile_stats_net(knerf_ctx* ctx, void* stream, int64_t* live, int64_t* t
  * i.e. the counts of the step just enqueued; wait == 0: of the newest step that has completed).  out: 3 values. */
 int knerf_grad_diagnostics(knerf_ctx* ctx, void* stream, int wait, int64_t* out);
 int knerf_step_count(const knerf_ctx* ctx);
+/* Sets the count of applied steps (host mirror and device counter) and re-derives the device-side rate of the next step from it --
+ * under a learning-rate schedule (knerf_set_optimizer) from the schedule. */
 int knerf_set_step_count(knerf_ctx* ctx, int step);
+
+/* ---- Optimizer options: tf.keras.optimizers.Adam(learning_rate=<schedule>, clipvalue / clipnorm / global_clipnorm, weight_decay) as
+ * the reference gets it from tf.keras.optimizers.get (nerf.py:163-165).  Everything is opt-in: a context that never calls
+ * knerf_set_optimizer, or calls it with a constant schedule, no clipping and no decay, runs knerf_apply_adam exactly as before (the
+ * same launches, the same bits).  beta1, beta2 and epsilon stay in knerf_config.
+ *   Schedule: lr(step), step = the number of steps APPLIED before this one (the first step uses lr(0), as Keras evaluates the schedule
+ *     at `iterations` before incrementing; a step skipped for a non-finite gradient advances nothing), evaluated on the device in double;
+ *     lr_t = lr(step) sqrt(1 - beta2^t) / (1 - beta1^t), t = step + 1.
+ *       KNERF_SCHEDULE_CONSTANT     lr                                  (held as fp32, as knerf_config.lr is)
+ *       KNERF_SCHEDULE_EXPONENTIAL  lr * decay_rate^(step / decay_steps); staircase != 0: the exponent is floored
+ *       KNERF_SCHEDULE_COSINE       s = min(step, decay_steps); lr * ((1 - alpha) * 0.5 * (1 + cos(pi s / decay_steps)) + alpha)
+ *       KNERF_SCHEDULE_PIECEWISE    values[i] for the first i with step <= boundaries[i], else values[n_values - 1]
+ *                                   (n_values <= KNERF_SCHEDULE_MAX_VALUES values, n_values - 1 ascending boundaries)
+ *   Clipping (clip = one KNERF_CLIP_* kind, or 0): applied to the gradient knerf_apply_adam finds in the accumulator -- after a
+ *     data-parallel all-reduce, so every rank derives the same factor -- behind the finite check (whose skip rule is unchanged) and in
+ *     front of the moment updates.
+ *       KNERF_CLIP_VALUE        g = min(max(g, -c), c)
+ *       KNERF_CLIP_NORM         per tensor (the 2 n_layers + 8 tensors of a net in Keras order): g * (c / max(|g_tensor|, c))
+ *       KNERF_CLIP_GLOBAL_NORM  g * min(1, c / |g_net|) over all tensors of ONE net (the reference has one optimizer per net, so the
+ *                               coarse and the fine norm are separate)
+ *     Sums of squares are taken in double (any finite fp32 gradient is safe) without floating-point atomics: per-workgroup partial sums,
+ *     then an ordered pass, so two runs give the same bits.  The factor is computed in double and rounded once to fp32; it is exactly
+ *     1.0f where nothing is clipped.  TensorFlow multiplies by c * min(1 / |g|, 1 / c) instead: the two differ by at most one ulp of the
+ *     factor.  One launch more than the plain step (the finite check is folded into the norm pass), no host synchronisation.
+ *   Decoupled weight decay (Keras `weight_decay`, the AdamW form): in front of the Adam update of the same step, every parameter
+ *     w -= w * fp32(weight_decay * lr(step)) -- the scheduled rate, not lr_t; the product in double on the device.  A skipped step
+ *     decays nothing.
+ * Element order of one step: read g, zero the accumulator, return if the step is non-finite, clip, decay, m, v, w. */
+enum { KNERF_SCHEDULE_CONSTANT = 0, KNERF_SCHEDULE_EXPONENTIAL = 1, KNERF_SCHEDULE_COSINE = 2, KNERF_SCHEDULE_PIECEWISE = 3 };
+enum { KNERF_CLIP_NONE = 0, KNERF_CLIP_VALUE = 1, KNERF_CLIP_NORM = 2, KNERF_CLIP_GLOBAL_NORM = 4 };   /* bits: more than one set is refused */
+#define KNERF_SCHEDULE_MAX_VALUES 16
+typedef struct knerf_optimizer {
+    int32_t schedule;            /* KNERF_SCHEDULE_* */
+    int32_t staircase;           /* exponential: 0 / 1 */
+    int32_t n_values;            /* piecewise: 1..KNERF_SCHEDULE_MAX_VALUES */
+    int32_t clip;                /* KNERF_CLIP_* */
+    double lr;                   /* the constant rate; the initial rate of the exponential and the cosine schedule */
+    double decay_steps;          /* exponential, cosine: > 0 */
+    double decay_rate;           /* exponential: >= 0 */
+    double alpha;                /* cosine: >= 0 */
+    double clip_arg;             /* c > 0 when clip != 0 */
+    double weight_decay;         /* >= 0; 0: off */
+    int64_t boundaries[KNERF_SCHEDULE_MAX_VALUES - 1];   /* piecewise: ascending, >= 0 */
+    double values[KNERF_SCHEDULE_MAX_VALUES];            /* piecewise: >= 0 */
+} knerf_optimizer;
+/* Callable at any time between steps; stream-ordered (steps enqueued earlier on `stream` keep the old settings), and the rate of
+ * the next step is re-derived on the device from the DEVICE step counter, so nothing waits.  A constant schedule with no clipping and
+ * no decay selects the plain kernels with knerf_config.lr replaced: a set_learning_rate for host callbacks.  KNERF_ERR_INVALID (with
+ * a message) on: an unknown schedule or clip kind, two clip kinds at once, decay_steps <= 0, boundaries that do not ascend, negative
+ * or non-finite numbers, n_values outside 1..KNERF_SCHEDULE_MAX_VALUES, a KNERF_FLAG_ENCODED_WIDTHS context. */
+int knerf_set_optimizer(knerf_ctx* ctx, void* stream, const knerf_optimizer* opt);
+int knerf_get_optimizer(knerf_ctx* ctx, knerf_optimizer* opt);
+/* Adam's two slots of one net, HOST pointers to n = param_count floats each, in the layout of knerf_get_weights.  Together with
+ * knerf_step_count / knerf_set_step_count and the weights this is the whole optimizer state: a context given all of it continues a
+ * run bit for bit.  Both synchronise `stream`. */
+int knerf_get_adam_state(knerf_ctx* ctx, void* stream, int net, float* m_host, float* v_host, size_t n);
+int knerf_set_adam_state(knerf_ctx* ctx, void* stream, int net, const float* m_host, const float* v_host, size_t n);
 
 /* RaysGenerator.__call__ (keras_nerf/data/rays.py:69-130) on device: c2w [B,4,4], noise [B,H,W,N] in [0,1) or
  * NULL for Philox; writes o,d [B,H,W,3] and t [B,H,W,N].  ctx may be NULL (stand-alone op). */

@@ -19,6 +19,18 @@ class KnerfConfig(C.Structure):
                 ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float), ("flags", C.c_int32)]
 
 
+class KnerfOptimizer(C.Structure):
+    """struct knerf_optimizer (include/knerf.h): schedule kind and parameters, clip kind and argument, weight decay"""
+    _fields_ = [("schedule", C.c_int32), ("staircase", C.c_int32), ("n_values", C.c_int32), ("clip", C.c_int32),
+                ("lr", C.c_double), ("decay_steps", C.c_double), ("decay_rate", C.c_double), ("alpha", C.c_double),
+                ("clip_arg", C.c_double), ("weight_decay", C.c_double),
+                ("boundaries", C.c_int64 * 15), ("values", C.c_double * 16)]
+
+
+SCHEDULE_CONSTANT, SCHEDULE_EXPONENTIAL, SCHEDULE_COSINE, SCHEDULE_PIECEWISE = 0, 1, 2, 3
+CLIP_NONE, CLIP_VALUE, CLIP_NORM, CLIP_GLOBAL_NORM = 0, 1, 2, 4
+SCHEDULE_MAX_VALUES = 16
+
 FLAG_FORCE_GENERIC = 1
 FLAG_ENCODED_WIDTHS = 2      # pos_emb_xyz / pos_emb_dir hold the two encoded input widths of a stand-alone NeRFMLP (include/knerf.h)
 
@@ -57,6 +69,10 @@ SIGNATURES = {
     "knerf_mlp_call": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_uint64, _P]),
     "knerf_step_count": (C.c_int, [_P]),
     "knerf_set_step_count": (C.c_int, [_P, C.c_int]),
+    "knerf_set_optimizer": (C.c_int, [_P, _P, C.POINTER(KnerfOptimizer)]),
+    "knerf_get_optimizer": (C.c_int, [_P, C.POINTER(KnerfOptimizer)]),
+    "knerf_get_adam_state": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]),
+    "knerf_set_adam_state": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]),
     "knerf_generate_rays": (C.c_int, [_P, _P, _F, _F, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_float, C.c_float, C.c_float, _F, _F, _F]),
     "knerf_draw_ray_batch": (C.c_int, [_P, _P, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int,

@@ -71,6 +71,17 @@ struct knerf_ctx {
     float* d_lr_t = nullptr;           // device: bias-corrected learning rate of the next step, derived from d_step on the device
     int* h_status = nullptr;           // pinned host: [0] number of skipped (non-finite) steps so far, written by the device
     int skipped_seen = 0;
+    // optimizer options (knerf_set_optimizer; optim_ext.h).  opt_ext: some extension is active and knerf_apply_adam takes the
+    // extended kernels; false (the default, and a constant schedule without clipping or decay): the plain kernels with cfg.lr.
+    // Device side, allocated by the first call that needs it: d_opt_f = [0] fp32(weight_decay * lr(step)) of the next step, [1..] the
+    // clip factors [2][kOptMaxTensors]; d_opt_partial = [2][opt_items] sums of squares; d_opt_tab = tensor offsets [n + 1], first item
+    // of each tensor [n + 1], item begin [items], item end [items]
+    knerf_optimizer opt = {};
+    bool opt_ext = false;
+    float* d_opt_f = nullptr;
+    double* d_opt_partial = nullptr;
+    int* d_opt_tab = nullptr;
+    int opt_tensors = 0, opt_items = 0;
     int n_cu = 256;
     // general-shape MLP path (generic.h): used when the fused kernels do not cover the config's MLP shape (layout.h KNERF_FUSED_SHAPES)
     bool generic = false;

@@ -2,6 +2,7 @@
 // lines each one replaces).  Host-side only: owns device memory, sequences the kernels on the caller's stream.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -16,6 +17,7 @@
 #include "generic.h"
 #include "layout.h"
 #include "occupancy.h"
+#include "optim_ext.h"
 #include "query.h"
 #include "rays.h"
 #include "termination.h"
@@ -746,6 +748,7 @@ int knerf_create(const knerf_config* cfg, knerf_ctx** out) {
         return fail(nullptr, KNERF_ERR_NODEVICE, std::string("libknerf_hip is built for gfx950 only; device is ") + prop.gcnArchName);
     ctx = new knerf_ctx();
     ctx->cfg = *cfg;
+    ctx->opt.lr = cfg->lr;
     // the fused kernels cover the trunk shapes of layout.h KNERF_FUSED_SHAPES (widths 256 and 128; the reference's encodings unless the build added others); everything
     // else -- and, for tests, any shape under KNERF_FLAG_FORCE_GENERIC -- runs on the general-shape kernels
     const int sid = widths ? -1 : fused_shape_id(cfg->n_layers, cfg->skip_layer, cfg->dense_units, cfg->pos_emb_xyz, cfg->pos_emb_dir);
@@ -845,6 +848,7 @@ int knerf_destroy(knerf_ctx* ctx) {
         free_dev(N.w); free_dev(N.m); free_dev(N.v); free_dev(N.fwd_stream); free_dev(N.bwd_stream); free_dev(N.bias);
     }
     free_dev(ctx->grads); free_dev(ctx->aux); free_dev(ctx->d_flag); free_dev(ctx->loss_tmp); free_dev(ctx->d_step); free_dev(ctx->d_lr_t);
+    free_dev(ctx->d_opt_f); free_dev(ctx->d_opt_partial); free_dev(ctx->d_opt_tab);
     if (ctx->h_status) { (void)hipHostFree(ctx->h_status); ctx->h_status = nullptr; }
     if (ctx->h_diag) { (void)hipHostFree(ctx->h_diag); ctx->h_diag = nullptr; }
     free_dev(ctx->d_diag); free_dev(ctx->diag_tmp);
@@ -1167,9 +1171,164 @@ int knerf_train_batch(knerf_ctx* ctx, void* stream, const float* o, const float*
     return KNERF_OK;
 }
 
+// ---- optimizer options (include/knerf.h knerf_set_optimizer; optim_ext.h) ------------------------------------------------------
+static SchedArgs sched_args(const knerf_ctx* ctx) {
+    const knerf_optimizer& o = ctx->opt;
+    SchedArgs a{};
+    a.kind = o.schedule; a.staircase = o.staircase; a.n_values = o.n_values;
+    a.lr = o.lr; a.decay_steps = o.decay_steps; a.decay_rate = o.decay_rate; a.alpha = o.alpha; a.weight_decay = o.weight_decay;
+    for (int i = 0; i < KNERF_SCHEDULE_MAX_VALUES - 1; ++i) a.boundaries[i] = o.boundaries[i];
+    for (int i = 0; i < KNERF_SCHEDULE_MAX_VALUES; ++i) a.values[i] = o.values[i];
+    a.b1 = ctx->cfg.beta1; a.b2 = ctx->cfg.beta2;
+    return a;
+}
+// device tables and buffers of the extended step, once per context: the tensors of one net in Keras order (mlp.py:11-27: layer_i
+// kernel [in, units] and bias, then sigma, features, rgb_features, rgb) and their cut into items of the sum-of-squares pass
+static int ensure_opt_buffers(knerf_ctx* ctx) {
+    if (ctx->d_opt_tab) return KNERF_OK;
+    const knerf_config& c = ctx->cfg;
+    const bool widths = (c.flags & KNERF_FLAG_ENCODED_WIDTHS) != 0;
+    const int xyz = widths ? c.pos_emb_xyz : 3 + 6 * c.pos_emb_xyz, dir = widths ? c.pos_emb_dir : 3 + 6 * c.pos_emb_dir, U = c.dense_units;
+    std::vector<int32_t> off{0};
+    auto dense = [&](int fan_in, int fan_out) { off.push_back(off.back() + fan_in * fan_out); off.push_back(off.back() + fan_out); };
+    int fan_in = xyz;
+    for (int i = 0; i < c.n_layers; ++i) {
+        dense(fan_in, U);
+        fan_in = (i % c.skip_layer == 0 && i > 0) ? U + xyz : U;
+    }
+    dense(fan_in, 1); dense(fan_in, U); dense(U + dir, U / 2); dense(U / 2, 3);
+    const int T = (int)off.size() - 1;
+    if (off.back() != ctx->n_params || T > kOptMaxTensors) return fail(ctx, KNERF_ERR_INVALID, "set_optimizer: the tensor list does not match the parameter count");
+    std::vector<int32_t> item0{0}, begin, end;
+    for (int t = 0; t < T; ++t) {
+        for (int b = off[t]; b < off[t + 1]; b += kOptItemElems) { begin.push_back(b); end.push_back(std::min(b + kOptItemElems, off[t + 1])); }
+        item0.push_back((int32_t)begin.size());
+    }
+    const int I = (int)begin.size();
+    std::vector<int32_t> tab(off);
+    tab.insert(tab.end(), item0.begin(), item0.end()); tab.insert(tab.end(), begin.begin(), begin.end()); tab.insert(tab.end(), end.begin(), end.end());
+    HIPCHK(hipMalloc(&ctx->d_opt_tab, tab.size() * sizeof(int32_t)));
+    HIPCHK(hipMemcpy(ctx->d_opt_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc(&ctx->d_opt_partial, 2 * (size_t)I * sizeof(double)));
+    HIPCHK(hipMemset(ctx->d_opt_partial, 0, 2 * (size_t)I * sizeof(double)));
+    HIPCHK(hipMalloc(&ctx->d_opt_f, (1 + 2 * (size_t)kOptMaxTensors) * sizeof(float)));
+    HIPCHK(hipMemset(ctx->d_opt_f, 0, (1 + 2 * (size_t)kOptMaxTensors) * sizeof(float)));
+    ctx->opt_tensors = T; ctx->opt_items = I;
+    return KNERF_OK;
+}
+
+int knerf_set_optimizer(knerf_ctx* ctx, void* stream, const knerf_optimizer* opt) {
+    if (!ctx) return KNERF_ERR_INVALID;
+    if (!opt) return fail(ctx, KNERF_ERR_INVALID, "set_optimizer: null argument");
+    if (ctx->mlp_only) return fail(ctx, KNERF_ERR_INVALID, "set_optimizer: a KNERF_FLAG_ENCODED_WIDTHS context has no optimizer");
+    knerf_optimizer o = *opt;
+    auto ok = [](double v) { return std::isfinite(v) && v >= 0; };
+    if (o.schedule < KNERF_SCHEDULE_CONSTANT || o.schedule > KNERF_SCHEDULE_PIECEWISE) return fail(ctx, KNERF_ERR_INVALID, "set_optimizer: unknown schedule kind " + std::to_string(o.schedule));
+    if (o.clip != KNERF_CLIP_NONE && o.clip != KNERF_CLIP_VALUE && o.clip != KNERF_CLIP_NORM && o.clip != KNERF_CLIP_GLOBAL_NORM)
+        return fail(ctx, KNERF_ERR_INVALID, (o.clip > 0 && o.clip < 8) ? "set_optimizer: at most one of clipvalue, clipnorm and global_clipnorm may be active"
+                                                                      : "set_optimizer: unknown clip kind " + std::to_string(o.clip));
+    if (o.clip != KNERF_CLIP_NONE && !(ok(o.clip_arg) && o.clip_arg > 0)) return fail(ctx, KNERF_ERR_INVALID, "set_optimizer: the clip argument must be finite and > 0");
+    if (!ok(o.weight_decay)) return fail(ctx, KNERF_ERR_INVALID, "set_optimizer: weight_decay must be finite and >= 0");
+    if (o.schedule != KNERF_SCHEDULE_PIECEWISE && !ok(o.lr)) return fail(ctx, KNERF_ERR_INVALID, "set_optimizer: the learning rate must be finite and >= 0");
+    if (o.schedule == KNERF_SCHEDULE_EXPONENTIAL || o.schedule == KNERF_SCHEDULE_COSINE) {
+        if (!(std::isfinite(o.decay_steps) && o.decay_steps > 0)) return fail(ctx, KNERF_ERR_INVALID, "set_optimizer: decay_steps must be finite and > 0");
+        if (o.schedule == KNERF_SCHEDULE_EXPONENTIAL && !ok(o.decay_rate)) return fail(ctx, KNERF_ERR_INVALID, "set_optimizer: decay_rate must be finite and >= 0");
+        if (o.schedule == KNERF_SCHEDULE_COSINE && !ok(o.alpha)) return fail(ctx, KNERF_ERR_INVALID, "set_optimizer: alpha must be finite and >= 0");
+    }
+    if (o.schedule == KNERF_SCHEDULE_PIECEWISE) {
+        if (o.n_values < 1 || o.n_values > KNERF_SCHEDULE_MAX_VALUES)
+            return fail(ctx, KNERF_ERR_INVALID, "set_optimizer: a piecewise schedule takes 1.." + std::to_string(KNERF_SCHEDULE_MAX_VALUES) + " values, got " + std::to_string(o.n_values));
+        for (int i = 0; i < o.n_values; ++i)
+            if (!ok(o.values[i])) return fail(ctx, KNERF_ERR_INVALID, "set_optimizer: piecewise values must be finite and >= 0");
+        for (int i = 0; i + 1 < o.n_values; ++i)
+            if (o.boundaries[i] < 0 || (i > 0 && o.boundaries[i] <= o.boundaries[i - 1])) return fail(ctx, KNERF_ERR_INVALID, "set_optimizer: piecewise boundaries must be >= 0 and ascend");
+    }
+    // what the chosen kinds do not read is stored as zero, so that knerf_get_optimizer returns a canonical record
+    if (o.schedule != KNERF_SCHEDULE_EXPONENTIAL) { o.staircase = 0; o.decay_rate = 0; }
+    if (o.schedule != KNERF_SCHEDULE_EXPONENTIAL && o.schedule != KNERF_SCHEDULE_COSINE) o.decay_steps = 0;
+    if (o.schedule != KNERF_SCHEDULE_COSINE) o.alpha = 0;
+    if (o.schedule != KNERF_SCHEDULE_PIECEWISE) o.n_values = 0; else o.lr = 0;
+    for (int i = 0; i < KNERF_SCHEDULE_MAX_VALUES; ++i) if (i >= o.n_values) o.values[i] = 0;
+    for (int i = 0; i < KNERF_SCHEDULE_MAX_VALUES - 1; ++i) if (i + 1 >= o.n_values) o.boundaries[i] = 0;
+    o.staircase = o.staircase != 0;
+    if (o.clip == KNERF_CLIP_NONE) o.clip_arg = 0;
+    if (o.schedule == KNERF_SCHEDULE_CONSTANT) o.lr = (double)(float)o.lr;          // held as fp32, as knerf_config.lr: the plain kernels' rate
+    const bool ext = o.schedule != KNERF_SCHEDULE_CONSTANT || o.clip != KNERF_CLIP_NONE || o.weight_decay > 0;
+    if (ext)
+        if (int r = ensure_opt_buffers(ctx)) return r;
+    ctx->opt = o; ctx->opt_ext = ext;
+    hipStream_t s = (hipStream_t)stream;
+    if (ext) {
+        HIPCHK(launch_step_set_ext(-1, ctx->d_step, ctx->d_lr_t, o.weight_decay > 0 ? ctx->d_opt_f : nullptr, sched_args(ctx), s));
+    } else {
+        ctx->cfg.lr = (float)o.lr;
+        HIPCHK(launch_step_set_ext(-1, ctx->d_step, ctx->d_lr_t, nullptr, sched_args(ctx), s));      // (a constant schedule: keras_lr_t's bits)
+    }
+    return KNERF_OK;
+}
+
+int knerf_get_optimizer(knerf_ctx* ctx, knerf_optimizer* opt) {
+    if (!ctx || !opt) return KNERF_ERR_INVALID;
+    *opt = ctx->opt;
+    return KNERF_OK;
+}
+
+int knerf_get_adam_state(knerf_ctx* ctx, void* stream, int net, float* m_host, float* v_host, size_t n) {
+    if (int r = check_net(ctx, net)) return r;
+    if (!m_host || !v_host || n != (size_t)ctx->n_params) return fail(ctx, KNERF_ERR_INVALID, "adam state: expected two arrays of " + std::to_string(ctx->n_params) + " floats");
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    HIPCHK(hipMemcpy(m_host, ctx->net[net].m, n * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(v_host, ctx->net[net].v, n * sizeof(float), hipMemcpyDeviceToHost));
+    return KNERF_OK;
+}
+
+int knerf_set_adam_state(knerf_ctx* ctx, void* stream, int net, const float* m_host, const float* v_host, size_t n) {
+    if (int r = check_net(ctx, net)) return r;
+    if (!m_host || !v_host || n != (size_t)ctx->n_params) return fail(ctx, KNERF_ERR_INVALID, "adam state: expected two arrays of " + std::to_string(ctx->n_params) + " floats");
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    HIPCHK(hipMemcpy(ctx->net[net].m, m_host, n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(ctx->net[net].v, v_host, n * sizeof(float), hipMemcpyHostToDevice));
+    return KNERF_OK;
+}
+
+// knerf_apply_adam while an optimizer extension is active (knerf_set_optimizer; optim_ext.h): the same sequence with the extended
+// element-wise and step kernels; the norm kinds of clipping replace the finite check by the sum-of-squares pass that contains it and add
+// one launch (the ordered pass that turns the partial sums into factors).
+static int apply_adam_ext(knerf_ctx* ctx, hipStream_t s) {
+    const knerf_optimizer& o = ctx->opt;
+    const bool norms = o.clip == KNERF_CLIP_NORM || o.clip == KNERF_CLIP_GLOBAL_NORM;
+    const int T = ctx->opt_tensors, I = ctx->opt_items;
+    const int *tensor_off = ctx->d_opt_tab, *tensor_item0 = tensor_off + T + 1, *item_begin = tensor_item0 + T + 1, *item_end = item_begin + I;
+    float* decay = o.weight_decay > 0 ? ctx->d_opt_f : nullptr;
+    HIPCHK(hipMemsetAsync(ctx->d_flag, 0, sizeof(int), s));
+    if (norms) {
+        HIPCHK(launch_sumsq_partial(ctx->grads, ctx->n_params, item_begin, item_end, I, ctx->d_opt_partial, ctx->d_flag, s));
+        HIPCHK(launch_clip_scale(ctx->d_opt_partial, I, tensor_item0, T, o.clip, o.clip_arg, ctx->d_opt_f + 1, s));
+    } else {
+        HIPCHK(launch_check_finite(ctx->grads, 2 * ctx->n_params, ctx->d_flag, s));
+    }
+    ctx->step += 1;
+    ProfScope ps(ctx, s, P_ADAM);
+    for (int n = 0; n < 2; ++n) {
+        AdamExtArgs x{};
+        AdamArgs& a = x.a;
+        a.w = ctx->net[n].w; a.m = ctx->net[n].m; a.v = ctx->net[n].v; a.g = ctx->net[n].g; a.n = ctx->n_params;
+        a.lr_t = ctx->d_lr_t; a.b1 = ctx->cfg.beta1; a.b2 = ctx->cfg.beta2; a.eps = ctx->cfg.epsilon; a.nonfinite = ctx->d_flag;
+        x.clip = o.clip; x.clip_value = (float)o.clip_arg; x.scale = ctx->d_opt_f + 1 + n * kOptMaxTensors; x.tensor_off = tensor_off; x.n_tensors = T;
+        x.decay = decay;
+        HIPCHK(launch_adam_ext(x, s));
+    }
+    if (!ctx->generic) HIPCHK(launch_head_compose(ctx->net[0].w, ctx->net[1].w, ctx->si.trunk_params, ctx->si.units, ctx->si.trunk_x, ctx->si.trunk_x_slots, ctx->si.dir_dim, ctx->si.dir_slots, s));
+    for (int n = 0; n < 2; ++n)
+        if (int r = repack(ctx, n, s, false)) return r;
+    HIPCHK(launch_step_status_ext(ctx->d_flag, ctx->h_status, ctx->d_step, ctx->d_lr_t, decay, sched_args(ctx), s));
+    return KNERF_OK;
+}
+
 int knerf_apply_adam(knerf_ctx* ctx, void* stream) {
     if (!ctx) return KNERF_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
+    if (ctx->opt_ext) return apply_adam_ext(ctx, s);
     // Finite check first, on the device; the Adam kernels read its flag and leave weights and slots untouched when it is
     // set (the reference aborts fit at nerf.py:381-382).  Nothing here waits for the GPU: the outcome reaches the host through
     // a pinned status word (knerf_poll_nonfinite).
@@ -1321,7 +1480,8 @@ int knerf_set_step_count(knerf_ctx* ctx, int step) {
     if (!ctx || step < 0) return KNERF_ERR_INVALID;
     HIPCHK(hipDeviceSynchronize());        // steps still in flight count from the old value
     ctx->step = step;
-    HIPCHK(launch_step_set(step, ctx->d_step, ctx->d_lr_t, AdamHyper{ctx->cfg.lr, ctx->cfg.beta1, ctx->cfg.beta2}, nullptr));
+    if (ctx->opt_ext) HIPCHK(launch_step_set_ext(step, ctx->d_step, ctx->d_lr_t, ctx->opt.weight_decay > 0 ? ctx->d_opt_f : nullptr, sched_args(ctx), nullptr));
+    else HIPCHK(launch_step_set(step, ctx->d_step, ctx->d_lr_t, AdamHyper{ctx->cfg.lr, ctx->cfg.beta1, ctx->cfg.beta2}, nullptr));
     HIPCHK(hipDeviceSynchronize());
     return KNERF_OK;
 }

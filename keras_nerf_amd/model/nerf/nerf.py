@@ -16,7 +16,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from ... import parallel
+from ... import optimizers, parallel
 from ...runtime import COARSE, FINE, OCCUPANCY_OUTSIDE, KnerfContext, NonFiniteGradientError, marching_cubes, occupancy_from_grid, occupancy_spec  # noqa: F401
 from .metrics import RAY_NAMES, Mean, MetricLogs, MetricState
 from .mlp import NeRFMLP
@@ -81,6 +81,58 @@ def _adam_hyper(optimizer) -> Dict[str, float]:
     return h
 
 
+_CLIP_OPTIONS = ("clipnorm", "clipvalue", "global_clipnorm")
+
+
+def _optimizer_spec(optimizer) -> optimizers.OptimizerSpec:
+    """What `compile(optimizer=...)` accepts: 'adam' / None, keras_nerf_amd.optimizers.Adam, any object with the Keras attribute names or
+    a `get_config()` (a real tf.keras Adam), and the serialised form {"class_name", "config"} (schedules nested the same way).  Beyond
+    plain Adam (`_adam_hyper`, which still supplies the four numbers): a learning rate that is an ExponentialDecay, CosineDecay or
+    PiecewiseConstantDecay, ONE of clipnorm / clipvalue / global_clipnorm, and weight_decay (decoupled, the AdamW form of Keras' Adam).
+    amsgrad, use_ema, gradient accumulation, other schedules, plain callables and other optimizers raise ValueError naming the option."""
+    if optimizer is None or isinstance(optimizer, str):
+        return optimizers.OptimizerSpec(**_adam_hyper(optimizer))
+    if isinstance(optimizer, optimizers.OptimizerSpec):
+        return optimizer
+    cfg = {}
+    if isinstance(optimizer, dict):
+        cfg = dict(optimizer.get("config", optimizer))
+        name = str(optimizer.get("class_name", cfg.get("name", "adam")))
+    else:
+        name = type(optimizer).__name__
+        if callable(getattr(optimizer, "get_config", None)):
+            try:
+                cfg = dict(optimizer.get_config())
+            except Exception:
+                cfg = {}
+        for k in ("learning_rate", "lr", "beta_1", "beta_2", "epsilon", "amsgrad", "weight_decay", "use_ema", "gradient_accumulation_steps") + _CLIP_OPTIONS:
+            if k not in cfg and getattr(optimizer, k, None) is not None:
+                cfg[k] = getattr(optimizer, k)
+        name = str(cfg.get("name", name))
+    for k in ("amsgrad", "use_ema"):
+        if cfg.get(k) not in (None, False, 0, 0.0):
+            raise ValueError(f"Adam option {k}={cfg[k]!r} is not implemented by the optimizer kernels")
+    if cfg.get("gradient_accumulation_steps") not in (None, 0, 1):
+        raise ValueError(f"Adam option gradient_accumulation_steps={cfg['gradient_accumulation_steps']!r} is not implemented")
+    clips = [(k, cfg[k]) for k in _CLIP_OPTIONS if cfg.get(k) is not None]
+    if len(clips) > 1:
+        raise ValueError(f"Adam: only one of clipnorm, clipvalue and global_clipnorm may be set, got {' and '.join(k for k, _ in clips)}")
+    lr_key = "learning_rate" if cfg.get("learning_rate") is not None else "lr"
+    lr = cfg.get(lr_key)
+    schedule = None
+    if lr is not None and not hasattr(lr, "__float__") and not isinstance(lr, (int, float, np.integer, np.floating)):
+        schedule = optimizers.schedule_from(lr, lr_key)                  # ValueError for unknown classes and plain callables
+    # the plain part through _adam_hyper: its name check, its number parsing, its defaults
+    plain = {k: cfg[k] for k in ("beta_1", "beta_2", "epsilon") if cfg.get(k) is not None}
+    if schedule is None and lr is not None:
+        plain["learning_rate"] = lr
+    h = _adam_hyper({"class_name": name, "config": plain})
+    wd = cfg.get("weight_decay")
+    return optimizers.OptimizerSpec(lr=h["lr"], beta1=h["beta1"], beta2=h["beta2"], epsilon=h["epsilon"], schedule=schedule,
+                                    clip=clips[0][0] if clips else None, clip_arg=clips[0][1] if clips else 0.0,
+                                    weight_decay=0.0 if wd in (None, False) else wd)
+
+
 class History(dict):
     """what tf.keras.Model.fit returns: `.history` = {log key: [one value per epoch]}, `.epoch` = the epochs run, `.params`.  Also a
     dict itself (rounds 1-4 returned the plain dictionary), so both `h["fine_loss"]` and `h.history["fine_loss"]` read the curves."""
@@ -117,8 +169,13 @@ class NeRF:
         self.stop_training = False
 
     # ------------------------------------------------------------------ save / load (nerf.py:45-76)
-    def save_model(self, path, weights_only=False):
+    def save_model(self, path, weights_only=False, optimizer_state=False):
+        """nerf.py:45-64.  optimizer_state=True (extension; needs a compiled model) additionally writes optimizer_state.npz: the count
+        of applied steps, Adam's m and v of both nets at their real widths and the optimizer configuration -- with the two weight files
+        the whole state of a run (load_optimizer_state).  The default writes exactly the reference's files."""
         logging.info("Saving NeRF model")
+        if optimizer_state and self._ctx is None:
+            raise RuntimeError("save_model(optimizer_state=True): the model is not compiled, there is no optimizer state")
         if self._ctx is not None:
             self._ctx.poll_nonfinite(wait=True)      # never checkpoint past an unreported skipped step
         os.makedirs(path, exist_ok=True)
@@ -130,6 +187,45 @@ class NeRF:
         # same file names AND container as the reference: Keras-layout HDF5 (keras_nerf_amd/io/hdf5_min.py)
         self.coarse.save_weights(os.path.join(path, "coarse.h5"))
         self.fine.save_weights(os.path.join(path, "fine.h5"))
+        if optimizer_state:
+            (cm, cv), (fm, fv) = self._ctx.get_adam_state(COARSE), self._ctx.get_adam_state(FINE)
+            optimizers.save_optimizer_state(path, self._ctx.step, dict(coarse_m=cm, coarse_v=cv, fine_m=fm, fine_v=fv),
+                                            self._opt_spec.get_config())
+
+    def load_optimizer_state(self, path):
+        """After compile: Adam's slots and the step count from <path>/optimizer_state.npz (save_model(optimizer_state=True)), so that
+        the next train_step continues the saved run bit for bit.  The optimizer itself is the one given to compile (the saved
+        configuration is returned for the caller to compare); raises ValueError if the parameter counts differ."""
+        if self._ctx is None:
+            raise RuntimeError("load_optimizer_state: call compile(...) first")
+        step, slots, config = optimizers.load_optimizer_state(path)
+        n = self._ctx.param_count
+        if slots["coarse_m"].size != n:
+            raise ValueError(f"load_optimizer_state: the file holds {slots['coarse_m'].size} parameters per net, the model has {n}")
+        self._ctx.poll_nonfinite(wait=True)
+        self._ctx.set_adam_state(COARSE, slots["coarse_m"], slots["coarse_v"])
+        self._ctx.set_adam_state(FINE, slots["fine_m"], slots["fine_v"])
+        self._ctx.step = step
+        return config
+
+    @property
+    def learning_rate(self) -> float:
+        """the rate of the NEXT optimizer step: the schedule (in Python floats) at the host's count of applied steps"""
+        if self._ctx is None:
+            raise RuntimeError("the model is not compiled: call compile(...) first")
+        return self._opt_spec.lr_at(self._ctx.step)
+
+    def set_learning_rate(self, lr):
+        """a new constant rate from the next step on (stream-ordered, nothing waits); constant schedules only"""
+        if self._ctx is None:
+            raise RuntimeError("the model is not compiled: call compile(...) first")
+        sp = self._opt_spec
+        if sp.schedule is not None:
+            raise ValueError(f"set_learning_rate: the learning rate follows a {type(sp.schedule).__name__} schedule")
+        new = optimizers.OptimizerSpec(lr=lr, beta1=sp.beta1, beta2=sp.beta2, epsilon=sp.epsilon, clip=sp.clip, clip_arg=sp.clip_arg,
+                                       weight_decay=sp.weight_decay)
+        self._ctx.set_optimizer(new)
+        self._opt_spec = new
 
     def load_model(self, path):
         with open(os.path.join(path, "model_config.json"), "r") as f:
@@ -163,7 +259,8 @@ class NeRF:
         if all_reduce not in ("sum", "mean"):
             raise ValueError("all_reduce must be 'sum' (Keras/MirroredStrategy semantics) or 'mean'")
         self.all_reduce = all_reduce
-        h = _adam_hyper(optimizer)
+        spec = _optimizer_spec(optimizer)
+        h = dict(lr=spec.lr, beta1=spec.beta1, beta2=spec.beta2, epsilon=spec.epsilon)
         if self._ctx is not None:
             self.coarse._host, self.fine._host = self.coarse.get_flat_weights(), self.fine.get_flat_weights()
             self.coarse._ctx = self.fine._ctx = None
@@ -178,6 +275,9 @@ class NeRF:
         self._ctx = KnerfContext(self.n_coarse, self.n_fine, self.pos_emb_xyz, self.pos_emb_dir, self.n_layers, self.dense_units,
                                  self.skip_layer, white_background, self.oob, h["lr"], h["beta1"], h["beta2"], h["epsilon"],
                                  options=opts)
+        self._opt_spec = spec
+        if not spec.is_plain:                            # schedules, clipping, weight decay: csrc/optim_ext.hip (plain Adam never goes there)
+            self._ctx.set_optimizer(spec)
         self.device = self._ctx.device
         self.nerf_utils = NeRFUtils(batch_size, image_height, image_width, self.ray_chunks, self.pos_emb_xyz, self.pos_emb_dir,
                                     white_background, self.oob)

@@ -544,6 +544,50 @@ class KnerfContext:
     def step(self, v: int):
         self._check(self.lib.knerf_set_step_count(self._ctx, int(v)))
 
+    # ---- optimizer options and state (include/knerf.h knerf_set_optimizer / knerf_get_adam_state)
+    def set_optimizer(self, opt=None, **kw):
+        """knerf_set_optimizer: opt = a _lib.KnerfOptimizer, an optimizers.OptimizerSpec (anything with to_struct()), or the
+        OptimizerSpec arguments as keywords (lr, schedule, clip, clip_arg, weight_decay).  Stream-ordered, callable between steps: the
+        rate of the next step is re-derived on the device from the device-side step count.  beta1 / beta2 / epsilon stay the context's."""
+        if opt is None:
+            from .optimizers import OptimizerSpec
+            opt = OptimizerSpec(**kw)
+        elif kw:
+            raise TypeError("set_optimizer: either an object or keywords")
+        if not isinstance(opt, _lib.KnerfOptimizer):
+            opt = opt.to_struct()
+        self._check(self.lib.knerf_set_optimizer(self._ctx, self._stream(), C.byref(opt)))
+
+    def get_optimizer(self) -> "_lib.KnerfOptimizer":
+        """the record knerf_set_optimizer stored (canonical: what the chosen kinds do not read is zero)"""
+        o = _lib.KnerfOptimizer()
+        self._check(self.lib.knerf_get_optimizer(self._ctx, C.byref(o)))
+        return o
+
+    def get_adam_state(self, net: int):
+        """(m, v) of one net: Adam's slots in the REAL flat layout (as get_weights)"""
+        n = self.param_count if self._pad_index is None else self.padded_param_count
+        m, v = np.empty(n, np.float32), np.empty(n, np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.knerf_get_adam_state(self._ctx, self._stream(), int(net), m.ctypes.data_as(fp), v.ctypes.data_as(fp), n))
+        return (m, v) if self._pad_index is None else (m[self._pad_index_host], v[self._pad_index_host])
+
+    def set_adam_state(self, net: int, m, v):
+        """the inverse of get_adam_state (width padding: the padded entries' slots are zero, as they always are)"""
+        slots = []
+        for name, x in (("m", m), ("v", v)):
+            x = np.ascontiguousarray(np.asarray(x, dtype=np.float32).reshape(-1))
+            if x.size != self.param_count:
+                raise ValueError(f"set_adam_state: {x.size} values of {name} for a network of {self.param_count} parameters")
+            if self._pad_index is not None:
+                wide = np.zeros(self.padded_param_count, np.float32)
+                wide[self._pad_index_host] = x
+                x = wide
+            slots.append(x)
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.knerf_set_adam_state(self._ctx, self._stream(), int(net), slots[0].ctypes.data_as(fp), slots[1].ctypes.data_as(fp),
+                                                  slots[0].size))
+
     def generate_rays(self, c2w, focal, height, width, near, far, n_samples, noise=None, seed=0, stream_id=0):
         c2w = self.f32(c2w).reshape(-1, 4, 4)
         B = c2w.shape[0]
