@@ -41,6 +41,21 @@ int knerf_debug_read_probe(const void* in, int workgroups, long long bytes_per_w
 /* MFMA-shape rate probe (shape 32: v_mfma_f32_32x32x16_bf16, 16: v_mfma_f32_16x16x32_bf16) with the chain kernels' operand
  * traffic; `blocks` workgroups of 512 threads, 96 * 2^15 * 16 FLOP per wave and iteration. */
 int knerf_debug_rate_probe(int shape, const void* in0, const void* in1, void* out, int blocks, int iters, void* stream);
+/* The compositing kernel's training half on caller-made inputs, without a context (csrc/composite.hip; CompositeArgs of
+ * csrc/kernels.h): raw [R,S,4], t [R,S], target [R,3] -> image [R,3], depth [R], weights [R,S], draw [R,S,4] and *loss +=
+ * loss_scale * sum of squared differences.  loss_partial [ceil(R/4)] or null: the deterministic mode's per-workgroup terms, added in a
+ * fixed order by the loss-reduction kernel behind the compositing kernel (as knerf_train_chunk does) instead of one atomic per
+ * workgroup.  tile_flags [R*S/32] or null; tile_list [R*S/32] with tile_count (one int, the caller sets it to zero) or both null;
+ * tile_list2 [*tile_count2 + R*S/32] with tile_count2 and tile_off2, only together with tile_list, or both null.  Tile outputs need
+ * S % 32 == 0.  All pointers are device pointers; 1 <= S <= 1024. */
+int knerf_debug_composite_train(void* stream, const float* raw, const float* t, const float* target, int n_rays, int n_samples,
+                                int white_background, float grad_scale, float loss_scale, float* image, float* depth, float* weights,
+                                float* draw, float* loss, float* loss_partial, int* tile_flags, int* tile_list, int* tile_count,
+                                int* tile_list2, int* tile_count2, int tile_off2);
+/* The deterministic mode's tile compaction (one workgroup): list = the ascending indices i in [0, n) with flags[i] != 0 and
+ * (i % period) < real, *count = their number, stats[0] += *count, stats[1] += the number of i with (i % period) < real; stats may
+ * be null.  list holds up to n entries.  All pointers are device pointers. */
+int knerf_debug_compact_tiles(const int* flags, int n, int period, int real, int* list, int* count, long long* stats, void* stream);
 
 #ifdef __cplusplus
 }

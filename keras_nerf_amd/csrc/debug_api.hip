@@ -4,6 +4,7 @@
 
 #include "../../include/knerf_debug.h"
 #include "ctx.h"
+#include "kernels.h"
 
 using namespace knerf;
 
@@ -77,6 +78,33 @@ int knerf_debug_buffer(knerf_ctx* ctx, int net, int which, void** dev, size_t* b
     }
     // not allocated: no pass has run yet, or the buffer belongs to the fused path and this context runs the general-shape kernels
     return *dev ? KNERF_OK : KNERF_ERR_INVALID;
+}
+
+int knerf_debug_composite_train(void* stream, const float* raw, const float* t, const float* target, int n_rays, int n_samples,
+                                int white_background, float grad_scale, float loss_scale, float* image, float* depth, float* weights,
+                                float* draw, float* loss, float* loss_partial, int* tile_flags, int* tile_list, int* tile_count,
+                                int* tile_list2, int* tile_count2, int tile_off2) {
+    if (!raw || !t || !target || !image || !depth || !weights || !draw || !loss || n_rays <= 0 || n_samples <= 0 || n_samples > 1024)
+        return KNERF_ERR_INVALID;
+    if ((tile_flags || tile_list) && n_samples % 32 != 0) return KNERF_ERR_INVALID;          // tiles must not straddle rays
+    if (!tile_list != !tile_count || !tile_list2 != !tile_count2 || (tile_list2 && !tile_list)) return KNERF_ERR_INVALID;
+    CompositeArgs ca{};
+    ca.raw = raw; ca.t = t; ca.target = target; ca.image = image; ca.depth = depth; ca.weights = weights;
+    ca.draw = draw; ca.loss = loss; ca.R = n_rays; ca.S = n_samples; ca.white = white_background;
+    ca.grad_scale = grad_scale; ca.loss_scale = loss_scale;
+    ca.tile_flags = tile_flags; ca.tile_list = tile_list; ca.tile_count = tile_count;
+    ca.tile_list2 = tile_list2; ca.tile_count2 = tile_count2; ca.tile_off2 = tile_off2;
+    ca.loss_partial = loss_partial;
+    hipStream_t s = (hipStream_t)stream;
+    if (launch_composite(ca, s) != hipSuccess) return KNERF_ERR_HIP;
+    // deterministic mode, as knerf_train_chunk: the workgroups' loss terms added in a fixed order
+    if (ca.loss_partial && launch_loss_reduce(ca.loss_partial, (n_rays + 3) / 4, loss, s) != hipSuccess) return KNERF_ERR_HIP;
+    return KNERF_OK;
+}
+
+int knerf_debug_compact_tiles(const int* flags, int n, int period, int real, int* list, int* count, long long* stats, void* stream) {
+    if (!flags || !list || !count || n <= 0 || period <= 0 || real < 0 || real > period) return KNERF_ERR_INVALID;
+    return launch_compact_tiles(flags, n, period, real, list, count, stats, (hipStream_t)stream) == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
 }
 
 }  // extern "C"
