@@ -241,6 +241,37 @@ int knerf_get_optimizer(knerf_ctx* ctx, knerf_optimizer* opt);
 int knerf_get_adam_state(knerf_ctx* ctx, void* stream, int net, float* m_host, float* v_host, size_t n);
 int knerf_set_adam_state(knerf_ctx* ctx, void* stream, int net, const float* m_host, const float* v_host, size_t n);
 
+/* ---- The objective of the train step: what tf.keras takes as `loss` in NeRF.compile beyond mean squared error, and two
+ * regularisers of a ray's weights.  Opt-in: a context that never calls knerf_set_objective, or calls it with KNERF_LOSS_MSE and both
+ * weights 0, runs the compositing kernel exactly as before (the same launches, the same bits).  Per ray, d_k = clip(pre_k, 0, 1) -
+ * target_k, w_i the weights, acc = sum w_i, delta_i = t_{i+1} - t_i (last: 1e-10), m_i = t_i + delta_i / 2:
+ *   photometric term: the mean over rays and channels of rho(d)
+ *       KNERF_LOSS_MSE d^2 | KNERF_LOSS_MAE |d| (sign(0) = 0) | KNERF_LOSS_HUBER d^2 / 2 where |d| <= huber_delta, else
+ *       huber_delta (|d| - huber_delta / 2) | KNERF_LOSS_LOG_COSH |d| + log1p(exp(-2 |d|)) - ln 2          (the Keras classes)
+ *     its gradient passes the clip gate of the colour (pre in [0, 1], inclusive) as the squared error's does
+ *   distortion (mip-NeRF 360): D = sum_i sum_j w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 delta_i, evaluated in O(n) with prefix sums,
+ *     which equals the definition for non-decreasing t (the contract; for unsorted t the prefix form's value is returned)
+ *   opacity entropy: a = clamp(acc, 1e-4, 1 - 1e-4), H = -a ln a - (1 - a) ln(1 - a); gradient ln((1 - a) / a) inside the clamp, else 0
+ * Loss of a net = photometric + distortion * mean D + opacity_entropy * mean H (means over rays); the regularisers' gradient enters
+ * dL/dw directly (the weights are not clipped) and applies to the nets of `nets`.  t carries no gradient. */
+enum { KNERF_LOSS_MSE = 0, KNERF_LOSS_MAE = 1, KNERF_LOSS_HUBER = 2, KNERF_LOSS_LOG_COSH = 3 };
+typedef struct knerf_objective {
+    int32_t loss_kind;           /* KNERF_LOSS_* */
+    float huber_delta;           /* KNERF_LOSS_HUBER: > 0 */
+    float distortion;            /* weight of the distortion term, >= 0; 0: off */
+    float opacity_entropy;       /* weight of the opacity-entropy term, >= 0; 0: off */
+    int32_t nets;                /* the regularisers apply to: 1 the coarse net, 2 the fine net, 3 both */
+} knerf_objective;
+/* Callable at any time between steps; stream-ordered.  Stored canonically (huber_delta 0 unless the kind is huber; nets 3 when both
+ * weights are 0).  KNERF_ERR_INVALID (with a message) on: a null record, an unknown kind, huber_delta <= 0 or non-finite under
+ * KNERF_LOSS_HUBER, a negative or non-finite weight, nets outside 1..3, a KNERF_FLAG_ENCODED_WIDTHS context. */
+int knerf_set_objective(knerf_ctx* ctx, void* stream, const knerf_objective* obj);
+int knerf_get_objective(knerf_ctx* ctx, knerf_objective* obj);
+/* out: DEVICE [2][4] floats, [coarse | fine] x [photometric, mean squared error, mean D, mean H] accumulated by the passes since the
+ * start of the last knerf_train_batch (which zeroes them; knerf_train_chunk adds its inv_chunks share).  All zero while the
+ * objective is the plain one: the plain kernel does not compute them.  Stream-ordered copy, nothing waits. */
+int knerf_objective_terms(knerf_ctx* ctx, void* stream, float* out);
+
 /* RaysGenerator.__call__ (keras_nerf/data/rays.py:69-130) on device: c2w [B,4,4], noise [B,H,W,N] in [0,1) or
  * NULL for Philox; writes o,d [B,H,W,3] and t [B,H,W,N].  ctx may be NULL (stand-alone op). */
 int knerf_generate_rays(knerf_ctx* ctx, void* stream, const float* c2w, const float* noise, uint64_t seed,

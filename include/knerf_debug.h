@@ -52,6 +52,15 @@ int knerf_debug_composite_train(void* stream, const float* raw, const float* t, 
                                 int white_background, float grad_scale, float loss_scale, float* image, float* depth, float* weights,
                                 float* draw, float* loss, float* loss_partial, int* tile_flags, int* tile_list, int* tile_count,
                                 int* tile_list2, int* tile_count2, int tile_off2);
+/* The same on the EXTENDED compositing kernel (csrc/composite_ext.hip; include/knerf.h knerf_set_objective), always -- also for
+ * KNERF_LOSS_MSE without a regulariser, where the product takes the plain kernel.  obj: the record (`nets` is not read: the weights
+ * apply to this pass); reg_scale: inv_chunks / R of knerf_train_chunk; terms [4] (photometric, squared error, distortion, entropy;
+ * added to); terms_partial [4][ceil(R/4)], given exactly when loss_partial is: the deterministic mode's per-workgroup terms. */
+int knerf_debug_composite_objective(void* stream, const float* raw, const float* t, const float* target, int n_rays, int n_samples,
+                                    int white_background, float grad_scale, float loss_scale, float* image, float* depth, float* weights,
+                                    float* draw, float* loss, float* loss_partial, int* tile_flags, int* tile_list, int* tile_count,
+                                    int* tile_list2, int* tile_count2, int tile_off2, const knerf_objective* obj, float reg_scale,
+                                    float* terms, float* terms_partial);
 /* The deterministic mode's tile compaction (one workgroup): list = the ascending indices i in [0, n) with flags[i] != 0 and
  * (i % period) < real, *count = their number, stats[0] += *count, stats[1] += the number of i with (i % period) < real; stats may
  * be null.  list holds up to n entries.  All pointers are device pointers. */

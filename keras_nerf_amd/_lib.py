@@ -27,6 +27,13 @@ class KnerfOptimizer(C.Structure):
                 ("boundaries", C.c_int64 * 15), ("values", C.c_double * 16)]
 
 
+class KnerfObjective(C.Structure):
+    """struct knerf_objective (include/knerf.h): loss kind, Huber's delta, the two regularisers' weights and the nets they apply to"""
+    _fields_ = [("loss_kind", C.c_int32), ("huber_delta", C.c_float), ("distortion", C.c_float), ("opacity_entropy", C.c_float),
+                ("nets", C.c_int32)]
+
+
+LOSS_MSE, LOSS_MAE, LOSS_HUBER, LOSS_LOG_COSH = 0, 1, 2, 3
 SCHEDULE_CONSTANT, SCHEDULE_EXPONENTIAL, SCHEDULE_COSINE, SCHEDULE_PIECEWISE = 0, 1, 2, 3
 CLIP_NONE, CLIP_VALUE, CLIP_NORM, CLIP_GLOBAL_NORM = 0, 1, 2, 4
 SCHEDULE_MAX_VALUES = 16
@@ -71,6 +78,9 @@ SIGNATURES = {
     "knerf_set_step_count": (C.c_int, [_P, C.c_int]),
     "knerf_set_optimizer": (C.c_int, [_P, _P, C.POINTER(KnerfOptimizer)]),
     "knerf_get_optimizer": (C.c_int, [_P, C.POINTER(KnerfOptimizer)]),
+    "knerf_set_objective": (C.c_int, [_P, _P, C.POINTER(KnerfObjective)]),
+    "knerf_get_objective": (C.c_int, [_P, C.POINTER(KnerfObjective)]),
+    "knerf_objective_terms": (C.c_int, [_P, _P, _F]),
     "knerf_get_adam_state": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]),
     "knerf_set_adam_state": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_size_t]),
     "knerf_generate_rays": (C.c_int, [_P, _P, _F, _F, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -82,6 +82,12 @@ struct knerf_ctx {
     double* d_opt_partial = nullptr;
     int* d_opt_tab = nullptr;
     int opt_tensors = 0, opt_items = 0;
+    // the objective (knerf_set_objective; composite_ext.h).  obj_ext: the loss is not the squared error or a regulariser is on, and the
+    // training passes' compositing goes to composite_ext.hip; false (the default, and mse with both weights 0): the plain kernel.
+    // d_terms: device [2][4], the terms of the passes since the last knerf_train_batch began
+    knerf_objective obj = {0, 0.f, 0.f, 0.f, 3};
+    bool obj_ext = false;
+    float* d_terms = nullptr;
     int n_cu = 256;
     // general-shape MLP path (generic.h): used when the fused kernels do not cover the config's MLP shape (layout.h KNERF_FUSED_SHAPES)
     bool generic = false;

@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "../../include/knerf_debug.h"
+#include "composite_ext.h"
 #include "ctx.h"
 #include "kernels.h"
 
@@ -99,6 +100,36 @@ int knerf_debug_composite_train(void* stream, const float* raw, const float* t, 
     if (launch_composite(ca, s) != hipSuccess) return KNERF_ERR_HIP;
     // deterministic mode, as knerf_train_chunk: the workgroups' loss terms added in a fixed order
     if (ca.loss_partial && launch_loss_reduce(ca.loss_partial, (n_rays + 3) / 4, loss, s) != hipSuccess) return KNERF_ERR_HIP;
+    return KNERF_OK;
+}
+
+int knerf_debug_composite_objective(void* stream, const float* raw, const float* t, const float* target, int n_rays, int n_samples,
+                                    int white_background, float grad_scale, float loss_scale, float* image, float* depth, float* weights,
+                                    float* draw, float* loss, float* loss_partial, int* tile_flags, int* tile_list, int* tile_count,
+                                    int* tile_list2, int* tile_count2, int tile_off2, const knerf_objective* obj, float reg_scale,
+                                    float* terms, float* terms_partial) {
+    if (!raw || !t || !target || !image || !depth || !weights || !draw || !loss || n_rays <= 0 || n_samples <= 0 || n_samples > 1024)
+        return KNERF_ERR_INVALID;
+    if ((tile_flags || tile_list) && n_samples % 32 != 0) return KNERF_ERR_INVALID;
+    if (!tile_list != !tile_count || !tile_list2 != !tile_count2 || (tile_list2 && !tile_list)) return KNERF_ERR_INVALID;
+    if (!obj || !terms || !loss_partial != !terms_partial) return KNERF_ERR_INVALID;
+    if (obj->loss_kind < KNERF_LOSS_MSE || obj->loss_kind > KNERF_LOSS_LOG_COSH || (obj->loss_kind == KNERF_LOSS_HUBER && !(obj->huber_delta > 0)))
+        return KNERF_ERR_INVALID;
+    CompositeArgs ca{};
+    ca.raw = raw; ca.t = t; ca.target = target; ca.image = image; ca.depth = depth; ca.weights = weights;
+    ca.draw = draw; ca.loss = loss; ca.R = n_rays; ca.S = n_samples; ca.white = white_background;
+    ca.grad_scale = grad_scale; ca.loss_scale = loss_scale;
+    ca.tile_flags = tile_flags; ca.tile_list = tile_list; ca.tile_count = tile_count;
+    ca.tile_list2 = tile_list2; ca.tile_count2 = tile_count2; ca.tile_off2 = tile_off2;
+    ca.loss_partial = loss_partial;
+    // always the extended kernel, also for mse without a regulariser (the product takes the plain kernel there)
+    CompositeExt ce{};
+    ce.loss_kind = obj->loss_kind; ce.huber_delta = obj->huber_delta; ce.lambda_d = obj->distortion; ce.lambda_e = obj->opacity_entropy;
+    ce.reg_scale = reg_scale; ce.terms = terms; ce.terms_partial = terms_partial;
+    hipStream_t s = (hipStream_t)stream;
+    if (launch_composite(ca, &ce, s) != hipSuccess) return KNERF_ERR_HIP;
+    if (ca.loss_partial && launch_loss_reduce(ca.loss_partial, (n_rays + 3) / 4, loss, s) != hipSuccess) return KNERF_ERR_HIP;
+    if (ce.terms_partial && launch_terms_reduce(ce.terms_partial, (n_rays + 3) / 4, terms, s) != hipSuccess) return KNERF_ERR_HIP;
     return KNERF_OK;
 }
 

@@ -12,6 +12,7 @@
 
 #include "../../include/knerf.h"
 #include "chain.h"
+#include "composite_ext.h"
 #include "ctx.h"
 #include "kernels.h"
 #include "generic.h"
@@ -210,7 +211,7 @@ int ensure_ws_impl(knerf_ctx* ctx, int n_rays, bool train, hipStream_t s, int gr
             HIPCHK(hipMalloc(&ctx->draw, ctx->raw_bytes));
             ctx->draw_bytes = ctx->raw_bytes;
             free_dev(ctx->loss_partial);
-            HIPCHK(hipMalloc(&ctx->loss_partial, ((size_t)R + 3) / 4 * sizeof(float)));
+            HIPCHK(hipMalloc(&ctx->loss_partial, 5 * (((size_t)R + 3) / 4) * sizeof(float)));     // the loss, then the objective's four terms (composite_ext.h)
             // dead-tile skipping: per-tile flags (deterministic mode) and the list of live tiles of the current pass
             free_dev(ctx->tile_flags); free_dev(ctx->tile_list);
             const size_t tiles = tiles_for((long long)ns);
@@ -295,7 +296,7 @@ int ensure_ws_impl(knerf_ctx* ctx, int n_rays, bool train, hipStream_t s, int gr
         HIPCHK(hipMemsetAsync(ctx->tile_flags, 0, tiles * sizeof(int), s));
         HIPCHK(hipMalloc(&ctx->tile_list, tiles * sizeof(int)));
         if (group > 1) HIPCHK(hipMalloc(&ctx->tile_list_g, (size_t)group * tiles_for((long long)R * ctx->cfg.n_coarse) * sizeof(int)));
-        HIPCHK(hipMalloc(&ctx->loss_partial, ((size_t)R + 3) / 4 * sizeof(float)));
+        HIPCHK(hipMalloc(&ctx->loss_partial, 5 * (((size_t)R + 3) / 4) * sizeof(float)));     // the loss, then the objective's four terms (composite_ext.h)
         ctx->ws_tiles = tiles;
         ctx->ws_train = true; ctx->ws_train_rays = R; ctx->ws_group = group;
     }
@@ -507,10 +508,22 @@ int run_pass(knerf_ctx* ctx, hipStream_t s, int net, const float* o, const float
         if (group_count) { ca.tile_list2 = ctx->tile_list_g; ca.tile_count2 = group_count; ca.tile_off2 = (int)tile0; }
     }
     if (train && ctx->deterministic) ca.loss_partial = ctx->loss_partial;
+    // an extended objective (knerf_set_objective): the launch goes to composite_ext.hip; the plain objective never does
+    CompositeExt ce{};
+    const bool ext = train && ctx->obj_ext;
+    if (ext) {
+        const bool regs = (ctx->obj.nets >> (net == KNERF_COARSE ? 0 : 1)) & 1;
+        ce.loss_kind = ctx->obj.loss_kind; ce.huber_delta = ctx->obj.huber_delta;
+        ce.lambda_d = regs ? ctx->obj.distortion : 0.f; ce.lambda_e = regs ? ctx->obj.opacity_entropy : 0.f;
+        ce.reg_scale = inv_chunks / (float)R;
+        ce.terms = ctx->d_terms + 4 * (net == KNERF_COARSE ? 0 : 1);
+        if (ca.loss_partial) ce.terms_partial = ctx->loss_partial + ((size_t)ctx->ws_train_rays + 3) / 4;
+    }
     {
         ProfScope ps(ctx, s, P_COMPOSITE);
-        HIPCHK(launch_composite(ca, s));
+        HIPCHK(launch_composite(ca, ext ? &ce : nullptr, s));
         if (ca.loss_partial) HIPCHK(launch_loss_reduce(ca.loss_partial, (R + 3) / 4, loss, s));
+        if (ce.terms_partial) HIPCHK(launch_terms_reduce(ce.terms_partial, (R + 3) / 4, ce.terms, s));
         // deterministic mode: the pass's live tiles (indices relative to tile0) in ascending order; the padding tiles behind the
         // last real one count as dead
         if (ca.tile_flags) { if (int r = compact_tiles(ctx, s, ca.tile_flags, (int)n_tiles, (int)n_tiles, (int)(fa.n_samples / kTile), ctx->tile_list, &live_count)) return r; }
@@ -810,6 +823,8 @@ int knerf_create(const knerf_config* cfg, knerf_ctx** out) {
     CREATECHK(hipHostMalloc(&ctx->h_status, 2 * sizeof(int), hipHostMallocDefault));   // written by the device (optim.hip step_status)
     ctx->h_status[0] = ctx->h_status[1] = 0;
     CREATECHK(hipMalloc(&ctx->loss_tmp, 2 * sizeof(float)));
+    CREATECHK(hipMalloc(&ctx->d_terms, 8 * sizeof(float)));
+    CREATECHK(hipMemset(ctx->d_terms, 0, 8 * sizeof(float)));
     for (int n = 0; n < 2; ++n) {
         Net& N = ctx->net[n];
         const size_t NW = ctx->generic ? NP : (size_t)ctx->si.ext_param_count;  // fused path: parameters + composed head (layout.h)
@@ -847,7 +862,7 @@ int knerf_destroy(knerf_ctx* ctx) {
         Net& N = ctx->net[n];
         free_dev(N.w); free_dev(N.m); free_dev(N.v); free_dev(N.fwd_stream); free_dev(N.bwd_stream); free_dev(N.bias);
     }
-    free_dev(ctx->grads); free_dev(ctx->aux); free_dev(ctx->d_flag); free_dev(ctx->loss_tmp); free_dev(ctx->d_step); free_dev(ctx->d_lr_t);
+    free_dev(ctx->grads); free_dev(ctx->aux); free_dev(ctx->d_flag); free_dev(ctx->loss_tmp); free_dev(ctx->d_terms); free_dev(ctx->d_step); free_dev(ctx->d_lr_t);
     free_dev(ctx->d_opt_f); free_dev(ctx->d_opt_partial); free_dev(ctx->d_opt_tab);
     if (ctx->h_status) { (void)hipHostFree(ctx->h_status); ctx->h_status = nullptr; }
     if (ctx->h_diag) { (void)hipHostFree(ctx->h_diag); ctx->h_diag = nullptr; }
@@ -1103,6 +1118,7 @@ int knerf_train_batch(knerf_ctx* ctx, void* stream, const float* o, const float*
     const int Nc = ctx->cfg.n_coarse, Nf = ctx->cfg.n_fine;
     if (ctx->plan_dirty) { if (int r = upload_plan(ctx)) return r; }
     ctx->tile_counter_next = 0;
+    if (ctx->obj_ext) HIPCHK(hipMemsetAsync(ctx->d_terms, 0, 8 * sizeof(float), s));      // knerf_objective_terms: of this batch
     // zero-gradient diagnostics count the LAST chunk's gradient (nerf.py:430-451): that chunk's launches must be its own
     int merge = ctx->grad_diag ? 1 : merge_factor(ctx->merge_rays, ray_chunks, n_rays / ray_chunks);
     const int user_chunks = ray_chunks;
@@ -1270,6 +1286,41 @@ int knerf_set_optimizer(knerf_ctx* ctx, void* stream, const knerf_optimizer* opt
 int knerf_get_optimizer(knerf_ctx* ctx, knerf_optimizer* opt) {
     if (!ctx || !opt) return KNERF_ERR_INVALID;
     *opt = ctx->opt;
+    return KNERF_OK;
+}
+
+// ---- the objective (include/knerf.h knerf_set_objective; composite_ext.h) -------------------------------------------------------
+int knerf_set_objective(knerf_ctx* ctx, void* stream, const knerf_objective* obj) {
+    if (!ctx) return KNERF_ERR_INVALID;
+    if (!obj) return fail(ctx, KNERF_ERR_INVALID, "set_objective: null argument");
+    if (ctx->mlp_only) return fail(ctx, KNERF_ERR_INVALID, "set_objective: a KNERF_FLAG_ENCODED_WIDTHS context has no train step");
+    knerf_objective o = *obj;
+    auto ok = [](float v) { return std::isfinite(v) && v >= 0; };
+    if (o.loss_kind < KNERF_LOSS_MSE || o.loss_kind > KNERF_LOSS_LOG_COSH) return fail(ctx, KNERF_ERR_INVALID, "set_objective: unknown loss kind " + std::to_string(o.loss_kind));
+    if (o.loss_kind == KNERF_LOSS_HUBER && !(std::isfinite(o.huber_delta) && o.huber_delta > 0)) return fail(ctx, KNERF_ERR_INVALID, "set_objective: huber_delta must be finite and > 0");
+    if (!ok(o.distortion)) return fail(ctx, KNERF_ERR_INVALID, "set_objective: the distortion weight must be finite and >= 0");
+    if (!ok(o.opacity_entropy)) return fail(ctx, KNERF_ERR_INVALID, "set_objective: the opacity_entropy weight must be finite and >= 0");
+    if (o.nets < 1 || o.nets > 3) return fail(ctx, KNERF_ERR_INVALID, "set_objective: nets must be 1 (coarse), 2 (fine) or 3 (both), got " + std::to_string(o.nets));
+    // what the chosen kind does not read is stored as zero, so that knerf_get_objective returns a canonical record
+    if (o.loss_kind != KNERF_LOSS_HUBER) o.huber_delta = 0;
+    if (o.distortion == 0 && o.opacity_entropy == 0) { o.distortion = 0; o.opacity_entropy = 0; o.nets = 3; }
+    ctx->obj = o;
+    ctx->obj_ext = o.loss_kind != KNERF_LOSS_MSE || o.distortion > 0 || o.opacity_entropy > 0;
+    HIPCHK(hipMemsetAsync(ctx->d_terms, 0, 8 * sizeof(float), (hipStream_t)stream));
+    return KNERF_OK;
+}
+
+int knerf_get_objective(knerf_ctx* ctx, knerf_objective* obj) {
+    if (!ctx || !obj) return KNERF_ERR_INVALID;
+    *obj = ctx->obj;
+    return KNERF_OK;
+}
+
+int knerf_objective_terms(knerf_ctx* ctx, void* stream, float* out) {
+    if (!ctx) return KNERF_ERR_INVALID;
+    if (!out) return fail(ctx, KNERF_ERR_INVALID, "objective_terms: null argument");
+    if (ctx->mlp_only) return fail(ctx, KNERF_ERR_INVALID, "objective_terms: a KNERF_FLAG_ENCODED_WIDTHS context has no train step");
+    HIPCHK(hipMemcpyAsync(out, ctx->d_terms, 8 * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return KNERF_OK;
 }
 

@@ -23,6 +23,8 @@ SIGNATURES = {
     "knerf_debug_rate_probe": (C.c_int, [C.c_int, _P, _P, _P, C.c_int, C.c_int, _P]),
     "knerf_debug_composite_train": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, _P,
                                               _P, _P, _P, _P, _P, _P, C.c_int]),
+    "knerf_debug_composite_objective": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, _P,
+                                                  _P, _P, _P, _P, _P, _P, C.c_int, C.POINTER(_lib.KnerfObjective), C.c_float, _P, _P]),
     "knerf_debug_compact_tiles": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
 }
 _probe = None
@@ -103,6 +105,43 @@ def composite_train(raw, t, target, white, grad_scale, loss_scale, loss0=0.0, pa
         _dev_ptr(out.get("tile_count")), _dev_ptr(out.get("tile_list2")), _dev_ptr(out.get("tile_count2")), int(tile_off2))
     if rc != 0:
         raise _lib.KnerfError(f"knerf_debug_composite_train failed ({rc})")
+    return out
+
+
+def composite_objective(raw, t, target, white, grad_scale, loss_scale, objective, reg_scale, loss0=0.0, partial=False, flags=False,
+                        tiles=False, count2_start=None, tile_off2=0):
+    """composite_train on the EXTENDED compositing kernel (knerf_debug_composite_objective), always -- also for mse without a
+    regulariser.  objective: a _lib.KnerfObjective (its `nets` is not read); reg_scale: inv_chunks / R.  Returns composite_train's dict
+    plus terms [4] (photometric, squared error, distortion, entropy) and, with partial=True, terms_partial [4, ceil(R/4)]."""
+    import torch
+    R, S = t.shape
+    dev = raw.device
+    assert raw.shape == (R, S, 4) and target.shape == (R, 3)
+    assert all(x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() for x in (raw, t, target))
+    n_tiles = R * (S // 32)
+    out = dict(image=torch.empty((R, 3), device=dev), depth=torch.empty((R,), device=dev), weights=torch.empty((R, S), device=dev),
+               draw=torch.empty((R, S, 4), device=dev), loss=torch.full((1,), float(loss0), device=dev), terms=torch.zeros((4,), device=dev))
+    if partial:
+        out["loss_partial"] = torch.zeros(((R + 3) // 4,), device=dev)
+        out["terms_partial"] = torch.zeros((4, (R + 3) // 4), device=dev)
+    if flags:
+        out["tile_flags"] = torch.full((max(n_tiles, 1),), -1, dtype=torch.int32, device=dev)
+    if tiles:
+        out["tile_list"] = torch.full((max(n_tiles, 1),), -1, dtype=torch.int32, device=dev)
+        out["tile_count"] = torch.zeros((1,), dtype=torch.int32, device=dev)
+    if count2_start is not None:
+        assert tiles and count2_start >= 0
+        out["tile_list2"] = torch.full((count2_start + max(n_tiles, 1),), -1, dtype=torch.int32, device=dev)
+        out["tile_count2"] = torch.full((1,), int(count2_start), dtype=torch.int32, device=dev)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    rc = load().knerf_debug_composite_objective(
+        stream, _dev_ptr(raw), _dev_ptr(t), _dev_ptr(target), R, S, int(white), float(grad_scale), float(loss_scale),
+        _dev_ptr(out["image"]), _dev_ptr(out["depth"]), _dev_ptr(out["weights"]), _dev_ptr(out["draw"]), _dev_ptr(out["loss"]),
+        _dev_ptr(out.get("loss_partial")), _dev_ptr(out.get("tile_flags")), _dev_ptr(out.get("tile_list")),
+        _dev_ptr(out.get("tile_count")), _dev_ptr(out.get("tile_list2")), _dev_ptr(out.get("tile_count2")), int(tile_off2),
+        C.byref(objective), float(reg_scale), _dev_ptr(out["terms"]), _dev_ptr(out.get("terms_partial")))
+    if rc != 0:
+        raise _lib.KnerfError(f"knerf_debug_composite_objective failed ({rc})")
     return out
 
 

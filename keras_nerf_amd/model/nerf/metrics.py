@@ -83,15 +83,17 @@ class MetricState:
             e1.record(torch.cuda.current_stream(self.device))
             self.events.append((e0, e1))
 
-    def update_rays(self, losses):
+    def update_rays(self, losses, mse=None):
         """one step's contribution when the batch is scattered rays: `losses` = device tensor [2], the batch's coarse and fine mean
-        squared errors; they feed the two loss rows, and -10 log10 of them the two PSNR rows.  Device arithmetic, no synchronisation."""
+        squared errors; they feed the two loss rows, and -10 log10 of them the two PSNR rows.  Device arithmetic, no synchronisation.
+        mse: device tensor [2] when the losses are not mean squared errors (another objective): the PSNR rows come from it."""
         if getattr(self, "_ray_rows", None) is None:
             self._ray_rows = torch.tensor([NAMES.index(n) for n in ("coarse_loss", "fine_loss", "coarse_psnr", "fine_psnr")],
                                           device=self.device)
             self._ray_ones = torch.ones(4, device=self.device, dtype=torch.float64)
-        mse = losses.to(device=self.device, dtype=torch.float64).reshape(2)
-        self.state[:, 0].index_add_(0, self._ray_rows, torch.cat([mse, -10.0 * torch.log10(mse)]))
+        loss = losses.to(device=self.device, dtype=torch.float64).reshape(2)
+        mse = loss if mse is None else mse.to(device=self.device, dtype=torch.float64).reshape(2)
+        self.state[:, 0].index_add_(0, self._ray_rows, torch.cat([loss, -10.0 * torch.log10(mse)]))
         self.state[:, 1].index_add_(0, self._ray_rows, self._ray_ones)
 
     def snapshot(self, names=NAMES) -> "MetricLogs":

@@ -16,6 +16,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from ... import losses as _losses
 from ... import optimizers, parallel
 from ...runtime import COARSE, FINE, OCCUPANCY_OUTSIDE, KnerfContext, NonFiniteGradientError, marching_cubes, occupancy_from_grid, occupancy_spec  # noqa: F401
 from .metrics import RAY_NAMES, Mean, MetricLogs, MetricState
@@ -236,14 +237,19 @@ class NeRF:
 
     # ------------------------------------------------------------------ compile (nerf.py:78-173)
     def compile(self, optimizer="adam", loss="mse", batch_size=1, image_height=128, image_width=128, ray_chunks=2048,
-                white_background=False, is_training=True, all_reduce="sum", deterministic=False, skip_dead_tiles=None, **kwargs):
+                white_background=False, is_training=True, all_reduce="sum", deterministic=False, skip_dead_tiles=None,
+                regularizers=None, **kwargs):
         """nerf.py:78-173.  Extensions (keyword-only in spirit; the reference's callers never pass them):
         all_reduce 'sum' | 'mean' (data parallel), deterministic (bit-reproducible gradient sums, slower),
         skip_dead_tiles (None = the library default, on, unless KNERF_SKIP_DEAD_TILES says otherwise: the backward skips 32-sample
-        tiles whose dL/d(rgb, sigma) is exactly zero -- same gradients, less work once the scene has empty space)."""
+        tiles whose dL/d(rgb, sigma) is exactly zero -- same gradients, less work once the scene has empty space).
+        loss: besides mean squared error (by name, None, or a callable that computes it) what keras_nerf_amd.losses.loss_from takes --
+        "mae", "huber", "log_cosh", the classes of that module, Keras loss objects of those classes and their serialised form; any
+        other callable raises ValueError (it could not run inside the kernel).  regularizers: a losses.RayRegularizers (distortion and
+        opacity-entropy terms of the rays' weights) or None."""
         logging.info("Compiling NeRF model")
-        if not _is_mse(loss):
-            raise ValueError("the fused HIP path implements the reference's mean-squared-error loss only")
+        # validated before any context exists: a refused loss raises on a machine without a GPU too
+        objective = _losses.objective_from(None if _is_mse(loss) else loss, regularizers)
         self.optimizer, self.loss = optimizer, loss
         self.batch_size, self.image_height, self.image_width = batch_size, image_height, image_width
         self.white_background = white_background
@@ -278,6 +284,11 @@ class NeRF:
         self._opt_spec = spec
         if not spec.is_plain:                            # schedules, clipping, weight decay: csrc/optim_ext.hip (plain Adam never goes there)
             self._ctx.set_optimizer(spec)
+        self._objective = objective
+        self._loss_fn = _losses.loss_from(None if _is_mse(loss) else loss)
+        self._objective_plain = _losses.is_plain(objective)
+        if not self._objective_plain:                    # other losses, regularisers: csrc/composite_ext.hip (plain mse never goes there)
+            self._ctx.set_objective(objective)
         self.device = self._ctx.device
         self.nerf_utils = NeRFUtils(batch_size, image_height, image_width, self.ray_chunks, self.pos_emb_xyz, self.pos_emb_dir,
                                     white_background, self.oob)
@@ -620,7 +631,8 @@ class NeRF:
             return {"coarse_loss": self._loss_acc[0], "fine_loss": self._loss_acc[1]}
         if ray_mode:
             # the chunks are equally sized, so the accumulated losses are the batch's mean squared errors: losses and PSNR, no SSIM
-            self._metric_state.update_rays(self._loss_acc)
+            # (another objective: the PSNR stays a PSNR -- it comes from the squared-error terms the kernel accumulates beside the loss)
+            self._metric_state.update_rays(self._loss_acc, None if self._objective_plain else self._ctx.objective_terms()[:, 1])
             logs = self._metric_state.snapshot(RAY_NAMES)
         else:
             B, H, W = self.batch_size, self.image_height, self.image_width
@@ -636,8 +648,20 @@ class NeRF:
         images = self._ctx.f32(images)[..., :3].contiguous()
         coarse, fine = self.predict_and_render_images(rays, u, outputs=("image",))     # nerf.py:489-497 reads the two images only
         # whole-image MSE (nerf.py:484-487) from the metrics kernel's squared-difference sums (losses=None)
-        self._metric_state.update(images, coarse["image"], fine["image"], None)
+        losses = None
+        if self._objective.loss_kind != 0:
+            # the chosen photometric term of the two images, without regularisers (one torch reduction each; not the hot path)
+            losses = torch.stack([self._loss_fn(images, coarse["image"]), self._loss_fn(images, fine["image"])]).float()
+        self._metric_state.update(images, coarse["image"], fine["image"], losses)
         return self._metric_state.snapshot()
+
+    def objective_terms(self):
+        """The terms of the last train step's objective, {"coarse": {...}, "fine": {...}} with photometric (the chosen loss), mse,
+        distortion and opacity_entropy (the means over rays of D and H, unweighted) and total (= the net's logged loss).  Lazy: the
+        values leave the device when first read.  Under plain mean squared error the kernel computes no terms and all are 0."""
+        if self._ctx is None:
+            raise RuntimeError("the model is not compiled: call compile(...) first")
+        return ObjectiveTerms(self._ctx.objective_terms(), self._objective)
 
     def evaluate(self, dataset, return_dict=False, callbacks=None, verbose=0):
         """tf.keras.Model.evaluate on the reference's test_step (nerf.py:475-497): the metrics averaged over the dataset's batches, as
@@ -714,3 +738,51 @@ class NeRF:
             steps = None
         self.history = History(history, epochs_run, {"epochs": epochs, "steps": steps, "verbose": verbose})
         return self.history
+
+
+class ObjectiveTerms(dict):
+    """NeRF.objective_terms(): a dict of two dicts whose numbers are read back from the device on first access"""
+
+    _KEYS = ("photometric", "mse", "distortion", "opacity_entropy")
+
+    def __init__(self, dev, objective):
+        super().__init__()
+        self._dev, self._obj = dev, objective
+
+    def _fill(self):
+        if self._dev is not None:
+            v, o = self._dev.cpu().numpy().astype(np.float64), self._obj
+            self._dev = None
+            for n, name in enumerate(("coarse", "fine")):
+                d = dict(zip(self._KEYS, (float(x) for x in v[n])))
+                on = (o.nets >> n) & 1
+                d["total"] = d["photometric"] + (o.distortion * d["distortion"] + o.opacity_entropy * d["opacity_entropy"] if on else 0.0)
+                dict.__setitem__(self, name, d)
+
+    def __getitem__(self, k):
+        self._fill()
+        return dict.__getitem__(self, k)
+
+    def __iter__(self):
+        self._fill()
+        return dict.__iter__(self)
+
+    def __len__(self):
+        return 2
+
+    def keys(self):
+        self._fill()
+        return dict.keys(self)
+
+    def items(self):
+        self._fill()
+        return dict.items(self)
+
+    def values(self):
+        self._fill()
+        return dict.values(self)
+
+    def __repr__(self):
+        self._fill()
+        return dict.__repr__(self)
+

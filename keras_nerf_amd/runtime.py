@@ -564,6 +564,30 @@ class KnerfContext:
         self._check(self.lib.knerf_get_optimizer(self._ctx, C.byref(o)))
         return o
 
+    # ---- the objective (include/knerf.h knerf_set_objective)
+    def set_objective(self, obj=None, **kw):
+        """knerf_set_objective: obj = a _lib.KnerfObjective, or the arguments of losses.objective_from as keywords (loss, regularizers).
+        Stream-ordered, callable between steps.  Mean squared error without a regulariser selects the plain compositing kernel."""
+        if obj is None:
+            from .losses import objective_from
+            obj = objective_from(**kw)
+        elif kw:
+            raise TypeError("set_objective: either a record or keywords")
+        self._check(self.lib.knerf_set_objective(self._ctx, self._stream(), C.byref(obj)))
+
+    def get_objective(self) -> "_lib.KnerfObjective":
+        """the record knerf_set_objective stored (canonical)"""
+        o = _lib.KnerfObjective()
+        self._check(self.lib.knerf_get_objective(self._ctx, C.byref(o)))
+        return o
+
+    def objective_terms(self) -> torch.Tensor:
+        """device tensor [2, 4]: [coarse | fine] x [photometric, mean squared error, mean distortion, mean entropy] of the last
+        train_batch (all zero under the plain objective); a stream-ordered copy, nothing waits"""
+        out = torch.empty((2, 4), device=self.device, dtype=torch.float32)
+        self._check(self.lib.knerf_objective_terms(self._ctx, self._stream(), _ptr(out)))
+        return out
+
     def get_adam_state(self, net: int):
         """(m, v) of one net: Adam's slots in the REAL flat layout (as get_weights)"""
         n = self.param_count if self._pad_index is None else self.padded_param_count
