@@ -292,6 +292,37 @@ int knerf_draw_ray_batch(knerf_ctx* ctx, void* stream, const float* images, cons
                          uint64_t epoch, uint64_t first, int n_rays, const float* noise, uint64_t noise_stream, float* o, float* d,
                          float* t, float* target, int64_t* index);
 
+/* ---- Ray models for forward-facing scenes.  Extension, no reference counterpart (NDC rays and samples linear in disparity as in the
+ * original NeRF release's LLFF configuration).  The two entry points below are knerf_generate_rays and knerf_draw_ray_batch with a ray
+ * model: the same arguments, the same pixel order, the same Philox counters; the plain entry points and their kernels are untouched.
+ *   ndc = 0, spacing = KNERF_SPACING_LINEAR: the plain rays and sample positions, bit for bit (model NULL means this).
+ *   spacing = KNERF_SPACING_DISPARITY (pinhole rays only; near_plane > 0): with s = the plain stratified sample drawn on [0, 1],
+ *     t = 1 / ((1 - s) / near_plane + s / far_plane): linear in 1 / t, monotone in s, so t stays sorted.
+ *   ndc = 1: the pinhole ray (o, d) of a camera that looks along -z is mapped to normalised device coordinates with the near plane at
+ *     distance n = ndc_near: the origin is moved onto the plane, s = -(n + o_z) / d_z, o <- o + s d; then
+ *       o' = (-(2f/W) o_x/o_z, -(2f/H) o_y/o_z, 1 + 2n/o_z)
+ *       d' = (-(2f/W) (d_x/d_z - o_x/o_z), -(2f/H) (d_y/d_z - o_y/o_z), -2n/o_z)
+ *     Written are o' and the UNIT direction d' / L, L = |d'|, and t = s L with s the plain stratified sample drawn on
+ *     [near_plane, far_plane], which must lie inside [0, 1]: o'_z = -1 and (o' + L d'/L)_z = +1, so t in [0, L] runs from the near
+ *     plane to infinity and the deltas of compositing are Euclidean lengths in NDC space.  Rays parallel to the image plane
+ *     (d_z = 0) have no NDC image; a forward-facing capture has none.
+ * KNERF_ERR_INVALID, before any launch, on: what the plain entry points refuse; ndc or spacing outside their values; ndc_near <= 0 or
+ * not finite; disparity spacing with near_plane <= 0; disparity spacing together with ndc; ndc with [near_plane, far_plane] outside
+ * [0, 1]. */
+enum { KNERF_SPACING_LINEAR = 0, KNERF_SPACING_DISPARITY = 1 };
+typedef struct knerf_ray_model {
+    int32_t ndc;                 /* 0 / 1 */
+    int32_t spacing;             /* KNERF_SPACING_* */
+    float ndc_near;              /* > 0; read only when ndc = 1 */
+} knerf_ray_model;
+int knerf_generate_rays_ext(knerf_ctx* ctx, void* stream, const float* c2w, const float* noise, uint64_t seed,
+                            uint64_t stream_id, int batch, int height, int width, int n_samples, float focal,
+                            float near_plane, float far_plane, float* o, float* d, float* t, const knerf_ray_model* model);
+int knerf_draw_ray_batch_ext(knerf_ctx* ctx, void* stream, const float* images, const float* c2w, int n_views, int height, int width,
+                             int channels, float focal, float near_plane, float far_plane, int n_samples, uint64_t seed,
+                             uint64_t epoch, uint64_t first, int n_rays, const float* noise, uint64_t noise_stream, float* o, float* d,
+                             float* t, float* target, int64_t* index, const knerf_ray_model* model);
+
 /* ---- NeRFUtils as stand-alone ops (no context needed; the train/render path fuses the same arithmetic) ----
  * positional_encoding (utils.py:176-186): x [n_rows,3] -> out [n_rows, 3+6L].
  * composite = render_image_depth_chunk (utils.py:16-58): raw [R,S,4] = (r,g,b,sigma), t [R,S] -> image [R,3], depth [R]

@@ -33,6 +33,13 @@ class KnerfObjective(C.Structure):
                 ("nets", C.c_int32)]
 
 
+class KnerfRayModel(C.Structure):
+    """struct knerf_ray_model (include/knerf.h): NDC rays or pinhole rays, sample spacing, the NDC near plane"""
+    _fields_ = [("ndc", C.c_int32), ("spacing", C.c_int32), ("ndc_near", C.c_float)]
+
+
+SPACING_LINEAR, SPACING_DISPARITY = 0, 1
+SPACINGS = {"linear": SPACING_LINEAR, "disparity": SPACING_DISPARITY}
 LOSS_MSE, LOSS_MAE, LOSS_HUBER, LOSS_LOG_COSH = 0, 1, 2, 3
 SCHEDULE_CONSTANT, SCHEDULE_EXPONENTIAL, SCHEDULE_COSINE, SCHEDULE_PIECEWISE = 0, 1, 2, 3
 CLIP_NONE, CLIP_VALUE, CLIP_NORM, CLIP_GLOBAL_NORM = 0, 1, 2, 4
@@ -87,6 +94,11 @@ SIGNATURES = {
                                       C.c_float, C.c_float, C.c_float, _F, _F, _F]),
     "knerf_draw_ray_batch": (C.c_int, [_P, _P, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int,
                                        C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _F, C.c_uint64, _F, _F, _F, _F, _P]),
+    "knerf_generate_rays_ext": (C.c_int, [_P, _P, _F, _F, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_float, C.c_float, C.c_float, _F, _F, _F, C.POINTER(KnerfRayModel)]),
+    "knerf_draw_ray_batch_ext": (C.c_int, [_P, _P, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int,
+                                           C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _F, C.c_uint64, _F, _F, _F, _F, _P,
+                                           C.POINTER(KnerfRayModel)]),
     "knerf_positional_encoding": (C.c_int, [_P, _F, C.c_longlong, C.c_int, _F]),
     "knerf_composite": (C.c_int, [_P, _F, _F, C.c_int, C.c_int, C.c_int, _F, _F, _F]),
     "knerf_inverse_cdf": (C.c_int, [_P, _F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F]),

@@ -22,7 +22,7 @@ LIB = os.path.join(HERE, "libknerf_hip.so")
 PROBE_LIB = os.path.join(HERE, "libknerf_probe.so")
 SOURCES = ["knerf_api.hip", "mlp_fwd.hip", "mlp_bwd.hip", "wgrad.hip", "generic.hip", "composite.hip", "sampler.hip", "optim.hip",
            "raygen.hip", "utils_ops.hip", "query.hip", "mesh.hip", "occupancy.hip", "train_list.hip",
-           "termination.hip", "raybatch.hip", "optim_ext.hip", "composite_ext.hip"]
+           "termination.hip", "raybatch.hip", "optim_ext.hip", "composite_ext.hip", "rays_ext.hip"]
 # The three big kernels are templates on the trunk shape (csrc/layout.h KNERF_FUSED_SHAPES): each of these sources is compiled once
 # per shape with -DKNERF_SHAPE_SLICE=<index> (that translation unit then defines the kernels of its shape only; slice 0 also holds
 # the run-time dispatchers), so the shapes build in parallel and the default shape's object is what it was before the others existed.
@@ -36,7 +36,7 @@ PROBE_SOURCES = ["debug_api.hip", "probe.hip"]
 # round 6: a concat behind the LAST trunk layer ((n_layers - 1) % skip_layer == 0): the head takes [h ; xyz_enc ; dir_enc]
 XSHAPES = ["6,3,128", "8,2,128", "8,4,256,6,2", "8,4,256,12,4", "8,4,128,5,1", "4,2,256,16,3",
            "6,3,64", "8,4,64,6,2", "8,4,256,10,8", "8,4,128,10,6", "9,4,256", "5,2,128", "5,4,64,6,2"]
-HEADERS = ["chain.h", "ctx.h", "kernels.h", "layout.h", "bwd_body.h", "wgrad_body.h", "generic.h", "query.h", "mesh_table.h", "occupancy.h", "train_list.h", "termination.h", "rays.h", "optim_ext.h", "composite_ext.h", os.path.join("..", "..", "include", "knerf.h"),
+HEADERS = ["chain.h", "ctx.h", "kernels.h", "layout.h", "bwd_body.h", "wgrad_body.h", "generic.h", "query.h", "mesh_table.h", "occupancy.h", "train_list.h", "termination.h", "rays.h", "rays_ext.h", "optim_ext.h", "composite_ext.h", os.path.join("..", "..", "include", "knerf.h"),
            os.path.join("..", "..", "include", "knerf_debug.h")]
 # -ffp-contract=off: the parity-critical fp32 arithmetic (ray points, sampler, compositing) must round like the
 # reference's separate mul/add ops; fused multiply-adds are written explicitly (__builtin_fmaf) where wanted.

@@ -21,6 +21,7 @@
 #include "optim_ext.h"
 #include "query.h"
 #include "rays.h"
+#include "rays_ext.h"
 #include "termination.h"
 #include "train_list.h"
 
@@ -1571,6 +1572,68 @@ int knerf_draw_ray_batch(knerf_ctx* ctx, void* stream, const float* images, cons
     a.n_rays = n_rays; a.H = height; a.W = width; a.C = channels; a.N = n_samples;
     a.focal = focal; a.near_ = near_plane; a.far_ = far_plane;
     if (launch_raybatch(a, (hipStream_t)stream) != hipSuccess) return fail(ctx, KNERF_ERR_HIP, "draw_ray_batch: launch failed");
+    return KNERF_OK;
+}
+
+// the checks of a ray model against the sample range it is used with; null = pinhole rays with linear spacing
+static int check_ray_model(knerf_ctx* ctx, const char* who, const knerf_ray_model* model, float near_plane, float far_plane, RayModel* out) {
+    const std::string w = std::string(who) + ": ";
+    knerf_ray_model m{0, KNERF_SPACING_LINEAR, 1.f};
+    if (model) m = *model;
+    if (m.ndc != 0 && m.ndc != 1) return fail(ctx, KNERF_ERR_INVALID, w + "ndc must be 0 or 1");
+    if (m.spacing != KNERF_SPACING_LINEAR && m.spacing != KNERF_SPACING_DISPARITY)
+        return fail(ctx, KNERF_ERR_INVALID, w + "unknown spacing " + std::to_string(m.spacing));
+    if (!(std::isfinite(m.ndc_near) && m.ndc_near > 0.f)) return fail(ctx, KNERF_ERR_INVALID, w + "ndc_near must be finite and > 0");
+    if (m.ndc && m.spacing == KNERF_SPACING_DISPARITY)
+        return fail(ctx, KNERF_ERR_INVALID, w + "NDC rays are sampled linearly in NDC depth; disparity spacing is for pinhole rays");
+    if (m.spacing == KNERF_SPACING_DISPARITY && !(near_plane > 0.f && far_plane > 0.f))
+        return fail(ctx, KNERF_ERR_INVALID, w + "disparity spacing needs near_plane > 0");
+    if (m.ndc && !(near_plane >= 0.f && far_plane <= 1.f && near_plane <= far_plane))
+        return fail(ctx, KNERF_ERR_INVALID, w + "NDC rays take their samples at fractions of the ray: need 0 <= near_plane <= far_plane <= 1");
+    *out = RayModel{m.ndc, m.spacing, m.ndc_near};
+    return KNERF_OK;
+}
+
+int knerf_generate_rays_ext(knerf_ctx* ctx, void* stream, const float* c2w, const float* noise, uint64_t seed, uint64_t stream_id,
+                            int batch, int height, int width, int n_samples, float focal, float near_plane, float far_plane,
+                            float* o, float* d, float* t, const knerf_ray_model* model) {
+    if (!c2w || !o || !d || !t || batch <= 0 || height <= 0 || width <= 0 || n_samples <= 0)
+        return fail(ctx, KNERF_ERR_INVALID, "generate_rays_ext: null/empty argument");
+    if ((unsigned long long)batch * (unsigned long long)height * (unsigned long long)width >= (1ull << 39) / (unsigned long long)n_samples)
+        return fail(ctx, KNERF_ERR_INVALID, "generate_rays_ext: batch x height x width x n_samples is too large for one launch");
+    RayModel m{};
+    if (int r = check_ray_model(ctx, "generate_rays_ext", model, near_plane, far_plane, &m)) return r;
+    RayGenArgs a{};
+    a.c2w = c2w; a.noise = noise; a.o = o; a.d = d; a.t = t; a.B = batch; a.H = height; a.W = width; a.N = n_samples;
+    a.focal = focal; a.near_ = near_plane; a.far_ = far_plane; a.seed = seed; a.stream_id = stream_id;
+    if (launch_raygen_ext(a, m, (hipStream_t)stream) != hipSuccess) return fail(ctx, KNERF_ERR_HIP, "generate_rays_ext: launch failed");
+    return KNERF_OK;
+}
+
+int knerf_draw_ray_batch_ext(knerf_ctx* ctx, void* stream, const float* images, const float* c2w, int n_views, int height, int width,
+                             int channels, float focal, float near_plane, float far_plane, int n_samples, uint64_t seed, uint64_t epoch,
+                             uint64_t first, int n_rays, const float* noise, uint64_t noise_stream, float* o, float* d, float* t,
+                             float* target, int64_t* index, const knerf_ray_model* model) {
+    if (!images || !c2w || !o || !d || !t || !target || n_views <= 0 || height <= 0 || width <= 0 || n_samples <= 0 || n_rays <= 0)
+        return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch_ext: null/empty argument");
+    if (channels != 3 && channels != 4) return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch_ext: channels must be 3 or 4");
+    const unsigned long long hw = (unsigned long long)height * (unsigned long long)width;
+    if (hw >= (1ull << 31) || hw * (unsigned long long)n_views >= (1ull << 40))
+        return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch_ext: the dataset must hold fewer than 2^40 pixels (2^31 per view)");
+    const unsigned long long P = hw * (unsigned long long)n_views;
+    if (first > P || (unsigned long long)n_rays > P - first)
+        return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch_ext: first + n_rays exceeds the pixels of the dataset");
+    if ((unsigned long long)n_rays * (unsigned long long)n_samples >= (1ull << 39))
+        return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch_ext: n_rays x n_samples is too large for one launch");
+    RayModel m{};
+    if (int r = check_ray_model(ctx, "draw_ray_batch_ext", model, near_plane, far_plane, &m)) return r;
+    RayBatchArgs a{};
+    a.images = images; a.c2w = c2w; a.noise = noise; a.o = o; a.d = d; a.t = t; a.target = target; a.index = (long long*)index;
+    a.perm = make_pixel_perm(P, seed, epoch);
+    a.first = first; a.seed = seed; a.noise_stream = noise_stream;
+    a.n_rays = n_rays; a.H = height; a.W = width; a.C = channels; a.N = n_samples;
+    a.focal = focal; a.near_ = near_plane; a.far_ = far_plane;
+    if (launch_raybatch_ext(a, m, (hipStream_t)stream) != hipSuccess) return fail(ctx, KNERF_ERR_HIP, "draw_ray_batch_ext: launch failed");
     return KNERF_OK;
 }
 

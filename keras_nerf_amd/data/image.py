@@ -2,7 +2,10 @@
 
 PNG -> float32 RGBA in [0,1], antialiased bilinear resize IN FLOAT32, RGB composited over a white or black background with the
 image's alpha, alpha kept as 4th channel, clip.  Note the reference passes (image_width, image_height) as the resize SIZE
-(image.py:22-23, i.e. height := image_width) -- identical for the square images it is used with; kept here.
+(image.py:22-23, i.e. height := image_width) -- identical for the square images it is used with; kept here as the default.
+`height_first=True` resizes to rows = image_height, cols = image_width instead (the forward-facing loader, data/llff.py: its
+photographs are never square); `output_size` says which (rows, cols) come out.  Any format PIL opens is accepted (JPEG photographs
+have no alpha: it is 1).
 
 The resize follows what `tf.image.resize(image, size, antialias=True)` (method bilinear, image.py:22-23) computes -- TensorFlow's
 scale-and-translate resampler with the triangle kernel: for output index x the sample point (x + 0.5) * in / out, a kernel widened by
@@ -54,13 +57,21 @@ def resize_antialiased(img: np.ndarray, rows: int, cols: int) -> np.ndarray:
 
 
 class ImageLoader:
-    def __init__(self, image_width: int, image_height: int, white_background: bool = False, **kwargs):
+    def __init__(self, image_width: int, image_height: int, white_background: bool = False, height_first: bool = False, **kwargs):
         self.image_width, self.image_height, self.white_background = image_width, image_height, white_background
+        self.height_first = bool(height_first)
+
+    @property
+    def output_size(self) -> tuple:
+        """(rows, cols) of the images this loader returns"""
+        if self.height_first:
+            return int(self.image_height), int(self.image_width)
+        return int(self.image_width), int(self.image_height)      # tf.image.resize(image, (image_width, image_height))
 
     def __call__(self, image_path) -> np.ndarray:
         img = Image.open(image_path).convert("RGBA")
         a = np.asarray(img, dtype=np.float32) / np.float32(255.0)                  # convert_image_dtype(uint8 -> float32)
-        rows, cols = self.image_width, self.image_height          # tf.image.resize(image, (image_width, image_height))
+        rows, cols = self.output_size
         a = resize_antialiased(a, rows, cols)
         alpha = a[..., 3:4]
         bg = np.ones_like(a[..., :3]) if self.white_background else np.zeros_like(a[..., :3])

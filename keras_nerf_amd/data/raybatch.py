@@ -82,6 +82,13 @@ def rank_positions(step: int, rays_per_step: int, rank: int = 0, world: int = 1)
     return step * rays_per_step + rank * n, n
 
 
+def loader_output_size(image_loader):
+    """(rows, cols) of the images a loader returns: its `output_size`, or the reference's swapped (image_width, image_height) for a
+    loader that does not say (ImageLoader's default)"""
+    size = getattr(image_loader, "output_size", None)
+    return tuple(int(v) for v in size) if size is not None else (int(image_loader.image_width), int(image_loader.image_height))
+
+
 class RayBatchDataset:
     """Re-iterable; one iteration is one epoch of `len(self)` steps, each yielding (target [n,3], (o [n,3], d [n,3], t [n,n_coarse]))
     on the device, n = rays_per_step / world.
@@ -96,7 +103,8 @@ class RayBatchDataset:
         self.steps_per_epoch = None if steps_per_epoch is None else int(steps_per_epoch)
         ld = images.image_loader
         self.n_views = len(images.image_paths)
-        self.n_pixels = self.n_views * int(ld.image_width) * int(ld.image_height)
+        self._rows, self._cols = loader_output_size(ld)
+        self.n_pixels = self.n_views * self._rows * self._cols
         if self.rays_per_step <= 0 or self.rays_per_step > self.n_pixels:
             raise ValueError(f"rays_per_step = {rays_per_step}: the dataset has {self.n_pixels} pixels")
         if self.steps_per_epoch is not None and self.steps_per_epoch <= 0:
@@ -129,8 +137,7 @@ class RayBatchDataset:
         if need > ds.device_cache_gb * 1e9:
             raise ValueError(f"ray batches need the whole dataset on the device: {need / 1e9:.2f} GB of images exceed "
                              f"device_cache_gb = {ds.device_cache_gb}")
-        ld = ds.image_loader
-        dev, have, cams = ds._resident((int(ld.image_width), int(ld.image_height), 4))      # (rows, cols) as ImageLoader resizes
+        dev, have, cams = ds._resident((self._rows, self._cols, 4))      # (rows, cols) as the image loader resizes
         missing = [i for i in range(self.n_views) if not have[i]]
         for k in range(0, len(missing), 16):                   # decode on the host, pinned non-blocking uploads
             idx = missing[k:k + 16]
@@ -156,6 +163,8 @@ class RayBatchDataset:
         if (rg.image_height, rg.image_width) != tuple(dev.shape[1:3]):
             raise ValueError(f"the ray generator's {rg.image_height} x {rg.image_width} pixels do not match the images' "
                              f"{dev.shape[1]} x {dev.shape[2]}")
+        model = getattr(rg, "ray_model", None)                 # None: the plain rays through the plain entry point
+        extra = {} if model is None else {"ray_model": model}
 
         def gen():
             for perm, step in steps:
@@ -165,6 +174,6 @@ class RayBatchDataset:
                 self._drawn += 1
                 self.last_draw = (perm, first, n)              # what the batch just yielded holds: positions [first, first + n) of `perm`
                 o, d, t, target = draw_ray_batch(dev, cams, rg.focal_length, rg.near, rg.far, rg.n_sample, self.seed, perm, first, n,
-                                                 noise_stream=stream)
+                                                 noise_stream=stream, **extra)
                 yield target, (o, d, t)
         return gen()

@@ -1,4 +1,8 @@
-"""RaysGenerator -- counterpart of reference keras_nerf/data/rays.py:4-130, generated on the GPU (csrc/raygen.hip)."""
+"""RaysGenerator -- counterpart of reference keras_nerf/data/rays.py:4-130, generated on the GPU (csrc/raygen.hip).
+
+Beyond the reference: `ndc=True` writes normalised-device-coordinate rays for forward-facing scenes and `spacing="disparity"` spaces
+the samples of pinhole rays linearly in 1 / depth (csrc/rays_ext.hip).  With the defaults the plain entry
+point is called exactly as before."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,13 +16,32 @@ from ..runtime import KnerfError
 
 class RaysGenerator:
     def __init__(self, focal_length: float, image_width: int, image_height: int, near: float, far: float, n_sample: int,
-                 seed: int = 0, **kwargs):
+                 seed: int = 0, ndc: bool = False, ndc_near: float = 1.0, spacing: str = "linear", **kwargs):
         self.focal_length, self.image_width, self.image_height = float(focal_length), int(image_width), int(image_height)
         self.near, self.far, self.n_sample = float(near), float(far), int(n_sample)
         self.seed, self._calls = seed, 0
+        self.ndc, self.ndc_near, self.spacing = bool(ndc), float(ndc_near), spacing
+        if spacing not in _lib.SPACINGS:
+            raise ValueError(f"spacing = {spacing!r}: expected one of {sorted(_lib.SPACINGS)}")
+        if not (np.isfinite(self.ndc_near) and self.ndc_near > 0):
+            raise ValueError(f"ndc_near = {ndc_near}: the NDC near plane lies at a positive distance in front of the camera")
+        if self.ndc and spacing == "disparity":
+            raise ValueError("NDC rays are sampled linearly in NDC depth (already linear in disparity of the scene); "
+                             "spacing='disparity' is for pinhole rays")
+        if spacing == "disparity" and not self.near > 0:
+            raise ValueError(f"spacing='disparity' needs near > 0, got {near}")
+        if self.ndc and not 0 <= self.near <= self.far <= 1:
+            raise ValueError(f"NDC rays take their samples at fractions of the ray: need 0 <= near <= far <= 1, got {near}, {far}")
         if not torch.cuda.is_available():
             raise KnerfError("keras_nerf_amd needs an MI355X (gfx950) GPU; there is no CPU path")
         self._lib = _lib.load()
+
+    @property
+    def ray_model(self):
+        """None for the plain rays (pinhole, samples linear in depth), else the struct knerf_ray_model of this generator"""
+        if not self.ndc and self.spacing == "linear":
+            return None
+        return _lib.KnerfRayModel(int(self.ndc), _lib.SPACINGS[self.spacing], self.ndc_near)
 
     def __call__(self, camera_params, noise=None):
         """camera_params: 4x4 camera-to-world (or [B,4,4]).  Returns (ray_origin, ray_direction [...,H,W,3],
@@ -33,8 +56,15 @@ class RaysGenerator:
         o = torch.empty((B, H, W, 3), device="cuda"); d = torch.empty_like(o); t = torch.empty((B, H, W, N), device="cuda")
         self._calls += 1
         p = lambda x: None if x is None else C.c_void_p(x.data_ptr())
-        rc = self._lib.knerf_generate_rays(None, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(c2w), p(nz), self.seed,
-                                           self._calls, B, H, W, N, self.focal_length, self.near, self.far, p(o), p(d), p(t))
+        model = self.ray_model
+        if model is None:
+            rc = self._lib.knerf_generate_rays(None, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(c2w), p(nz), self.seed,
+                                               self._calls, B, H, W, N, self.focal_length, self.near, self.far, p(o), p(d), p(t))
+        else:
+            rc = self._lib.knerf_generate_rays_ext(None, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(c2w), p(nz), self.seed,
+                                                   self._calls, B, H, W, N, self.focal_length, self.near, self.far, p(o), p(d), p(t),
+                                                   C.byref(model))
         if rc != 0:
-            raise KnerfError(f"knerf_generate_rays failed ({rc})")
+            raise KnerfError(f"knerf_generate_rays{'' if model is None else '_ext'} failed ({rc}): "
+                             f"{self._lib.knerf_last_error(None).decode(errors='replace')}")
         return (o[0], d[0], t[0]) if single else (o, d, t)
