@@ -451,6 +451,69 @@ int knerf_occupancy_decay_max(void* stream, float* state, const float* sigma, ui
  * passes.  Synchronises `stream`. */
 int knerf_termination_stats(knerf_ctx* ctx, void* stream, int64_t* live, int64_t* total, int reset);
 
+/* ---- The baked field: a voxel grid with spherical-harmonic colour, rendered without the MLP.  Extension, no reference counterpart
+ * (as PlenOctrees, SNeRG and Plenoxels bake a trained NeRF).  All three entry points are context-free; every pointer is a DEVICE
+ * pointer unless it says HOST.
+ * Lattice [Rx,Ry,Rz] (C order, z fastest; 2 <= R <= 1025 per axis) placed over [lo, hi] as in knerf_query_grid.  One RECORD per lattice
+ * point, records in lattice order:
+ *   bytes 0..3: fp32 sigma (the net's density after ReLU; the baker stores every value <= its threshold as 0);
+ *   then 3 K halfs, K = (sh_degree + 1)^2, sh_degree 0..3, ordered [k][c] (coefficient k of colour channel c);
+ *   zero padding to a multiple of 16 bytes: 16 / 32 / 64 / 112 bytes per record for degree 0 / 1 / 2 / 3.
+ * Colour seen along the unit vector u: clamp(sum_k c_k Y_k(u), 0, 1), Y_k the orthonormal real spherical harmonics, k = l (l + 1) + m,
+ * without the Condon-Shortley phase (Y_0 = 1 / (2 sqrt(pi)), Y_1..3 = sqrt(3 / (4 pi)) (y, z, x), ...: csrc/baked.hip sh_eval).
+ * points x record bytes must stay below 2^40 (KNERF_ERR_INVALID otherwise); every element offset is computed in 64 bits. */
+/* knerf_baked_project -- extension, no reference counterpart.  One direction of the least-squares SH fit, for i < n, k < n_coeff, c < 3:
+ *   comp NULL:  acc[i][k][c] = fma(fit[k][j], rgb[i][c], acc[i][k][c]), one fused multiply-add per element;
+ *   otherwise:  a compensated sum: acc takes the rounded sum, comp [n, n_coeff, 3] collects the rounding errors of the product (by fma)
+ *               and of the sum (two-sum), both exact in fp32, so acc + comp carries the sum of all directions to about one rounding
+ *               whatever the partial sums were (the plain form loses up to n_dirs x 2^-24 x the largest partial sum).
+ * rgb [n,3], fit [n_coeff, n_dirs] (the pseudo-inverse of the basis at the fit directions), acc [n, n_coeff, 3], all fp32.
+ * KNERF_ERR_INVALID: a NULL rgb, fit or acc, n_coeff not in {1, 4, 9, 16}, n_dirs < 1, j outside [0, n_dirs), acc of 2^40 bytes or more. */
+int knerf_baked_project(void* stream, const float* rgb, const float* fit, int n_coeff, int n_dirs, int j, uint64_t n, float* acc,
+                        float* comp);
+/* knerf_baked_pack -- extension, no reference counterpart.  Writes n whole records: record p = index[i] (int64 [n], every value in
+ * [0, n_points); index NULL: p = i and n = n_points) gets sigma[p] (sigma: fp32 [n_points], the whole lattice) and acc[i] [K,3] fp32
+ * (comp not NULL: fp32(acc[i] + comp[i]), knerf_baked_project's pair) rounded to fp16 (nearest even).  Records not named keep their
+ * bytes (the baker starts from zeros).
+ * KNERF_ERR_INVALID: a NULL sigma, acc or records, sh_degree outside 0..3, n > n_points, index NULL with n != n_points,
+ * n_points x record bytes >= 2^40. */
+int knerf_baked_pack(void* stream, const float* sigma, const float* acc, const float* comp, const int64_t* index, uint64_t n,
+                     uint64_t n_points, int sh_degree, void* records);
+/* knerf_baked_render -- extension, no reference counterpart.  Volume rendering of n_rays rays through a baked field.
+ * field: HOST struct; records as above; bits: the occupancy bitfield of the (Rx-1)(Ry-1)(Rz-1) cells in the layout of
+ * knerf_set_occupancy (bit set = some corner has sigma > 0), needed only with KNERF_BAKED_SKIP_EMPTY.
+ * origins, directions [n_rays,3]; near, far [n_rays] or NULL (then near_all / far_all hold for every ray).  t is in units of |d|:
+ * directions need not be unit vectors.  Per ray, in fp32 unless said otherwise:
+ *   S = ceil((far - near) / step) evaluated in double (at most 2^23), samples i = 0..S-1 at t_i = near + (i + 0.5) step,
+ *   p = __fadd_rn(o, __fmul_rn(d, t_i)).  Sample positions do not depend on the box; the ray-box intersection only narrows the range of
+ *   i that is visited (an axis with d = 0 is inside for all t if lo <= o <= hi, else the ray misses).
+ *   u = __fmul_rn(__fsub_rn(p, lo), scale), scale = fp32(cells / (hi - lo)) computed in double (knerf_set_occupancy's lookup); a sample
+ *   with u < 0, u > cells or u NaN on any axis is outside: sigma = 0.  Otherwise cell = min(floor(u), cells - 1) (a sample on the upper
+ *   face belongs to the last cell), sigma and the coefficients are interpolated trilinearly with weights from u - cell.
+ *   alpha = 1 - expf(-sigma step |d|), w = T alpha, image += w colour(d / |d|), depth += w t_i, opacity += w, T <- T (1 - alpha),
+ *   strictly in ascending i, T = 1 at the start.  termination = eps > 0: the ray stops once T < eps.
+ *   KNERF_BAKED_WHITE_BACKGROUND: image += 1 - opacity at the end.  The image is clipped to [0, 1].
+ * KNERF_BAKED_SKIP_EMPTY: samples in cells whose bit is 0 are not fetched.  With bits as described their trilinear sigma is exactly 0,
+ * so alpha = w = 0 and T is unchanged: outputs with and without the flag are bit-identical.
+ * Lanes per ray (bits 8..11 of flags): 0 = the library's choice, 1 = one ray per lane, 2 (degree 1) / 4 (degree 2 and 3) = a group of
+ * lanes reads each record as one contiguous fetch and adds its channel sums across lanes; the choices differ in summation order only.
+ * image [n_rays,3], depth [n_rays], opacity [n_rays]: each may be NULL.  stats: int64 [2] or NULL; [0] += samples whose 8 corners
+ * were fetched, [1] += sum of S over the rays (one atomic pair per wave).
+ * KNERF_ERR_INVALID, before any launch: NULL field, records, origins or directions; no output and no stats; sh_degree outside 0..3; a
+ * resolution outside 2..1025; lo / hi not finite or hi <= lo; points x record bytes >= 2^40; step <= 0 or not finite; termination
+ * outside [0, 1); unknown flag bits, a lane count the degree does not have, SKIP_EMPTY without bits; n_rays >= 2^36. */
+enum { KNERF_BAKED_WHITE_BACKGROUND = 1, KNERF_BAKED_SKIP_EMPTY = 2, KNERF_BAKED_LANES_SHIFT = 8, KNERF_BAKED_LANES_MASK = 0xF00 };
+typedef struct knerf_baked_field {
+    const void* records;         /* DEVICE */
+    const uint32_t* bits;        /* DEVICE, may be NULL without KNERF_BAKED_SKIP_EMPTY */
+    int32_t resolution[3];       /* lattice points per axis */
+    int32_t sh_degree;           /* 0..3 */
+    float lo[3], hi[3];
+} knerf_baked_field;
+int knerf_baked_render(void* stream, const knerf_baked_field* field, const float* origins, const float* directions, const float* near,
+                       const float* far, float near_all, float far_all, uint64_t n_rays, float step, float termination, int flags,
+                       float* image, float* depth, float* opacity, int64_t* stats);
+
 /* Diagnostics (layout tables, workspace views, hardware-fact and bandwidth probes) are NOT part of this library: they are
  * declared in include/knerf_debug.h and built into libknerf_probe.so for tests/ and tools/ only. */
 

@@ -38,6 +38,13 @@ class KnerfRayModel(C.Structure):
     _fields_ = [("ndc", C.c_int32), ("spacing", C.c_int32), ("ndc_near", C.c_float)]
 
 
+class KnerfBakedField(C.Structure):
+    """struct knerf_baked_field (include/knerf.h): device records and occupancy bits, lattice resolution, SH degree, the box"""
+    _fields_ = [("records", C.c_void_p), ("bits", C.c_void_p), ("resolution", C.c_int32 * 3), ("sh_degree", C.c_int32),
+                ("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+
+BAKED_WHITE_BACKGROUND, BAKED_SKIP_EMPTY, BAKED_LANES_SHIFT = 1, 2, 8
 SPACING_LINEAR, SPACING_DISPARITY = 0, 1
 SPACINGS = {"linear": SPACING_LINEAR, "disparity": SPACING_DISPARITY}
 LOSS_MSE, LOSS_MAE, LOSS_HUBER, LOSS_LOG_COSH = 0, 1, 2, 3
@@ -114,6 +121,10 @@ SIGNATURES = {
     "knerf_occupancy_train_stats": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
     "knerf_occupancy_decay_max": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_float]),
     "knerf_termination_stats": (C.c_int, [_P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int]),
+    "knerf_baked_project": (C.c_int, [_P, _F, _F, C.c_int, C.c_int, C.c_int, C.c_uint64, _F, _F]),
+    "knerf_baked_pack": (C.c_int, [_P, _F, _F, _F, _P, C.c_uint64, C.c_uint64, C.c_int, _P]),
+    "knerf_baked_render": (C.c_int, [_P, C.POINTER(KnerfBakedField), _F, _F, _F, _F, C.c_float, C.c_float, C.c_uint64, C.c_float,
+                                     C.c_float, C.c_int, _F, _F, _F, _P]),
 }
 
 _lib = None

@@ -1,0 +1,415 @@
+"""The baked field: a trained NeRF stored as a voxel grid with spherical-harmonic colour and rendered without the MLP (extension,
+no reference counterpart; PlenOctrees, SNeRG and Plenoxels bake a trained NeRF in this way).
+
+The arithmetic is HIP (csrc/baked.hip: knerf_baked_project, knerf_baked_pack, knerf_baked_render; include/knerf.h holds the contract);
+torch is used for device memory, streams and the index plumbing of the bake only.  Host-side pieces (basis, fit matrix, record
+layout) are NumPy and need no device.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+MAX_DEGREE = 3
+MAX_RECORD_BYTES = 1 << 40
+OUTPUTS = ("image", "depth", "opacity")
+SLAB_BYTES = 1 << 30       # working memory of one slab of a bake (accumulator + compensation) or of from_arrays (fp32 coefficients)
+LANES = {0: (1,), 1: (1, 2), 2: (1, 4), 3: (1, 4)}        # lanes per ray the render kernel is built for, per degree
+
+
+def check_degree(sh_degree) -> int:
+    if isinstance(sh_degree, bool) or not isinstance(sh_degree, (int, np.integer)) or not 0 <= int(sh_degree) <= MAX_DEGREE:
+        raise ValueError(f"sh_degree must be an integer 0..{MAX_DEGREE}, got {sh_degree!r}")
+    return int(sh_degree)
+
+
+def n_coefficients(sh_degree: int) -> int:
+    return (check_degree(sh_degree) + 1) ** 2
+
+
+def record_bytes(sh_degree: int) -> int:
+    """fp32 sigma + 3 K halfs, padded to a multiple of 16 bytes: 16 / 32 / 64 / 112"""
+    return (4 + 6 * n_coefficients(sh_degree) + 15) // 16 * 16
+
+
+def sh_basis(directions, sh_degree: int) -> np.ndarray:
+    """The orthonormal real spherical harmonics Y_k, k = l (l + 1) + m, without the Condon-Shortley phase, at unit vectors [..., 3]:
+    [..., K] in float64 (the constants of csrc/baked.hip sh_eval)."""
+    deg = check_degree(sh_degree)
+    v = np.asarray(directions, dtype=np.float64)
+    x, y, z = v[..., 0], v[..., 1], v[..., 2]
+    pi = np.pi
+    Y = [np.full(x.shape, 0.5 / np.sqrt(pi))]
+    if deg >= 1:
+        c = np.sqrt(3.0 / (4.0 * pi))
+        Y += [c * y, c * z, c * x]
+    if deg >= 2:
+        a, b = 0.5 * np.sqrt(15.0 / pi), 0.25 * np.sqrt(5.0 / pi)
+        Y += [a * x * y, a * y * z, b * (3.0 * z * z - 1.0), a * x * z, 0.5 * a * (x * x - y * y)]
+    if deg >= 3:
+        a, b = 0.25 * np.sqrt(35.0 / (2.0 * pi)), 0.5 * np.sqrt(105.0 / pi)
+        c, d = 0.25 * np.sqrt(21.0 / (2.0 * pi)), 0.25 * np.sqrt(7.0 / pi)
+        Y += [a * y * (3.0 * x * x - y * y), b * x * y * z, c * y * (5.0 * z * z - 1.0), d * z * (5.0 * z * z - 3.0),
+              c * x * (5.0 * z * z - 1.0), 0.5 * b * z * (x * x - y * y), a * x * (x * x - 3.0 * y * y)]
+    return np.stack(Y, axis=-1)
+
+
+def fibonacci_sphere(n: int) -> np.ndarray:
+    """n unit vectors [n, 3] (float64) on the golden-angle spiral: z_i = 1 - (2 i + 1) / n, longitude i * pi (3 - sqrt 5)"""
+    i = np.arange(int(n), dtype=np.float64)
+    z = 1.0 - (2.0 * i + 1.0) / float(n)
+    r = np.sqrt(np.maximum(0.0, 1.0 - z * z))
+    phi = i * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=-1)
+
+
+def default_directions(sh_degree: int) -> int:
+    K = n_coefficients(sh_degree)
+    return 1 if K == 1 else max(4 * K, 16)
+
+
+def fit_directions(sh_degree: int, n_directions=None):
+    """(directions [D,3] float64, P = pinv(Y) [K,D] float64) of the least-squares SH fit.  Degree 0: one zero direction (the network
+    seen as query(points, None) sees it) and P = 1 / Y_0.  Otherwise a Fibonacci sphere of D = n_directions (default max(4 K, 16))
+    unit vectors; D < 2 K is refused."""
+    K = n_coefficients(sh_degree)
+    if K == 1:
+        if n_directions not in (None, 1):
+            raise ValueError(f"sh_degree 0 is baked from the single zero direction; n_directions must be None or 1, got {n_directions!r}")
+        return np.zeros((1, 3)), np.array([[2.0 * np.sqrt(np.pi)]])
+    D = default_directions(sh_degree) if n_directions is None else n_directions
+    if isinstance(D, bool) or not isinstance(D, (int, np.integer)) or D < 2 * K:
+        raise ValueError(f"n_directions must be an integer >= 2 K = {2 * K} for sh_degree {sh_degree}, got {n_directions!r}")
+    dirs = fibonacci_sphere(int(D))
+    return dirs, np.linalg.pinv(sh_basis(dirs, sh_degree))
+
+
+def pack_records(sigma: np.ndarray, coefficients: np.ndarray) -> np.ndarray:
+    """NumPy mirror of the record layout (knerf_baked_pack): sigma [...] fp32, coefficients [..., K, 3] fp16 -> uint8 [P, record bytes]"""
+    co = np.ascontiguousarray(coefficients, dtype=np.float16)
+    K = co.shape[-2]
+    deg = int(round(np.sqrt(K))) - 1
+    if co.shape[-1] != 3 or (deg + 1) ** 2 != K:
+        raise ValueError(f"coefficients must be [..., K, 3] with K = 1, 4, 9 or 16, got {co.shape}")
+    sg = np.ascontiguousarray(sigma, dtype=np.float32).reshape(-1)
+    co = co.reshape(-1, 3 * K)
+    if co.shape[0] != sg.size:
+        raise ValueError(f"{sg.size} sigma values for {co.shape[0]} coefficient sets")
+    rec = np.zeros((sg.size, record_bytes(deg)), dtype=np.uint8)
+    rec[:, :4] = sg.view(np.uint8).reshape(-1, 4)
+    rec[:, 4:4 + 6 * K] = co.view(np.uint8).reshape(-1, 6 * K)
+    return rec
+
+
+def unpack_records(records: np.ndarray, sh_degree: int):
+    """the inverse of pack_records: (sigma [P] fp32, coefficients [P, K, 3] fp16)"""
+    K = n_coefficients(sh_degree)
+    rec = np.ascontiguousarray(records, dtype=np.uint8).reshape(-1, record_bytes(sh_degree))
+    sg = np.ascontiguousarray(rec[:, :4]).view(np.float32).reshape(-1)
+    co = np.ascontiguousarray(rec[:, 4:4 + 6 * K]).view(np.float16).reshape(-1, K, 3)
+    return sg, co
+
+
+def check_table_size(n_points: int, sh_degree: int) -> int:
+    """the bytes of n_points records; ValueError at 2^40 bytes and more (the kernels refuse such a table with KNERF_ERR_INVALID)"""
+    nbytes = int(n_points) * record_bytes(sh_degree)
+    if nbytes >= MAX_RECORD_BYTES:
+        raise ValueError(f"{int(n_points)} records of {record_bytes(sh_degree)} bytes reach 2^40 bytes; lower the resolution or sh_degree")
+    return nbytes
+
+
+def check_lattice_spec(resolution, bounds, sh_degree):
+    """validated ((Rx,Ry,Rz), lo[3], hi[3]); ValueError on a resolution outside 2..1025, hi <= lo, or 2^40 bytes of records and more"""
+    res = (resolution,) * 3 if isinstance(resolution, (int, np.integer)) and not isinstance(resolution, bool) else \
+        (tuple(resolution) if isinstance(resolution, (tuple, list, np.ndarray)) else ())
+    if len(res) != 3 or any(isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 2 <= int(r) <= 1025 for r in res):
+        raise ValueError(f"resolution must be an int or three ints, each 2..1025 lattice points; got {resolution!r}")
+    try:
+        lo, hi = ([float(v) for v in b] for b in bounds)
+    except (TypeError, ValueError):
+        raise ValueError(f"bounds must be (lo[3], hi[3]); got {bounds!r}") from None
+    if len(lo) != 3 or len(hi) != 3 or not all(np.isfinite(np.float32(v)) for v in lo + hi) or \
+            not all(np.float32(h) > np.float32(l) for l, h in zip(lo, hi)):
+        raise ValueError(f"bounds must be finite (lo[3], hi[3]) with hi > lo on every axis; got {bounds!r}")
+    res = tuple(int(r) for r in res)
+    check_table_size(res[0] * res[1] * res[2], sh_degree)
+    return res, tuple(lo), tuple(hi)
+
+
+def check_threshold(sigma_threshold) -> float:
+    """a finite sigma_threshold >= 0.  With a negative one, negative densities would be stored: a cell whose corners are all negative has
+    no occupancy bit (the bits mean sigma > 0) yet a non-zero trilinear sigma, and skipping it would no longer be exact."""
+    try:
+        thr = float(sigma_threshold)
+    except (TypeError, ValueError):
+        raise ValueError(f"sigma_threshold must be a number, got {sigma_threshold!r}") from None
+    if isinstance(sigma_threshold, bool) or not np.isfinite(thr) or thr < 0.0:
+        raise ValueError(f"sigma_threshold must be finite and >= 0, got {sigma_threshold!r}")
+    return thr
+
+
+def check_render_args(step, termination, outputs, sh_degree=None, lanes_per_ray=0):
+    """ValueError on step <= 0, termination outside [0, 1), unknown outputs or a lane count the degree does not have"""
+    if step is not None and not (np.isfinite(float(step)) and float(step) > 0.0):
+        raise ValueError(f"step must be a positive number or None, got {step!r}")
+    if not 0.0 <= float(termination) < 1.0:
+        raise ValueError(f"termination must lie in [0, 1), got {termination!r}")
+    outs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    if not outs or any(o not in OUTPUTS for o in outs) or len(set(outs)) != len(outs):
+        raise ValueError(f"outputs must be a non-empty selection of {OUTPUTS}, got {outputs!r}")
+    if lanes_per_ray != 0 and (sh_degree is None or lanes_per_ray not in LANES[sh_degree]):
+        raise ValueError(f"lanes_per_ray must be 0 (default) or one of {LANES.get(sh_degree)} for sh_degree {sh_degree}, got {lanes_per_ray!r}")
+    return outs
+
+
+def _stream(device):
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _check(rc, what):
+    from . import _lib
+    if rc != 0:
+        raise ValueError(f"{what} refused its arguments (KNERF_ERR_INVALID)") if rc == _lib.KNERF_ERR_INVALID else \
+            _lib.KnerfError(f"{what} failed ({rc})")
+
+
+class BakedField:
+    """A lattice of (sigma fp32, 3 K fp16 SH coefficients) records over a box plus the occupancy bits of its cells; render() marches
+    rays through it on the GPU.  Built by NeRF.bake, BakedField.from_arrays or BakedField.load."""
+
+    def __init__(self, records, words, resolution, bounds, sh_degree, sigma_threshold=0.0):
+        self._records, self._words = records, words          # uint8 [P, record bytes], int32 [ceil(cells / 32)] on the device
+        self.resolution = tuple(int(r) for r in resolution)
+        self.bounds = (tuple(float(v) for v in bounds[0]), tuple(float(v) for v in bounds[1]))
+        self.sh_degree = int(sh_degree)
+        self.sigma_threshold = float(sigma_threshold)
+        from . import _lib
+        self._c = _lib.KnerfBakedField(C.c_void_p(records.data_ptr()), C.c_void_p(words.data_ptr()), (C.c_int32 * 3)(*self.resolution),
+                                       self.sh_degree, (C.c_float * 3)(*self.bounds[0]), (C.c_float * 3)(*self.bounds[1]))
+
+    # ---- construction
+    @classmethod
+    def _empty(cls, sigma, resolution, lo, hi, sh_degree, sigma_threshold):
+        """sigma: device fp32 lattice, already thresholded.  All-zero records and the occupancy bits; _pack fills the records in."""
+        import torch
+        from .runtime import occupancy_words_from_grid
+        records = torch.zeros((int(sigma.numel()), record_bytes(sh_degree)), device=sigma.device, dtype=torch.uint8)
+        words = occupancy_words_from_grid(sigma, 0.0, 0, what="BakedField")
+        return cls(records, words, resolution, (lo, hi), sh_degree, sigma_threshold)
+
+    def _pack(self, sigma, acc, comp, index):
+        """knerf_baked_pack: the records of the points `index` (int64 [n]) from acc (+ comp) fp32 [n, K, 3]; the others keep their bytes"""
+        from . import _lib
+        from .runtime import _ptr
+        n = int(index.numel())
+        if n:
+            _check(_lib.load().knerf_baked_pack(_stream(sigma.device), _ptr(sigma), _ptr(acc), _ptr(comp), _ptr(index), n,
+                                                int(sigma.numel()), self.sh_degree, _ptr(self._records)), "knerf_baked_pack")
+
+    @classmethod
+    def from_arrays(cls, sigma, coefficients, bounds, sigma_threshold=0.0, device=None):
+        """sigma [Rx,Ry,Rz] fp32 and coefficients [Rx,Ry,Rz,K,3] fp16 / fp32 (NumPy or torch) over bounds = (lo[3], hi[3]): packs the
+        records on the device, stores every sigma <= sigma_threshold as 0 and builds the occupancy bits.  sigma_threshold >= 0: no
+        negative density is stored, so a cell without an occupancy bit has sigma = 0 at all 8 corners."""
+        import torch
+        co = coefficients if isinstance(coefficients, torch.Tensor) else torch.as_tensor(np.asarray(coefficients))
+        sg = sigma if isinstance(sigma, torch.Tensor) else torch.as_tensor(np.asarray(sigma, dtype=np.float32))
+        if sg.dim() != 3 or co.dim() != 5 or tuple(co.shape[:3]) != tuple(sg.shape) or co.shape[4] != 3 or \
+                co.shape[3] not in (1, 4, 9, 16):
+            raise ValueError(f"need sigma [Rx,Ry,Rz] and coefficients [Rx,Ry,Rz,K,3] with K = 1, 4, 9 or 16; got {tuple(sg.shape)} and "
+                             f"{tuple(co.shape)}")
+        if co.dtype not in (torch.float16, torch.float32):
+            raise ValueError(f"coefficients must be float16 or float32, got {co.dtype}")
+        deg = int(round(np.sqrt(co.shape[3]))) - 1
+        res, lo, hi = check_lattice_spec(tuple(sg.shape), bounds, deg)
+        thr = check_threshold(sigma_threshold)
+        dev = torch.device(device if device is not None else (sg.device if sg.is_cuda else "cuda"))
+        sg = sg.to(device=dev, dtype=torch.float32).contiguous()
+        sg = torch.where(sg > thr, sg, torch.zeros_like(sg))
+        field = cls._empty(sg, res, lo, hi, deg, thr)
+        K = co.shape[3]
+        co = co.reshape(-1, K, 3)
+        slab = max(1, SLAB_BYTES // (12 * K))                 # the fp32 copy of a slab's coefficients stays under about 1 GB
+        for s0 in range(0, co.shape[0], slab):
+            acc = co[s0:s0 + slab].to(device=dev, dtype=torch.float32).contiguous()
+            field._pack(sg, acc, None, torch.arange(s0, s0 + acc.shape[0], device=dev, dtype=torch.int64))
+        return field
+
+    # ---- the unpacked views
+    @property
+    def device(self):
+        return self._records.device
+
+    @property
+    def sigma(self):
+        """fp32 [Rx,Ry,Rz] (a copy out of the records)"""
+        import torch
+        return self._records[:, :4].contiguous().view(torch.float32).reshape(self.resolution)
+
+    @property
+    def coefficients(self):
+        """fp16 [Rx,Ry,Rz,K,3] (a copy out of the records)"""
+        import torch
+        K = n_coefficients(self.sh_degree)
+        return self._records[:, 4:4 + 6 * K].contiguous().view(torch.float16).reshape(self.resolution + (K, 3))
+
+    @property
+    def occupied(self):
+        """bool [Rx-1,Ry-1,Rz-1] on the device: the cells with sigma > 0 at one of their corners"""
+        return _unpack_words(self._words, tuple(r - 1 for r in self.resolution))
+
+    @property
+    def cell_size(self):
+        return tuple((np.float32(h) - np.float32(l)) / (r - 1) for l, h, r in zip(self.bounds[0], self.bounds[1], self.resolution))
+
+    # ---- persistence
+    KEYS = ("format", "records", "words", "resolution", "lo", "hi", "sh_degree", "sigma_threshold")
+
+    def save(self, path):
+        """one .npz file at exactly `path` (no suffix is appended): the records and bits as they are on the device, resolution,
+        bounds, degree, threshold"""
+        with open(path, "wb") as f:
+            np.savez(f, records=self._records.cpu().numpy(), words=self._words.cpu().numpy(),
+                     resolution=np.asarray(self.resolution, dtype=np.int32), lo=np.asarray(self.bounds[0], dtype=np.float64),
+                     hi=np.asarray(self.bounds[1], dtype=np.float64), sh_degree=np.int32(self.sh_degree),
+                     sigma_threshold=np.float64(self.sigma_threshold), format=np.int32(1))
+
+    @classmethod
+    def load(cls, path, device=None):
+        """the field save(path) wrote; ValueError on a file that is not one.  The padding of the records is never read as data."""
+        import torch
+        with np.load(path) as z:
+            missing = [k for k in cls.KEYS if k not in z.files]
+            if missing:
+                raise ValueError(f"{path}: not a baked field (missing {missing})")
+            if int(z["format"]) != 1:
+                raise ValueError(f"{path}: unknown baked-field format {int(z['format'])}")
+            deg = check_degree(int(z["sh_degree"]))
+            res, lo, hi = check_lattice_spec(tuple(int(r) for r in z["resolution"]), (z["lo"], z["hi"]), deg)
+            records, words = z["records"], z["words"]
+            n_points, cells = int(np.prod(res)), int(np.prod([r - 1 for r in res]))
+            if records.dtype != np.uint8 or records.shape != (n_points, record_bytes(deg)) or words.dtype != np.int32 or \
+                    words.shape != ((cells + 31) // 32,):
+                raise ValueError(f"{path}: records {records.shape} / bits {words.shape} do not fit a {res} lattice of degree {deg}")
+            dev = torch.device(device if device is not None else "cuda")
+            return cls(torch.as_tensor(records).to(dev), torch.as_tensor(words).to(dev), res, (lo, hi), deg, float(z["sigma_threshold"]))
+
+    # ---- rendering
+    def render(self, origins, directions, near, far, step=None, white_background=False, termination=0.0,
+               outputs=("image", "depth", "opacity"), skip_empty=True, stats=False, lanes_per_ray=0):
+        """Volume rendering of rays (origins, directions [N,3]; directions need not be unit vectors, t is in units of |d|) between
+        near and far (scalars or [N]) with samples every `step` (None: half the smallest cell edge): {"image": [N,3], "depth": [N],
+        "opacity": [N]} restricted to `outputs`, and with stats=True also "stats": int64 [2] device tensor (samples fetched, samples
+        inside [near, far] of all rays).  The march is specified in include/knerf.h (knerf_baked_render).  skip_empty only saves
+        work: the outputs are bit-identical without it.  lanes_per_ray is a tuning / diagnostic knob for tests and tools/baked_bench.py,
+        not a promised part of the interface: it picks the kernel variant (0, the default: the library's choice; the variants differ
+        in summation order only)."""
+        import torch
+        from . import _lib
+        from .runtime import _f32, _ptr
+        outs = check_render_args(step, termination, outputs, self.sh_degree, lanes_per_ray)
+        dev = self.device
+        o, d = _f32(origins, dev).reshape(-1, 3), _f32(directions, dev).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError(f"{n} origins for {d.shape[0]} directions")
+        h = float(step) if step is not None else 0.5 * float(min(self.cell_size))
+        if not np.float32(h) > 0:
+            raise ValueError(f"step {h!r} is not a positive float32")
+        ends = []
+        for name, v in (("near", near), ("far", far)):
+            if isinstance(v, (int, float, np.floating, np.integer)):
+                if not np.isfinite(np.float32(v)):
+                    raise ValueError(f"{name} must be finite, got {v!r}")
+                ends.append((None, float(v)))
+            else:
+                tv = _f32(v, dev).reshape(-1)
+                if tv.numel() != n:
+                    raise ValueError(f"{name} must be a scalar or hold one value per ray ({n}), got {tv.numel()}")
+                ends.append((tv, 0.0))
+        (near_t, near0), (far_t, far0) = ends
+        if near_t is None and far_t is None and (far0 - near0) / h >= float(1 << 23):
+            raise ValueError(f"(far - near) / step = {(far0 - near0) / h:.3g} samples per ray; at most 2^23")
+        e = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)
+        res = {"image": e(n, 3) if "image" in outs else None, "depth": e(n) if "depth" in outs else None,
+               "opacity": e(n) if "opacity" in outs else None}
+        counter = torch.zeros(2, device=dev, dtype=torch.int64) if stats else None
+        flags = (_lib.BAKED_WHITE_BACKGROUND if white_background else 0) | (_lib.BAKED_SKIP_EMPTY if skip_empty else 0) | \
+            (int(lanes_per_ray) << _lib.BAKED_LANES_SHIFT)
+        if n:
+            _check(_lib.load().knerf_baked_render(_stream(dev), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t), _ptr(far_t), near0, far0, n,
+                                                  h, float(termination), flags, _ptr(res["image"]), _ptr(res["depth"]),
+                                                  _ptr(res["opacity"]), _ptr(counter)), "knerf_baked_render")
+        out = {k: v for k, v in res.items() if v is not None}
+        if stats:
+            out["stats"] = counter
+        return out
+
+
+def _unpack_words(words, cells):
+    """device int32 words of an occupancy bitfield -> bool [cx, cy, cz] on the device"""
+    import torch
+    shifts = torch.arange(32, device=words.device, dtype=torch.int32)
+    bits = (words[:, None] >> shifts[None, :]) & 1
+    n = cells[0] * cells[1] * cells[2]
+    return bits.reshape(-1)[:n].reshape(cells).bool()
+
+
+def bake(nerf, resolution=256, bounds=((-1.5,) * 3, (1.5,) * 3), net="fine", sh_degree=2, n_directions=None, sigma_threshold=0.0,
+         slab_bytes=SLAB_BYTES):
+    """NeRF.bake: see there.  The work list is processed in slabs: accumulator and compensation of ONE slab ([slab, K, 3] fp32 each,
+    together at most slab_bytes) are summed over the directions and packed into the records before the next slab starts, so the
+    working memory does not grow with the lattice.  Nothing waits for the GPU between slabs and directions; the one host read is the
+    length of the work list.  slab_bytes is a tuning / diagnostic knob (tests force several slabs with it), not a promised part of the
+    interface."""
+    import torch
+    from .runtime import _ptr, baked_project, occupancy_words_from_grid
+    deg = check_degree(sh_degree)
+    res, lo, hi = check_lattice_spec(resolution, bounds, deg)
+    dirs, P = fit_directions(deg, n_directions)
+    thr = check_threshold(sigma_threshold)
+    if isinstance(slab_bytes, bool) or int(slab_bytes) != slab_bytes or int(slab_bytes) < 1:
+        raise ValueError(f"slab_bytes must be a positive integer, got {slab_bytes!r}")
+    n_net = nerf._field_net(net)
+    ctx = nerf._ctx
+    dev = torch.device(ctx.device)
+    K, D = P.shape
+    sigma = nerf.density_grid(res, (lo, hi), net)
+    sigma = torch.where(sigma > thr, sigma, torch.zeros_like(sigma))
+    field = BakedField._empty(sigma, res, lo, hi, deg, thr)
+    # the work list: lattice points that are a corner of an occupied cell (a cell is occupied when a corner has sigma > 0)
+    occ = field.occupied
+    touched = torch.zeros(res, device=dev, dtype=torch.bool)
+    cx, cy, cz = occ.shape
+    for a in (0, 1):
+        for b in (0, 1):
+            for c in (0, 1):
+                touched[a:a + cx, b:b + cy, c:c + cz] |= occ
+    index = touched.reshape(-1).nonzero().reshape(-1)                  # int64, ascending
+    n = int(index.numel())
+    del touched, occ
+    if n:
+        lib = ctx.lib
+        lo32 = torch.tensor(lo, device=dev, dtype=torch.float32)
+        step32 = torch.tensor([(np.float32(h) - np.float32(l)) / np.float32(r - 1) for l, h, r in zip(lo, hi, res)], device=dev,
+                              dtype=torch.float32)
+        fit = torch.as_tensor(P.astype(np.float32)).to(dev).contiguous()
+        dirs32 = torch.as_tensor(dirs.astype(np.float32)).to(dev).contiguous()
+        slab = max(1, min(n, int(slab_bytes) // ((24 if D > 1 else 12) * K)))
+        rgb = torch.empty((slab, 3), device=dev, dtype=torch.float32)
+        acc = torch.empty((slab, K, 3), device=dev, dtype=torch.float32)
+        comp = torch.empty_like(acc) if D > 1 else None            # the compensated sum over directions (knerf_baked_project)
+        for s0 in range(0, n, slab):
+            idx = index[s0:s0 + slab]
+            m = int(idx.numel())
+            ijk = torch.stack([idx // (res[1] * res[2]), (idx // res[2]) % res[1], idx % res[2]], dim=1).to(torch.float32)
+            pts = torch.add(torch.mul(ijk, step32), lo32).contiguous()          # two roundings, as knerf_query_grid places its points
+            a, e = acc[:m].zero_(), (None if comp is None else comp[:m].zero_())
+            for j in range(D):
+                dj = None if deg == 0 else dirs32[j]
+                ctx._check(lib.knerf_query_points(ctx._ctx, ctx._stream(), n_net, _ptr(pts), _ptr(dj), 0, m, None, None, _ptr(rgb)))
+                baked_project(rgb[:m], fit, j, a, e)
+            field._pack(sigma, a, e, idx)
+    return field

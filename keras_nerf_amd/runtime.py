@@ -850,3 +850,22 @@ def occupancy_decay_max(state: torch.Tensor, sigma: torch.Tensor, decay: float, 
     if rc != 0:
         raise KnerfError(f"knerf_occupancy_decay_max failed ({rc})")
     return state
+
+
+# ---- the baked field (extension: knerf_baked_project / knerf_baked_pack / knerf_baked_render; keras_nerf_amd/baked.py holds the class)
+def baked_project(rgb: torch.Tensor, fit: torch.Tensor, j: int, acc: torch.Tensor, comp: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """knerf_baked_project: acc[n,K,3] += fit[k,j] rgb[n,c] in place on the current stream (one fma per element; with comp [n,K,3] the
+    compensated sum of include/knerf.h); rgb [n,3], fit [K,D], all contiguous float32 device tensors; returns acc"""
+    for name, x in (("rgb", rgb), ("fit", fit), ("acc", acc)) + ((("comp", comp),) if comp is not None else ()):
+        if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous():
+            raise ValueError(f"baked_project: {name} must be a contiguous float32 device tensor")
+    n = rgb.shape[0]
+    if rgb.shape != (n, 3) or fit.dim() != 2 or acc.shape != (n, fit.shape[0], 3) or (comp is not None and comp.shape != acc.shape):
+        raise ValueError(f"baked_project: need rgb [n,3], fit [K,D], acc [n,K,3]; got {tuple(rgb.shape)}, {tuple(fit.shape)}, {tuple(acc.shape)}")
+    stream = C.c_void_p(torch.cuda.current_stream(acc.device).cuda_stream)
+    rc = _lib.load().knerf_baked_project(stream, _ptr(rgb), _ptr(fit), int(fit.shape[0]), int(fit.shape[1]), int(j), n, _ptr(acc), _ptr(comp))
+    if rc != 0:
+        raise ValueError(f"knerf_baked_project refused its arguments (K = {fit.shape[0]}, D = {fit.shape[1]}, j = {j})") \
+            if rc == _lib.KNERF_ERR_INVALID else KnerfError(f"knerf_baked_project failed ({rc})")
+    return acc
+
