@@ -61,20 +61,21 @@ int knerf_debug_table(int kind, int32_t* out, size_t* n) {
 
 int knerf_debug_buffer(knerf_ctx* ctx, int net, int which, void** dev, size_t* bytes) {
     if (!ctx || !dev || !bytes) return KNERF_ERR_INVALID;
+    auto view = [&](const auto& b) { *dev = b.get(); *bytes = b.bytes(); };
     switch (which) {
-        case 0: *dev = ctx->act; *bytes = ctx->act_bytes; break;
-        case 1: *dev = ctx->mask; *bytes = ctx->mask_bytes; break;
-        case 2: *dev = ctx->dz; *bytes = ctx->dz_bytes; break;
-        case 3: *dev = ctx->raw; *bytes = ctx->raw_bytes; break;
-        case 4: *dev = ctx->draw; *bytes = ctx->draw_bytes; break;      // sized by the largest TRAINING chunk (raw follows renders too)
-        case 5: *dev = ctx->t_f; *bytes = (size_t)ctx->ws_rays * (ctx->cfg.n_coarse + ctx->cfg.n_fine) * sizeof(float); break;
-        case 6: *dev = ctx->w_c; *bytes = (size_t)ctx->ws_rays * ctx->cfg.n_coarse * sizeof(float); break;
+        case 0: view(ctx->act); break;
+        case 1: view(ctx->mask); break;
+        case 2: view(ctx->dz); break;
+        case 3: view(ctx->raw); break;
+        case 4: view(ctx->draw); break;      // sized by the largest TRAINING chunk (raw follows renders too)
+        case 5: view(ctx->t_f); break;
+        case 6: view(ctx->w_c); break;
         case 7:
             if (net != 0 && net != 1) return KNERF_ERR_INVALID;
-            *dev = ctx->net[net].w; *bytes = (size_t)(ctx->generic ? ctx->n_params : ctx->si.ext_param_count) * sizeof(float); break;
+            view(ctx->net[net].w); break;
         // general-shape path (generic.h): every activation buffer [Mp][ld] bf16 / every dZ buffer of the last pass
-        case 8: *dev = ctx->gws.act; *bytes = ctx->gplan.act_elems_per_row * ctx->gws.mp * sizeof(unsigned short); break;
-        case 9: *dev = ctx->gws.dz; *bytes = ctx->gplan.dz_elems_per_row * ctx->gws.mp * sizeof(unsigned short); break;
+        case 8: view(ctx->gws_buf.act); break;
+        case 9: view(ctx->gws_buf.dz); break;
         default: return KNERF_ERR_INVALID;
     }
     // not allocated: no pass has run yet, or the buffer belongs to the fused path and this context runs the general-shape kernels

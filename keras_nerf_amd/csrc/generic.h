@@ -61,16 +61,15 @@ Plan build_plan(int n_layers, int units, int skip, int lx, int ld);
 // forward_encoded only
 Plan build_plan_widths(int n_layers, int units, int skip, int xyz_dim, int dir_dim);
 
-struct Workspace {             // per context, grow-only; Mp = padded sample count
+struct Workspace {             // per context, grow-only; Mp = padded sample count.  A view: the context owns the buffers (ctx.h)
     size_t mp = 0;
     unsigned short* act = nullptr;     // all activation buffers, buffer b at act + off_b * mp
     unsigned short* dz = nullptr;
     unsigned char* mask = nullptr;     // training workspaces only: the relu bits of every trunk layer (relu_bits_bytes; generic.hip GemmArgs)
-    float* zs = nullptr;               // (unused since the head collapse; kept so that callers' allocation code stays valid)
     float* zc = nullptr;               // [Mp][32] head pre-activations: columns r, g, b, sigma
 };
 
-struct NetDev {                // per net
+struct NetDev {                // per net (a view, as Workspace)
     unsigned short* packed = nullptr;  // packed bf16 weights (Wt and Wd of every trunk layer and of the composed head)
     float* head = nullptr;             // head_floats(plan) fp32: composed head matrix [head_K][4] in buffer-column order, bias [4],
                                        //   then scratch P [units + dir_dim][3] and Q [units][3]

@@ -90,8 +90,8 @@ int repack(knerf_ctx* ctx, int n, hipStream_t s, bool compose = true) {
         return KNERF_OK;
     }
     if (compose) HIPCHK(launch_head_compose(N.w, nullptr, ctx->si.trunk_params, ctx->si.units, ctx->si.trunk_x, ctx->si.trunk_x_slots, ctx->si.dir_dim, ctx->si.dir_slots, s));   // the composed head behind the parameters (layout.h), then the bf16 streams
-    HIPCHK(launch_pack(N.w, ctx->tab.d_fwd, reinterpret_cast<unsigned short*>(N.fwd_stream), (size_t)ctx->si.fwd_blocks * 512, s));
-    HIPCHK(launch_pack(N.w, ctx->tab.d_bwd, reinterpret_cast<unsigned short*>(N.bwd_stream), (size_t)ctx->si.bwd_blocks * 512, s));
+    HIPCHK(launch_pack(N.w, ctx->tab.d_fwd, reinterpret_cast<unsigned short*>(N.fwd_stream.get()), (size_t)ctx->si.fwd_blocks * 512, s));
+    HIPCHK(launch_pack(N.w, ctx->tab.d_bwd, reinterpret_cast<unsigned short*>(N.bwd_stream.get()), (size_t)ctx->si.bwd_blocks * 512, s));
     HIPCHK(launch_gather_f32(N.w, ctx->tab.d_bias, N.bias, (size_t)ctx->si.fwd_bias_tiles * 32, s));
     return KNERF_OK;
 }
@@ -102,29 +102,24 @@ size_t tiles_for(long long n_samples) {
     return (t + q - 1) / q * q;                  // whole workgroups (and whole layout groups, layout.h)
 }
 
+// a host table -> a device buffer of exactly its size
+hipError_t upload(DevBuf<int>& b, const std::vector<int32_t>& v) {
+    b.reset();
+    if (hipError_t e = b.grow(v.size(), nullptr)) return e;
+    return hipMemcpy(b, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+}
+
 // (re)build the wgrad plan from ctx->wgrad_cost and upload it with the jobs' workgroup offsets
 int upload_plan(knerf_ctx* ctx) {
     std::vector<int32_t> job_wg0;
     std::vector<int32_t> plan = build_wgrad_plan(ctx->n_cu, ctx->wgrad_cost, ctx->si.n_jobs, job_wg0);
-    if (ctx->tab.d_plan) { (void)hipFree(ctx->tab.d_plan); ctx->tab.d_plan = nullptr; }
-    if (ctx->d_job_wg0) { (void)hipFree(ctx->d_job_wg0); ctx->d_job_wg0 = nullptr; }
-    HIPCHK(hipMalloc(&ctx->tab.d_plan, plan.size() * sizeof(int32_t)));
-    HIPCHK(hipMemcpy(ctx->tab.d_plan, plan.data(), plan.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&ctx->d_job_wg0, job_wg0.size() * sizeof(int32_t)));
-    HIPCHK(hipMemcpy(ctx->d_job_wg0, job_wg0.data(), job_wg0.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(upload(ctx->tab.d_plan, plan));
+    HIPCHK(upload(ctx->d_job_wg0, job_wg0));
     ctx->tab.n_plan = (int)plan.size() / 4;
     ctx->plan_dirty = false;
     return KNERF_OK;
 }
 
-template <class T> void free_dev(T*& p) { if (p) { (void)hipFree(p); p = nullptr; } }
-
-// grow-only workspaces; the zero-fills are enqueued on the caller's stream `s`, the one the consuming kernels run on
-// (hipMalloc / hipFree themselves synchronise the device).
-// Inference buffers (raw, w_c, t_f, img_tmp) follow the largest chunk of ANY call; the training workspaces of the fused path
-// (draw, act / mask / dz, tile flags and lists) follow the largest TRAINING chunk and group: `group` coarse-pass regions followed
-// by one fine-pass region, so that one weight-gradient launch covers the coarse passes of a group of chunks
-// (launch_wgrad_tiles below).  A render with a larger ray_chunks therefore never re-sizes the training regions.
 // option "workspace_limit_gb": the out-of-memory paths of the callers (a merged launch or a wgrad group that does not fit) are taken
 // by a REAL failed hipMalloc -- same error code, same state of the runtime's last-error word -- without filling 288 GB first
 int over_limit(knerf_ctx* ctx, double bytes) {
@@ -148,7 +143,7 @@ OccWs occ_ws_view(char* base, long long n) {
     w.count = w.blk_off + occ_blocks(n);
     return w;
 }
-bool occ_attached(const knerf_ctx* ctx) { return ctx->occ[0].bits || ctx->occ[1].bits; }
+bool occ_attached(const knerf_ctx* ctx) { return ctx->occ[0].grid.bits || ctx->occ[1].grid.bits; }
 
 // early ray termination (options "termination_threshold" / "termination_segment"): the segment length of a pass of S samples (a
 // segment longer than the pass is the whole pass), and the fused path's workspace of a pass of R rays: ballots [term_blocks * 32]
@@ -167,138 +162,134 @@ TermWs term_ws_view(char* base, long long R, int L) {
     w.count = w.blk_off + nb;
     return w;
 }
-// the workspace for passes of up to n_rays rays with up to Na samples: the largest of the coarse and the fine pass's needs
-size_t term_ws_need(const knerf_ctx* ctx, int n_rays) {
-    const size_t c = term_ws_bytes(n_rays, term_segment(ctx, ctx->cfg.n_coarse));
-    const size_t f = term_ws_bytes(n_rays, term_segment(ctx, ctx->cfg.n_coarse + ctx->cfg.n_fine));
-    return c > f ? c : f;
-}
 // training behind the grids (option "occupancy_train"): for one net / for either net
-bool occ_train_on(const knerf_ctx* ctx, int net) { return ctx->occ_train && ctx->occ[net].bits; }
+bool occ_train_on(const knerf_ctx* ctx, int net) { return ctx->occ_train && ctx->occ[net].grid.bits; }
 bool occ_train_any(const knerf_ctx* ctx) { return ctx->occ_train && occ_attached(ctx); }
 
+// the view of the general-shape path's buffers that generic.hip takes
+gen::Workspace gen_view(const GenWsBufs& b, size_t mp) { return gen::Workspace{mp, b.act, b.dz, b.mask, b.zc}; }
+
+// Every buffer size of passes of up to R rays, as element counts of the buffers' own types: the one place that knows them (pure host
+// arithmetic on the configuration).  Training buffers of the fused path hold `group` coarse-pass regions followed by one fine-pass
+// region, so that one weight-gradient launch covers the coarse passes of a group of chunks (launch_wgrad_tiles below); group 1: the
+// coarse and the fine pass of a chunk share one region (each pass's weight gradients follow it at once).
+struct WsSizes {
+    size_t raw, w_c, t_f, img_tmp;             // inference buffers
+    size_t tiles_c, tiles;                     // sample tiles of one coarse region / of all regions of the training workspaces
+    size_t draw, loss_partial;                 // loss_partial: the loss, then the objective's four terms (composite_ext.h)
+    size_t act, mask, dz, tile_list_g;         // fused path: saved regions (bytes); the list of a group of coarse passes (group > 1)
+    size_t mp, g_act, g_zc, g_dz, g_mask;      // general-shape path (generic.h): padded rows and its forward / training buffers
+    size_t occ_ws, occ_c;                      // compaction workspace; each of the compacted raw and dL/draw
+    size_t term_ws;                            // the largest of the coarse and the fine pass's needs
+    // (tile_flags and tile_list hold `tiles` ints each)
+    double base_bytes(bool generic) const { return 4.0 * (raw + w_c + t_f + img_tmp) + (generic ? 2.0 * g_act + 4.0 * g_zc : 0.0); }
+    double train_bytes(bool generic) const {
+        return 4.0 * (draw + loss_partial + 2 * tiles) + (generic ? 2.0 * g_dz + (double)g_mask : (double)act + mask + dz + 4.0 * tile_list_g);
+    }
+};
+WsSizes ws_sizes(const knerf_ctx* ctx, int R, int group = 1) {
+    const size_t Nc = (size_t)ctx->cfg.n_coarse, Na = Nc + ctx->cfg.n_fine, ns = (size_t)R * Na;
+    WsSizes z{};
+    z.raw = ns * 4; z.w_c = (size_t)R * Nc; z.t_f = ns; z.img_tmp = (size_t)R * 8;
+    z.tiles_c = tiles_for((long long)((size_t)R * Nc));
+    z.tiles = group == 1 ? tiles_for((long long)ns) : (size_t)group * z.tiles_c + tiles_for((long long)ns);
+    z.draw = ns * 4; z.loss_partial = 5 * (((size_t)R + 3) / 4);
+    if (ctx->generic) {
+        z.mp = gen::padded_rows((long long)ns);
+        z.g_act = ctx->gplan.act_elems_per_row * z.mp; z.g_zc = z.mp * 32;
+        z.g_dz = ctx->gplan.dz_elems_per_row * z.mp; z.g_mask = gen::relu_bits_bytes(ctx->gplan, z.mp);
+    } else {
+        z.act = saved_region_bytes(z.tiles, ctx->si.act_blocks); z.mask = saved_region_bytes(z.tiles, ctx->si.mask_blocks);
+        z.dz = saved_region_bytes(z.tiles, ctx->si.dz_blocks);
+        z.tile_list_g = group > 1 ? (size_t)group * z.tiles_c : 0;
+    }
+    z.occ_ws = occ_ws_bytes((long long)ns); z.occ_c = ns * 4;
+    const size_t tc = term_ws_bytes(R, term_segment(ctx, (int)Nc)), tf = term_ws_bytes(R, term_segment(ctx, (int)Na));
+    z.term_ws = tc > tf ? tc : tf;
+    return z;
+}
+
+// grow-only workspaces; the zero-fills are enqueued on the caller's stream `s`, the one the consuming kernels run on
+// (hipMalloc / hipFree themselves synchronise the device).
+// Inference buffers (raw, w_c, t_f, img_tmp) follow the largest chunk of ANY call; the training workspaces of the fused path
+// (draw, act / mask / dz, tile flags and lists) follow the largest TRAINING chunk and group, so that a render with a larger
+// ray_chunks never re-sizes the training regions.  The general-shape path keeps one size for everything (its activations are forward
+// buffers too).  Each group of buffers gives its memory back before it is allocated again, and its policy counter (ws_rays, ws_train,
+// ws_occ_rays, ...) reads 0 until every buffer of the group is there: after a failed allocation the next call re-sizes the whole group.
 int ensure_ws_impl(knerf_ctx* ctx, int n_rays, bool train, hipStream_t s, int group) {
-    const int Na = ctx->cfg.n_coarse + ctx->cfg.n_fine;
-    if (ctx->generic) {          // general-shape path: one size for everything (its activations are forward buffers too)
+    const bool generic = ctx->generic;
+    bool grow_base, grow_train, grow_occ = false, grow_occ_train = false, grow_term = false;
+    int R = n_rays > ctx->ws_train_rays ? n_rays : ctx->ws_train_rays;          // the training buffers' size
+    if (generic) {
         if (n_rays <= ctx->ws_rays && (!train || ctx->ws_train)) return KNERF_OK;
-        const int R = n_rays > ctx->ws_rays ? n_rays : ctx->ws_rays;
-        train = train || ctx->ws_train;
-        {
-            const double mp = (double)gen::padded_rows((long long)R * Na);
-            if (int r = over_limit(ctx, (double)R * Na * 20 + mp * 256 + 2.0 * ctx->gplan.act_elems_per_row * mp +
-                                            (train ? 2.0 * ctx->gplan.dz_elems_per_row * mp + (double)R * Na * 16 : 0.0))) return r;
-        }
-        HIPCHK(hipStreamSynchronize(s));           // nothing enqueued earlier may still use the buffers that are freed below
-        free_dev(ctx->raw); free_dev(ctx->draw); free_dev(ctx->w_c); free_dev(ctx->t_f); free_dev(ctx->img_tmp);
-        ctx->ws_rays = 0;
-        const size_t ns = (size_t)R * Na;
-        ctx->raw_bytes = ns * 4 * sizeof(float);
-        HIPCHK(hipMalloc(&ctx->raw, ctx->raw_bytes));
-        HIPCHK(hipMalloc(&ctx->w_c, (size_t)R * ctx->cfg.n_coarse * sizeof(float)));
-        HIPCHK(hipMalloc(&ctx->t_f, ns * sizeof(float)));
-        HIPCHK(hipMalloc(&ctx->img_tmp, (size_t)R * 8 * sizeof(float)));
-        gen::Workspace& g = ctx->gws;
-        free_dev(g.act); free_dev(g.dz); free_dev(g.zs); free_dev(g.zc); free_dev(g.mask);
-        g.mp = gen::padded_rows((long long)ns);
-        const size_t ab = ctx->gplan.act_elems_per_row * g.mp * sizeof(unsigned short), zb = ctx->gplan.dz_elems_per_row * g.mp * sizeof(unsigned short);
-        HIPCHK(hipMalloc(&g.act, ab));
-        HIPCHK(hipMemsetAsync(g.act, 0, ab, s));
-        HIPCHK(hipMalloc(&g.zs, g.mp * 32 * sizeof(float)));
-        HIPCHK(hipMalloc(&g.zc, g.mp * 32 * sizeof(float)));
-        if (train) {
-            HIPCHK(hipMalloc(&g.dz, zb));
-            HIPCHK(hipMemsetAsync(g.dz, 0, zb, s));
-            HIPCHK(hipMalloc(&g.mask, gen::relu_bits_bytes(ctx->gplan, g.mp)));
-            HIPCHK(hipMalloc(&ctx->draw, ctx->raw_bytes));
-            ctx->draw_bytes = ctx->raw_bytes;
-            free_dev(ctx->loss_partial);
-            HIPCHK(hipMalloc(&ctx->loss_partial, 5 * (((size_t)R + 3) / 4) * sizeof(float)));     // the loss, then the objective's four terms (composite_ext.h)
-            // dead-tile skipping: per-tile flags (deterministic mode) and the list of live tiles of the current pass
-            free_dev(ctx->tile_flags); free_dev(ctx->tile_list);
-            const size_t tiles = tiles_for((long long)ns);
-            HIPCHK(hipMalloc(&ctx->tile_flags, tiles * sizeof(int)));
-            HIPCHK(hipMemsetAsync(ctx->tile_flags, 0, tiles * sizeof(int), s));
-            HIPCHK(hipMalloc(&ctx->tile_list, tiles * sizeof(int)));
-            ctx->ws_tiles = tiles;
-        }
-        ctx->ws_rays = R; ctx->ws_train = train; ctx->ws_train_rays = train ? R : 0; ctx->ws_group = 1;
-        return KNERF_OK;
+        R = n_rays = n_rays > ctx->ws_rays ? n_rays : ctx->ws_rays;
+        grow_base = true; grow_train = train || ctx->ws_train; group = 1;
+    } else {
+        grow_base = n_rays > ctx->ws_rays;
+        grow_train = train && (!ctx->ws_train || n_rays > ctx->ws_train_rays || group > ctx->ws_group);
+        // renders behind an occupancy grid: the compaction workspace (4 B + 1 bit per sample), only while a grid is attached; training
+        // behind one ("occupancy_train"): the same at the training size, and the compacted raw / dL/draw (32 B per sample)
+        const bool occ_tr = train && occ_train_any(ctx);
+        grow_occ = (train ? occ_tr : occ_attached(ctx)) && n_rays > ctx->ws_occ_rays;
+        grow_occ_train = occ_tr && n_rays > ctx->ws_occ_train_rays;
     }
-    const bool grow_base = n_rays > ctx->ws_rays;
-    const bool grow_train = train && (!ctx->ws_train || n_rays > ctx->ws_train_rays || group > ctx->ws_group);
-    // renders behind an occupancy grid: the compaction workspace (4 B + 1 bit per sample), only while a grid is attached; training
-    // behind one ("occupancy_train"): the same at the training size, and the compacted raw / dL/draw (32 B per sample)
-    const bool occ_tr = train && occ_train_any(ctx);
-    const bool grow_occ = (train ? occ_tr : occ_attached(ctx)) && n_rays > ctx->ws_occ_rays;
-    const bool grow_occ_train = occ_tr && n_rays > ctx->ws_occ_train_rays;
+    const WsSizes z = ws_sizes(ctx, n_rays), zt = ws_sizes(ctx, R, group);
     // renders with early ray termination ("termination_threshold" > 0): T, the segment's ballots, counts and list (about 4 L + 8 bytes per ray)
-    const size_t term_b = !train && ctx->term_eps > 0 ? term_ws_need(ctx, n_rays) : 0;
-    const bool grow_term = term_b > ctx->term_ws_bytes;
+    if (!generic) grow_term = !train && ctx->term_eps > 0 && z.term_ws > ctx->term_ws.size();
     if (!grow_base && !grow_train && !grow_occ && !grow_occ_train && !grow_term) return KNERF_OK;
-    if (ctx->ws_limit_gb > 0) {
-        const int Rt = n_rays > ctx->ws_train_rays ? n_rays : ctx->ws_train_rays;
-        const size_t tl = group == 1 ? tiles_for((long long)Rt * Na) : (size_t)group * tiles_for((long long)Rt * ctx->cfg.n_coarse) + tiles_for((long long)Rt * Na);
-        const double base_b = grow_base ? (double)n_rays * Na * 20 + (double)n_rays * (ctx->cfg.n_coarse * 4 + 32) : 0.0;
-        const double train_b = grow_train ? (double)Rt * Na * 16 + (double)saved_region_bytes(tl, ctx->si.act_blocks) +
-                                                (double)saved_region_bytes(tl, ctx->si.mask_blocks) + (double)saved_region_bytes(tl, ctx->si.dz_blocks) : 0.0;
-        const double occ_b = (grow_occ ? (double)occ_ws_bytes((long long)n_rays * Na) : 0.0) + (grow_occ_train ? (double)n_rays * Na * 32 : 0.0);
-        if (int r = over_limit(ctx, base_b + train_b + occ_b + (grow_term ? (double)term_b : 0.0))) return r;
-    }
+    // the sum of what is about to be requested (tile flags, tile lists and loss partials included; the general-shape path no longer
+    // counts the head buffer it used to allocate without reading it)
+    if (int r = over_limit(ctx, (grow_base ? z.base_bytes(generic) : 0.0) + (grow_train ? zt.train_bytes(generic) : 0.0) + (grow_occ ? (double)z.occ_ws : 0.0) +
+                                    (grow_occ_train ? 8.0 * z.occ_c : 0.0) + (grow_term ? (double)z.term_ws : 0.0))) return r;
     HIPCHK(hipStreamSynchronize(s));               // nothing enqueued earlier may still use the buffers that are freed below
     if (grow_base) {
-        free_dev(ctx->raw); free_dev(ctx->w_c); free_dev(ctx->t_f); free_dev(ctx->img_tmp);
-        ctx->ws_rays = 0;
-        const size_t ns = (size_t)n_rays * Na;
-        ctx->raw_bytes = ns * 4 * sizeof(float);
-        HIPCHK(hipMalloc(&ctx->raw, ctx->raw_bytes));
-        HIPCHK(hipMalloc(&ctx->w_c, (size_t)n_rays * ctx->cfg.n_coarse * sizeof(float)));
-        HIPCHK(hipMalloc(&ctx->t_f, ns * sizeof(float)));
-        HIPCHK(hipMalloc(&ctx->img_tmp, (size_t)n_rays * 8 * sizeof(float)));
+        release(ctx->raw, ctx->w_c, ctx->t_f, ctx->img_tmp, ctx->gws_buf.act, ctx->gws_buf.zc);
+        if (generic) release(ctx->draw, ctx->gws_buf.dz, ctx->gws_buf.mask);      // one size for everything: these follow below
+        ctx->ws_rays = 0; ctx->gws = gen::Workspace{};
+        HIPCHK(ctx->raw.grow(z.raw, s));
+        HIPCHK(ctx->w_c.grow(z.w_c, s));
+        HIPCHK(ctx->t_f.grow(z.t_f, s));
+        HIPCHK(ctx->img_tmp.grow(z.img_tmp, s));
+        if (generic) {
+            HIPCHK(ctx->gws_buf.act.grow(z.g_act, s, true));
+            HIPCHK(ctx->gws_buf.zc.grow(z.g_zc, s));
+            ctx->gws = gen_view(ctx->gws_buf, z.mp);
+        }
         ctx->ws_rays = n_rays;
     }
     if (grow_occ) {
-        free_dev(ctx->occ_ws);
         ctx->ws_occ_rays = 0;
-        HIPCHK(hipMalloc(&ctx->occ_ws, occ_ws_bytes((long long)n_rays * Na)));
+        release(ctx->occ_ws);
+        HIPCHK(ctx->occ_ws.grow(z.occ_ws, s));
         ctx->ws_occ_rays = n_rays;
     }
-    if (grow_term) {
-        free_dev(ctx->term_ws);
-        ctx->term_ws_bytes = 0;
-        HIPCHK(hipMalloc(&ctx->term_ws, term_b));
-        ctx->term_ws_bytes = term_b;
-    }
+    if (grow_term) HIPCHK(ctx->term_ws.grow(z.term_ws, s));
     if (grow_occ_train) {
-        free_dev(ctx->occ_raw_c); free_dev(ctx->occ_draw_c);
         ctx->ws_occ_train_rays = 0;
-        HIPCHK(hipMalloc(&ctx->occ_raw_c, (size_t)n_rays * Na * 4 * sizeof(float)));
-        HIPCHK(hipMalloc(&ctx->occ_draw_c, (size_t)n_rays * Na * 4 * sizeof(float)));
+        release(ctx->occ_raw_c, ctx->occ_draw_c);
+        HIPCHK(ctx->occ_raw_c.grow(z.occ_c, s));
+        HIPCHK(ctx->occ_draw_c.grow(z.occ_c, s));
         ctx->ws_occ_train_rays = n_rays;
     }
     if (grow_train) {
-        const int R = n_rays > ctx->ws_train_rays ? n_rays : ctx->ws_train_rays;
-        if (group < ctx->ws_group && n_rays <= ctx->ws_train_rays) group = ctx->ws_group;   // a larger chunk size starts from the group asked for: group x size is what costs memory
-        free_dev(ctx->draw); free_dev(ctx->act); free_dev(ctx->mask); free_dev(ctx->dz);
-        free_dev(ctx->tile_flags); free_dev(ctx->tile_list); free_dev(ctx->tile_list_g); free_dev(ctx->loss_partial);
+        release(ctx->draw, ctx->act, ctx->mask, ctx->dz, ctx->gws_buf.dz, ctx->gws_buf.mask);
+        release(ctx->tile_flags, ctx->tile_list, ctx->tile_list_g, ctx->loss_partial);
         ctx->ws_train = false; ctx->ws_train_rays = 0; ctx->ws_group = 1; ctx->group_cache = 0;
-        const size_t ns = (size_t)R * Na;
-        // group 1: the coarse and the fine pass of a chunk share one region (each pass's weight gradients follow it at once)
-        const size_t tiles = group == 1 ? tiles_for((long long)ns) : (size_t)group * tiles_for((long long)R * ctx->cfg.n_coarse) + tiles_for((long long)ns);
-        ctx->act_bytes = saved_region_bytes(tiles, ctx->si.act_blocks); ctx->mask_bytes = saved_region_bytes(tiles, ctx->si.mask_blocks);
-        ctx->dz_bytes = saved_region_bytes(tiles, ctx->si.dz_blocks);
-        ctx->draw_bytes = ns * 4 * sizeof(float);
-        HIPCHK(hipMalloc(&ctx->draw, ctx->draw_bytes));
-        HIPCHK(hipMalloc(&ctx->act, ctx->act_bytes));
-        HIPCHK(hipMalloc(&ctx->mask, ctx->mask_bytes));
-        HIPCHK(hipMalloc(&ctx->dz, ctx->dz_bytes));
-        HIPCHK(hipMemsetAsync(ctx->dz, 0, ctx->dz_bytes, s));     // block kDzHead+1 is never written and must read 0
-        HIPCHK(hipMemsetAsync(ctx->act, 0, ctx->act_bytes, s));
-        HIPCHK(hipMalloc(&ctx->tile_flags, tiles * sizeof(int)));
-        HIPCHK(hipMemsetAsync(ctx->tile_flags, 0, tiles * sizeof(int), s));
-        HIPCHK(hipMalloc(&ctx->tile_list, tiles * sizeof(int)));
-        if (group > 1) HIPCHK(hipMalloc(&ctx->tile_list_g, (size_t)group * tiles_for((long long)R * ctx->cfg.n_coarse) * sizeof(int)));
-        HIPCHK(hipMalloc(&ctx->loss_partial, 5 * (((size_t)R + 3) / 4) * sizeof(float)));     // the loss, then the objective's four terms (composite_ext.h)
-        ctx->ws_tiles = tiles;
+        HIPCHK(ctx->draw.grow(zt.draw, s));
+        if (generic) {
+            HIPCHK(ctx->gws_buf.dz.grow(zt.g_dz, s, true));
+            HIPCHK(ctx->gws_buf.mask.grow(zt.g_mask, s));
+        } else {
+            HIPCHK(ctx->act.grow(zt.act, s, true));
+            HIPCHK(ctx->mask.grow(zt.mask, s));
+            HIPCHK(ctx->dz.grow(zt.dz, s, true));                     // block kDzHead+1 is never written and must read 0
+        }
+        // dead-tile skipping: per-tile flags (deterministic mode) and the list of live tiles of the current pass
+        HIPCHK(ctx->tile_flags.grow(zt.tiles, s, true));
+        HIPCHK(ctx->tile_list.grow(zt.tiles, s));
+        HIPCHK(ctx->tile_list_g.grow(zt.tile_list_g, s));
+        HIPCHK(ctx->loss_partial.grow(zt.loss_partial, s));
+        if (generic) ctx->gws = gen_view(ctx->gws_buf, zt.mp);
         ctx->ws_train = true; ctx->ws_train_rays = R; ctx->ws_group = group;
     }
     return KNERF_OK;
@@ -350,8 +341,8 @@ bool skipping(const knerf_ctx* ctx) {
 // A fresh (zero) counter for one list of live tiles.  The ring is zeroed by one memset when a call takes its first counter, and again
 // if a call runs through the whole ring (the consumers of its earlier counters are enqueued by then; the stream orders the memset).
 int next_tile_counter(knerf_ctx* ctx, hipStream_t s, int** count) {
-    if (ctx->tile_counter_next >= ctx->tile_counters) ctx->tile_counter_next = 0;     // not reached by the entry points: they size the ring first
-    if (ctx->tile_counter_next == 0) HIPCHK(hipMemsetAsync(ctx->tile_count, 0, (size_t)ctx->tile_counters * sizeof(int), s));
+    if (ctx->tile_counter_next >= (int)ctx->tile_count.size()) ctx->tile_counter_next = 0;     // not reached by the entry points: they size the ring first
+    if (ctx->tile_counter_next == 0) HIPCHK(hipMemsetAsync(ctx->tile_count, 0, ctx->tile_count.bytes(), s));
     *count = ctx->tile_count + ctx->tile_counter_next++;
     return KNERF_OK;
 }
@@ -359,13 +350,11 @@ int next_tile_counter(knerf_ctx* ctx, hipStream_t s, int** count) {
 // The ring holds every counter one call takes (grow-only): a wrap inside a call would zero a group's counter that later coarse
 // passes still append to, and the grouped weight-gradient launch would then see a short list.
 int ensure_tile_counters(knerf_ctx* ctx, hipStream_t s, long long need) {
-    if (need <= ctx->tile_counters) return KNERF_OK;
-    HIPCHK(hipStreamSynchronize(s));               // consumers of the old ring's counters have finished
-    free_dev(ctx->tile_count);
-    long long n = ctx->tile_counters;
+    if (need <= (long long)ctx->tile_count.size()) return KNERF_OK;
+    long long n = knerf_ctx::kTileCounters;
     while (n < need) n *= 2;
-    HIPCHK(hipMalloc(&ctx->tile_count, (size_t)n * sizeof(int)));
-    ctx->tile_counters = (int)n; ctx->tile_counter_next = 0;
+    HIPCHK(ctx->tile_count.grow((size_t)n, s));    // (behind a synchronise: consumers of the old ring's counters have finished)
+    ctx->tile_counter_next = 0;
     return KNERF_OK;
 }
 
@@ -386,48 +375,71 @@ int launch_wgrad_tiles(knerf_ctx* ctx, hipStream_t s, int net, size_t tile0, siz
     wa.grad = ctx->net[net].g; wa.aux = ctx->net[net].aux; wa.dst = ctx->tab.d_wgrad;
     wa.fwd_stream = ctx->net[net].fwd_stream; wa.bias = ctx->net[net].bias; wa.bwd_stream = ctx->net[net].bwd_stream;
     wa.n_tiles = (long long)n_tiles;
-    wa.plan = ctx->tab.d_plan; wa.n_plan = ctx->tab.n_plan; wa.net = net == KNERF_COARSE ? 0 : 1;
+    wa.plan = ctx->tab.d_plan; wa.n_plan = ctx->tab.n_plan; wa.net = net;
     for (int j = 0; j <= ctx->si.n_jobs; ++j) wa.job_off[j] = ctx->tab.wgrad_off[j];
     if (live) { wa.live = live; wa.n_live = live_count; wa.by_range = ctx->deterministic ? 1 : 0; }
-    wa.stats = ctx->tile_stats + 4 * (net == KNERF_COARSE ? 0 : 1);
+    wa.stats = ctx->tile_stats + 4 * net;
     if (ctx->deterministic) {
         // per-workgroup slabs (zeroed: a workgroup without tiles writes nothing) + the ordered second pass
-        if (!ctx->partial || ctx->partial_plan != ctx->tab.n_plan) {
-            HIPCHK(hipStreamSynchronize(s));
-            free_dev(ctx->partial);
-            HIPCHK(hipMalloc(&ctx->partial, wgrad_partial_floats(ctx->tab.n_plan, ctx->si.partial_stride) * sizeof(float)));
-            ctx->partial_plan = ctx->tab.n_plan;
-        }
-        HIPCHK(hipMemsetAsync(ctx->partial, 0, wgrad_partial_floats(ctx->tab.n_plan, ctx->si.partial_stride) * sizeof(float), s));
+        const size_t slabs = wgrad_partial_floats(ctx->tab.n_plan, ctx->si.partial_stride);
+        HIPCHK(ctx->partial.grow(slabs, s));
+        HIPCHK(hipMemsetAsync(ctx->partial, 0, slabs * sizeof(float), s));
         wa.partial = ctx->partial;
     }
-    ProfScope ps(ctx, s, net == KNERF_COARSE ? P_WGRAD_C : P_WGRAD_F);
+    ProfScope ps(ctx, s, P_WGRAD_C + net);
     HIPCHK(launch_wgrad(wa, s));
     if (ctx->deterministic) HIPCHK(launch_wgrad_reduce(wa, ctx->d_job_wg0, ctx->si.partial_stride, s));
     return KNERF_OK;
 }
 
-// tile0: first tile of this pass in the training workspaces; wgrad_now: launch the weight-gradient kernel for just this pass
-// (false: the caller launches it later over several passes, launch_wgrad_tiles)
-// group_count: (default-mode skipping, coarse pass of a grouped launch) the group's counter: the pass's live tiles are appended to
-// ctx->tile_list_g as well, as indices relative to the group's first region (+ tile0)
-// render: a pass of knerf_render_chunk -- the net's occupancy grid, if one is attached, applies; to training passes only under option
-// "occupancy_train" (never to forward_chunk or queries)
-int run_pass(knerf_ctx* ctx, hipStream_t s, int net, const float* o, const float* d, const float* t, int R, int S,
-             float* image, float* depth, float* weights, const float* target, float inv_chunks, float* loss,
-             size_t tile0 = 0, bool wgrad_now = true, int* group_count = nullptr, bool render = false) {
-    const bool train = target != nullptr;
-    const knerf_ctx::Occ* og = ((render && !train) || (train && occ_train_on(ctx, net))) && ctx->occ[net].bits ? &ctx->occ[net] : nullptr;
+// One pass of one net over R rays of S samples.  target set: a training pass (loss, dL/draw, dgrad and, with wgrad_now, its weight gradients).
+static_assert(KNERF_COARSE == 0 && KNERF_FINE == 1 && P_FWD_F == P_FWD_C + 1 && P_BWD_F == P_BWD_C + 1 && P_WGRAD_F == P_WGRAD_C + 1,
+              "the net is the index of its stats words, objective bit and profile class");
+struct Pass {
+    int net;
+    const float *o, *d, *t;                 // [R,3], [R,3], [R,S]
+    int R, S;
+    float *image = nullptr, *depth = nullptr, *weights = nullptr;
+    const float* target = nullptr;
+    float inv_chunks = 1.f;
+    float* loss = nullptr;
+    size_t tile0 = 0;                       // first tile of this pass in the training workspaces
+    bool wgrad_now = true;                  // false: the caller launches the weight gradients later over several passes (launch_wgrad_tiles)
+    // (default-mode skipping, coarse pass of a grouped launch) the group's counter: the pass's live tiles are appended to
+    // ctx->tile_list_g as well, as indices relative to the group's first region (+ tile0)
+    int* group_count = nullptr;
+    // a pass of knerf_render_chunk -- the net's occupancy grid, if one is attached, applies; to training passes only under option
+    // "occupancy_train" (never to forward_chunk or queries)
+    bool render = false;
+};
+
+// the lists of a compaction workspace (OccWs / TermWs) as the mark kernels take them
+template <class Args, class Ws>
+void take_lists(Args& a, const Ws& w) { a.masks = w.masks; a.blk_cnt = w.blk_cnt; a.blk_off = w.blk_off; a.list = w.list; a.count = w.count; }
+
+// the fused MLP on a list of live samples of the pass (query.hip list mode); the caller sets n
+QueryArgs list_query(const knerf_ctx* ctx, const Pass& p, const int* list, const int* count) {
+    QueryArgs q{};
+    q.stream = ctx->net[p.net].fwd_stream; q.bias = ctx->net[p.net].bias; q.shape = ctx->shape;
+    q.raw = ctx->raw; q.list = list; q.count = count; q.o = p.o; q.d = p.d; q.t = p.t; q.S = p.S;
+    return q;
+}
+
+int run_pass(knerf_ctx* ctx, hipStream_t s, const Pass& p) {
+    const int net = p.net, R = p.R, S = p.S;
+    const float *o = p.o, *d = p.d, *t = p.t;
+    const size_t tile0 = p.tile0;
+    const bool train = p.target != nullptr;
+    const OccGrid* og = ((p.render && !train) || (train && occ_train_on(ctx, net))) && ctx->occ[net].grid.bits ? &ctx->occ[net].grid : nullptr;
     // fused training behind a grid: forward, dgrad and weight gradients on the compacted list of live samples (train_list.h)
     const bool compact = og && train && !ctx->generic;
     // early ray termination: render passes only, while "termination_threshold" > 0 (termination.h)
-    const bool term = render && !train && ctx->term_eps > 0;
+    const bool term = p.render && !train && ctx->term_eps > 0;
     OccArgs oa{};
     if (og) {
-        oa.grid.bits = og->bits; oa.grid.outside_empty = og->outside_empty;
-        for (int c = 0; c < 3; ++c) { oa.grid.cells[c] = og->cells[c]; oa.grid.lo[c] = og->lo[c]; oa.grid.scale[c] = og->scale[c]; }
+        oa.grid = *og;
         oa.o = o; oa.d = d; oa.t = t; oa.n = (long long)R * S; oa.S = S; oa.raw = ctx->raw;
-        oa.stats = (train ? ctx->occ_train_stats : ctx->occ_stats) + 2 * (net == KNERF_COARSE ? 0 : 1);
+        oa.stats = (train ? ctx->occ_train_stats : ctx->occ_stats) + 2 * net;
         if (!ctx->generic && oa.n >= (1ll << 31))       // the list holds int32 sample indices
             return fail(ctx, KNERF_ERR_INVALID, "pass behind an occupancy grid: a pass of 2^31 samples or more (use a smaller ray_chunks)");
     }
@@ -435,7 +447,7 @@ int run_pass(knerf_ctx* ctx, hipStream_t s, int net, const float* o, const float
     if (term) {
         if (og) { ta.grid = oa.grid; ta.has_grid = 1; ta.occ_stats = oa.stats; }
         ta.o = o; ta.d = d; ta.t = t; ta.raw = ctx->raw; ta.R = R; ta.S = S; ta.L = term_segment(ctx, S); ta.eps = (float)ctx->term_eps;
-        ta.stats = ctx->term_stats + 2 * (net == KNERF_COARSE ? 0 : 1);
+        ta.stats = ctx->term_stats + 2 * net;
         if (!ctx->generic && (long long)R * S >= (1ll << 31))       // the list holds int32 sample indices
             return fail(ctx, KNERF_ERR_INVALID, "pass with early ray termination: a pass of 2^31 samples or more (use a smaller ray_chunks)");
     }
@@ -444,86 +456,80 @@ int run_pass(knerf_ctx* ctx, hipStream_t s, int net, const float* o, const float
     fa.o = o; fa.d = d; fa.t = t; fa.raw = ctx->raw;
     fa.act = ctx->act ? ctx->act + saved_tile_off(tile0, ctx->si.act_blocks) : nullptr;
     fa.mask = ctx->mask ? ctx->mask + saved_tile_off(tile0, ctx->si.mask_blocks) : nullptr;
-    fa.n_samples = (long long)R * S; fa.S = S; fa.net = net == KNERF_COARSE ? 0 : 1; fa.shape = ctx->shape;
-    if (ctx->generic) {
-        ProfScope ps(ctx, s, net == KNERF_COARSE ? P_FWD_C : P_FWD_F);
-        HIPCHK(gen::forward(ctx->gplan, ctx->gws, ctx->gnet[net], ctx->net[net].w, o, d, t, fa.n_samples, S, ctx->raw, s));
-        // general-shape path: the MLP ran on every sample; the dead ones are zeroed behind it (same outputs, no speed-up)
-        if (og) HIPCHK(launch_occupancy_mark(oa, s));
-        // ... and the terminated ones behind the dead ones, by the same cut rule
-        if (term) HIPCHK(launch_termination_walk(ta, s));
-    } else if (compact) {
-        // fused training: ordered compaction of the live samples, then the SAVE forward on the list alone; saved tensors of compacted
-        // tile i / 32, raw to raw[list[i]]
-        ProfScope ps(ctx, s, net == KNERF_COARSE ? P_FWD_C : P_FWD_F);
-        const OccWs w = occ_ws_view(ctx->occ_ws, oa.n);
-        oa.masks = w.masks; oa.blk_cnt = w.blk_cnt; oa.blk_off = w.blk_off; oa.list = w.list; oa.count = w.count;
-        HIPCHK(launch_occupancy_mark(oa, s));
-        TrainListArgs la{};
-        la.f = fa; la.list = w.list; la.count = w.count;
-        HIPCHK(launch_mlp_fwd_list(la, s));
-    } else if (term) {
-        // fused path with early ray termination: one round per segment -- fold the previous segment into T, cut, grid, ordered
-        // compaction of the segment's live samples -- then the fused MLP on that list; no host synchronisation between rounds
-        ProfScope ps(ctx, s, net == KNERF_COARSE ? P_FWD_C : P_FWD_F);
-        const TermWs w = term_ws_view(ctx->term_ws, R, ta.L);
-        ta.T = w.T; ta.masks = w.masks; ta.blk_cnt = w.blk_cnt; ta.blk_off = w.blk_off; ta.list = w.list; ta.count = w.count;
-        QueryArgs q{};
-        q.stream = ctx->net[net].fwd_stream; q.bias = ctx->net[net].bias; q.shape = ctx->shape;
-        q.raw = ctx->raw; q.list = w.list; q.count = w.count; q.o = o; q.d = d; q.t = t; q.S = S;
-        for (int k = 0; k * ta.L < S; ++k) {
-            ta.k = k;
-            HIPCHK(launch_termination_round(ta, s));
-            const int Lk = S - k * ta.L < ta.L ? S - k * ta.L : ta.L;
-            q.n = (long long)R * Lk;
+    fa.n_samples = (long long)R * S; fa.S = S; fa.net = net; fa.shape = ctx->shape;
+    {
+        ProfScope ps(ctx, s, P_FWD_C + net);
+        if (ctx->generic) {
+            HIPCHK(gen::forward(ctx->gplan, ctx->gws, ctx->gnet[net], ctx->net[net].w, o, d, t, fa.n_samples, S, ctx->raw, s));
+            // general-shape path: the MLP ran on every sample; the dead ones are zeroed behind it (same outputs, no speed-up)
+            if (og) HIPCHK(launch_occupancy_mark(oa, s));
+            // ... and the terminated ones behind the dead ones, by the same cut rule
+            if (term) HIPCHK(launch_termination_walk(ta, s));
+        } else if (compact) {
+            // fused training: ordered compaction of the live samples, then the SAVE forward on the list alone; saved tensors of compacted
+            // tile i / 32, raw to raw[list[i]]
+            take_lists(oa, occ_ws_view(ctx->occ_ws, oa.n));
+            HIPCHK(launch_occupancy_mark(oa, s));
+            TrainListArgs la{};
+            la.f = fa; la.list = oa.list; la.count = oa.count;
+            HIPCHK(launch_mlp_fwd_list(la, s));
+        } else if (term) {
+            // fused path with early ray termination: one round per segment -- fold the previous segment into T, cut, grid, ordered
+            // compaction of the segment's live samples -- then the fused MLP on that list; no host synchronisation between rounds
+            const TermWs w = term_ws_view(ctx->term_ws, R, ta.L);
+            ta.T = w.T; take_lists(ta, w);
+            QueryArgs q = list_query(ctx, p, w.list, w.count);
+            for (int k = 0; k * ta.L < S; ++k) {
+                ta.k = k;
+                HIPCHK(launch_termination_round(ta, s));
+                const int Lk = S - k * ta.L < ta.L ? S - k * ta.L : ta.L;
+                q.n = (long long)R * Lk;
+                HIPCHK(launch_query_list(q, s));
+            }
+        } else if (og) {
+            // fused path: ordered compaction of the live samples, then the fused MLP on the list alone (query.hip list mode)
+            take_lists(oa, occ_ws_view(ctx->occ_ws, oa.n));
+            HIPCHK(launch_occupancy_mark(oa, s));
+            QueryArgs q = list_query(ctx, p, oa.list, oa.count);
+            q.n = oa.n;
             HIPCHK(launch_query_list(q, s));
+        } else {
+            HIPCHK(launch_mlp_fwd(fa, train, s));
         }
-    } else if (og) {
-        // fused path: ordered compaction of the live samples, then the fused MLP on the list alone (query.hip list mode)
-        ProfScope ps(ctx, s, net == KNERF_COARSE ? P_FWD_C : P_FWD_F);
-        const OccWs w = occ_ws_view(ctx->occ_ws, oa.n);
-        oa.masks = w.masks; oa.blk_cnt = w.blk_cnt; oa.blk_off = w.blk_off; oa.list = w.list; oa.count = w.count;
-        HIPCHK(launch_occupancy_mark(oa, s));
-        QueryArgs q{};
-        q.stream = ctx->net[net].fwd_stream; q.bias = ctx->net[net].bias; q.shape = ctx->shape;
-        q.raw = ctx->raw; q.n = oa.n; q.list = w.list; q.count = w.count; q.o = o; q.d = d; q.t = t; q.S = S;
-        HIPCHK(launch_query_list(q, s));
-    } else {
-        ProfScope ps(ctx, s, net == KNERF_COARSE ? P_FWD_C : P_FWD_F);
-        HIPCHK(launch_mlp_fwd(fa, train, s));
     }
     CompositeArgs ca{};
-    ca.raw = ctx->raw; ca.t = t; ca.target = target; ca.image = image; ca.depth = depth; ca.weights = weights;
-    ca.draw = train ? ctx->draw : nullptr; ca.loss = loss; ca.R = R; ca.S = S; ca.white = ctx->cfg.white_background;
-    ca.grad_scale = 2.0f / (3.0f * (float)R) * inv_chunks;
-    ca.loss_scale = inv_chunks / (3.0f * (float)R);
+    ca.raw = ctx->raw; ca.t = t; ca.target = p.target; ca.image = p.image; ca.depth = p.depth; ca.weights = p.weights;
+    ca.draw = train ? ctx->draw.get() : nullptr; ca.loss = p.loss; ca.R = R; ca.S = S; ca.white = ctx->cfg.white_background;
+    ca.grad_scale = 2.0f / (3.0f * (float)R) * p.inv_chunks;
+    ca.loss_scale = p.inv_chunks / (3.0f * (float)R);
     // (the compacted path makes its own list of live tiles behind compositing, below)
     const bool skip = train && skipping(ctx) && !compact;
     const size_t n_tiles = tiles_for(fa.n_samples);
+    long long* const tile_stats = ctx->tile_stats + 4 * net;
     int* live_count = nullptr;
     if (skip && ctx->deterministic) {
         ca.tile_flags = ctx->tile_flags + tile0;                     // flags now, an ascending list from the compaction kernel below
     } else if (skip) {
         if (int r = next_tile_counter(ctx, s, &live_count)) return r;     // the compositing kernel appends the live tiles itself
         ca.tile_list = ctx->tile_list; ca.tile_count = live_count;
-        if (group_count) { ca.tile_list2 = ctx->tile_list_g; ca.tile_count2 = group_count; ca.tile_off2 = (int)tile0; }
+        if (p.group_count) { ca.tile_list2 = ctx->tile_list_g; ca.tile_count2 = p.group_count; ca.tile_off2 = (int)tile0; }
     }
     if (train && ctx->deterministic) ca.loss_partial = ctx->loss_partial;
     // an extended objective (knerf_set_objective): the launch goes to composite_ext.hip; the plain objective never does
     CompositeExt ce{};
     const bool ext = train && ctx->obj_ext;
     if (ext) {
-        const bool regs = (ctx->obj.nets >> (net == KNERF_COARSE ? 0 : 1)) & 1;
+        const bool regs = (ctx->obj.nets >> net) & 1;
         ce.loss_kind = ctx->obj.loss_kind; ce.huber_delta = ctx->obj.huber_delta;
         ce.lambda_d = regs ? ctx->obj.distortion : 0.f; ce.lambda_e = regs ? ctx->obj.opacity_entropy : 0.f;
-        ce.reg_scale = inv_chunks / (float)R;
-        ce.terms = ctx->d_terms + 4 * (net == KNERF_COARSE ? 0 : 1);
+        ce.reg_scale = p.inv_chunks / (float)R;
+        ce.terms = ctx->d_terms + 4 * net;
         if (ca.loss_partial) ce.terms_partial = ctx->loss_partial + ((size_t)ctx->ws_train_rays + 3) / 4;
     }
     {
         ProfScope ps(ctx, s, P_COMPOSITE);
         HIPCHK(launch_composite(ca, ext ? &ce : nullptr, s));
-        if (ca.loss_partial) HIPCHK(launch_loss_reduce(ca.loss_partial, (R + 3) / 4, loss, s));
+        if (ca.loss_partial) HIPCHK(launch_loss_reduce(ca.loss_partial, (R + 3) / 4, p.loss, s));
         if (ce.terms_partial) HIPCHK(launch_terms_reduce(ce.terms_partial, (R + 3) / 4, ce.terms, s));
         // deterministic mode: the pass's live tiles (indices relative to tile0) in ascending order; the padding tiles behind the
         // last real one count as dead
@@ -532,37 +538,34 @@ int run_pass(knerf_ctx* ctx, hipStream_t s, int net, const float* o, const float
             // raw and dL/draw of the live samples in list order (the last tile padded with zeros), one flag per compacted tile, then the ascending
             // list of the flagged tiles -- in both modes.  Compacted tiles straddle rays, so the per-ray tile flags of compositing (which
             // need S % 32 == 0) do not apply; the flags come from the gathered dL/draw instead, with the same dead-sample rule.
-            const OccWs w = occ_ws_view(ctx->occ_ws, oa.n);
-            HIPCHK(launch_occupancy_train_gather(w.list, w.count, ctx->raw, ctx->draw, ctx->occ_draw_c, ctx->occ_raw_c, ctx->tile_flags + tile0, fa.n_samples,
+            HIPCHK(launch_occupancy_train_gather(oa.list, oa.count, ctx->raw, ctx->draw, ctx->occ_draw_c, ctx->occ_raw_c, ctx->tile_flags + tile0, fa.n_samples,
                                                  (long long)n_tiles, ctx->skip_dead ? 1 : 0, s));
             if (int r = compact_tiles(ctx, s, ctx->tile_flags + tile0, (int)n_tiles, (int)n_tiles, (int)n_tiles, ctx->tile_list, &live_count)) return r;
         }
     }
     if (train && ctx->generic) {
-        ProfScope ps(ctx, s, net == KNERF_COARSE ? P_BWD_C : P_BWD_F);
+        ProfScope ps(ctx, s, P_BWD_C + net);
         if (og) {              // general-shape path behind a grid: no gradient from the dead samples (the mark kernel zeroes dL/draw there)
             OccArgs od = oa;
             od.raw = ctx->draw; od.stats = nullptr;
             HIPCHK(launch_occupancy_mark(od, s));
         }
-        if (ctx->deterministic && !ctx->partial) {       // general-shape path: the slab arena of generic.hip (the fused path's lives in launch_wgrad_tiles)
-            HIPCHK(hipStreamSynchronize(s));
-            HIPCHK(hipMalloc(&ctx->partial, gen::wgrad_partial_floats(ctx->gplan) * sizeof(float)));
-        }
+        // general-shape path: the slab arena of generic.hip (the fused path's lives in launch_wgrad_tiles)
+        if (ctx->deterministic) HIPCHK(ctx->partial.grow(gen::wgrad_partial_floats(ctx->gplan), s));
         HIPCHK(gen::backward(ctx->gplan, ctx->gws, ctx->gnet[net], ctx->raw, ctx->draw, fa.n_samples, ctx->net[net].g, s,
-                             ctx->deterministic ? ctx->partial : nullptr, skip ? ctx->tile_list : nullptr, skip ? live_count : nullptr,
-                             skip ? ctx->tile_stats + 4 * fa.net : nullptr));
+                             ctx->deterministic ? ctx->partial.get() : nullptr, skip ? ctx->tile_list.get() : nullptr, skip ? live_count : nullptr,
+                             skip ? tile_stats : nullptr));
     } else if (train) {
         BwdArgs ba{};
         ba.stream = ctx->net[net].bwd_stream; ba.raw = ctx->raw; ba.draw = ctx->draw; ba.mask = fa.mask; ba.dz = ctx->dz + saved_tile_off(tile0, ctx->si.dz_blocks);
-        ba.n_samples = fa.n_samples; ba.net = fa.net; ba.shape = ctx->shape;
-        if (skip) { ba.live = ctx->tile_list; ba.n_live = live_count; ba.stats = ctx->tile_stats + 4 * fa.net; }
+        ba.n_samples = fa.n_samples; ba.net = net; ba.shape = ctx->shape;
+        if (skip) { ba.live = ctx->tile_list; ba.n_live = live_count; ba.stats = tile_stats; }
         if (compact) {
             ba.raw = ctx->occ_raw_c; ba.draw = ctx->occ_draw_c; ba.live = ctx->tile_list; ba.n_live = live_count;
-            ba.stats = ctx->skip_dead ? ctx->tile_stats + 4 * fa.net : nullptr;
+            ba.stats = ctx->skip_dead ? tile_stats : nullptr;
         }
-        { ProfScope ps(ctx, s, net == KNERF_COARSE ? P_BWD_C : P_BWD_F); HIPCHK(launch_mlp_bwd(ba, s)); }
-        if (wgrad_now) { if (int r = launch_wgrad_tiles(ctx, s, net, tile0, n_tiles, skip || compact ? ctx->tile_list : nullptr, live_count)) return r; }
+        { ProfScope ps(ctx, s, P_BWD_C + net); HIPCHK(launch_mlp_bwd(ba, s)); }
+        if (p.wgrad_now) { if (int r = launch_wgrad_tiles(ctx, s, net, tile0, n_tiles, skip || compact ? ctx->tile_list.get() : nullptr, live_count)) return r; }
     }
     return KNERF_OK;
 }
@@ -584,18 +587,29 @@ int expand_head_grads(knerf_ctx* ctx, hipStream_t s) {
 // launch carries ~44 us of flush, ramp and tail, 12 % of a coarse launch (8192 tiles at ray_chunks 4096) but 4 % of a fine one, and
 // launches of 4 x 24576 tiles ran 4.7 % SLOWER per tile (41.4 vs 39.6 ns; power-limited clocks over a 4 ms kernel) -- measured with
 // both nets grouped: coarse 2.86 -> 2.57 ms, fine 7.8 -> 8.15 ms per step.
-int train_chunk_impl(knerf_ctx* ctx, hipStream_t s, const float* o, const float* d, const float* t, const float* target,
-                     const float* u, uint64_t seed, uint64_t ray_offset, int n_rays, float inv_chunks, float* loss,
-                     float* c_image, float* f_image, int slot = 0, int group = 1, int* group_count = nullptr) {
+struct Chunk {
+    const float *o, *d, *t, *target, *u;    // u: null, or the fine sampler's random numbers
+    uint64_t seed, ray_offset;
+    int n_rays;
+    float inv_chunks;
+    float *loss, *c_image, *f_image;        // null: the context's own scratch
+    int slot = 0, group = 1;
+    int* group_count = nullptr;             // Pass::group_count of the coarse pass
+};
+int train_chunk_impl(knerf_ctx* ctx, hipStream_t s, const Chunk& c) {
     const int Nc = ctx->cfg.n_coarse, Na = Nc + ctx->cfg.n_fine;
-    float* ci = c_image ? c_image : ctx->img_tmp;
-    float* fi = f_image ? f_image : ctx->img_tmp + (size_t)n_rays * 4;
-    float* ls = loss ? loss : ctx->loss_tmp;
-    const size_t tc = ctx->generic ? 0 : tiles_for((long long)n_rays * Nc);
-    const size_t tile0_c = group == 1 ? 0 : slot * tc, tile0_f = group == 1 ? 0 : group * tc;
-    if (int r = run_pass(ctx, s, KNERF_COARSE, o, d, t, n_rays, Nc, ci, nullptr, ctx->w_c, target, inv_chunks, ls, tile0_c, group == 1, group_count)) return r;
-    if (int r = knerf_sample_fine(ctx, s, t, ctx->w_c, u, seed, 0, ray_offset, n_rays, ctx->t_f)) return r;
-    return run_pass(ctx, s, KNERF_FINE, o, d, ctx->t_f, n_rays, Na, fi, nullptr, nullptr, target, inv_chunks, ls + 1, tile0_f, true);
+    float* ls = c.loss ? c.loss : ctx->loss_tmp.get();
+    const size_t tc = ws_sizes(ctx, c.n_rays).tiles_c;
+    Pass p{KNERF_COARSE, c.o, c.d, c.t, c.n_rays, Nc};
+    p.image = c.c_image ? c.c_image : ctx->img_tmp.get(); p.weights = ctx->w_c;
+    p.target = c.target; p.inv_chunks = c.inv_chunks; p.loss = ls;
+    p.tile0 = c.group == 1 ? 0 : c.slot * tc; p.wgrad_now = c.group == 1; p.group_count = c.group_count;
+    if (int r = run_pass(ctx, s, p)) return r;
+    if (int r = knerf_sample_fine(ctx, s, c.t, ctx->w_c, c.u, c.seed, 0, c.ray_offset, c.n_rays, ctx->t_f)) return r;
+    p.net = KNERF_FINE; p.t = ctx->t_f; p.S = Na;
+    p.image = c.f_image ? c.f_image : ctx->img_tmp + (size_t)c.n_rays * 4; p.weights = nullptr; p.loss = ls + 1;
+    p.tile0 = c.group == 1 ? 0 : c.group * tc; p.wgrad_now = true; p.group_count = nullptr;
+    return run_pass(ctx, s, p);
 }
 
 // chunks per COARSE weight-gradient launch of knerf_train_batch: up to KNERF_WGRAD_GROUP_MAX (4), within the budget
@@ -606,14 +620,13 @@ int wgrad_group_for(knerf_ctx* ctx, int n_rays, int n_chunks) {
     auto memo = [&](int g) { ctx->group_cache_rays = n_rays; ctx->group_cache_chunks = n_chunks; ctx->group_cache = g; return g; };
     const double budget = ctx->wgrad_group_gb;
     if (budget <= 0 || ctx->wgrad_group_max <= 1) return memo(1);
-    const int Nc = ctx->cfg.n_coarse, Na = Nc + ctx->cfg.n_fine;
-    const double per_chunk = (double)(saved_region_bytes(tiles_for((long long)n_rays * Nc), ctx->si.act_blocks) + saved_region_bytes(tiles_for((long long)n_rays * Nc), ctx->si.mask_blocks) +
-                                      saved_region_bytes(tiles_for((long long)n_rays * Nc), ctx->si.dz_blocks));   // one coarse region
-    (void)Na;
+    const size_t tc = ws_sizes(ctx, n_rays).tiles_c;
+    const double per_chunk = (double)(saved_region_bytes(tc, ctx->si.act_blocks) + saved_region_bytes(tc, ctx->si.mask_blocks) +
+                                      saved_region_bytes(tc, ctx->si.dz_blocks));   // one coarse region
     size_t free_b = 0, total_b = 0;
     double avail = budget * 1e9;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-        const double mine = ctx->ws_train ? (double)(ctx->act_bytes + ctx->mask_bytes + ctx->dz_bytes) : 0.0;   // what a re-allocation gives back
+        const double mine = ctx->ws_train ? (double)(ctx->act.bytes() + ctx->mask.bytes() + ctx->dz.bytes()) : 0.0;   // what a re-allocation gives back
         const double cap = 0.25 * ((double)free_b + mine);
         if (cap < avail) avail = cap;
     }
@@ -651,23 +664,21 @@ int ensure_call(knerf_ctx* ctx, long long n, hipStream_t s) {
         const knerf_config& c = ctx->cfg;
         ctx->call_plan = ctx->mlp_only ? gen::build_plan_widths(c.n_layers, c.dense_units, c.skip_layer, c.pos_emb_xyz, c.pos_emb_dir)
                                        : gen::build_plan(c.n_layers, c.dense_units, c.skip_layer, c.pos_emb_xyz, c.pos_emb_dir);
-        HIPCHK(hipMalloc(&ctx->call_net.packed, ctx->call_plan.packed_elems * sizeof(unsigned short)));
-        HIPCHK(hipMalloc(&ctx->call_net.head, gen::head_floats(ctx->call_plan) * sizeof(float)));
+        GenNetBufs& nb = ctx->call_net_buf;
+        HIPCHK(nb.packed.grow(ctx->call_plan.packed_elems, s));
+        HIPCHK(nb.head.grow(gen::head_floats(ctx->call_plan), s));
+        ctx->call_net.packed = nb.packed; ctx->call_net.head = nb.head;
         ctx->call_plan_ok = true;
     }
-    const gen::Plan& p = ctx->call_plan;
     const size_t mp = gen::padded_rows(n);
-    gen::Workspace& w = ctx->call_ws;
-    if (mp > w.mp) {
+    if (mp > ctx->call_ws.mp) {
+        GenWsBufs& b = ctx->call_ws_buf;
         HIPCHK(hipStreamSynchronize(s));
-        free_dev(w.act); free_dev(w.zs); free_dev(w.zc); free_dev(ctx->call_raw);
-        w.mp = 0;
-        const size_t ab = p.act_elems_per_row * mp * sizeof(unsigned short);
-        HIPCHK(hipMalloc(&w.act, ab));
-        HIPCHK(hipMemsetAsync(w.act, 0, ab, s));        // on the stream the consuming kernels run on
-        HIPCHK(hipMalloc(&w.zs, mp * 32 * sizeof(float)));
-        HIPCHK(hipMalloc(&w.zc, mp * 32 * sizeof(float)));
-        w.mp = mp;
+        release(b.act, b.zc);
+        ctx->call_ws = gen::Workspace{};
+        HIPCHK(b.act.grow(ctx->call_plan.act_elems_per_row * mp, s, true));
+        HIPCHK(b.zc.grow(mp * 32, s));
+        ctx->call_ws = gen_view(b, mp);
     }
     return KNERF_OK;
 }
@@ -685,13 +696,7 @@ int query_general(knerf_ctx* ctx, hipStream_t s, int net, const QueryArgs& q0) {
     if (chunk < 1024) chunk = 1024;
     if (chunk > q0.n) chunk = q0.n;
     if (int r = ensure_call(ctx, chunk, s)) return r;
-    const size_t tmp = (size_t)chunk * row_floats * sizeof(float);
-    if (tmp > ctx->query_tmp_bytes) {
-        HIPCHK(hipStreamSynchronize(s));
-        free_dev(ctx->query_tmp); ctx->query_tmp_bytes = 0;
-        HIPCHK(hipMalloc(&ctx->query_tmp, tmp));
-        ctx->query_tmp_bytes = tmp;
-    }
+    HIPCHK(ctx->query_tmp.grow((size_t)chunk * row_floats, s));
     float* xyz = ctx->query_tmp;
     float* dir = xyz + 3 * chunk;
     float* xenc = dir + 3 * chunk;
@@ -779,11 +784,6 @@ int knerf_create(const knerf_config* cfg, knerf_ctx** out) {
     const size_t NP = (size_t)ctx->n_params;
     const Tables& ht = host_tables(ctx->shape);
     ctx->tab.host = ht.host; ctx->tab.wgrad = ht.wgrad; ctx->tab.wgrad_off = ht.wgrad_off;
-    auto up = [&](int*& dptr, const std::vector<int32_t>& v) -> hipError_t {
-        hipError_t e = hipMalloc(&dptr, v.size() * sizeof(int32_t));
-        if (e != hipSuccess) return e;
-        return hipMemcpy(dptr, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    };
 #define CREATECHK(expr)                                                                                          \
     do {                                                                                                         \
         hipError_t e_ = (expr);                                                                                  \
@@ -793,65 +793,51 @@ int knerf_create(const knerf_config* cfg, knerf_ctx** out) {
             return fail(nullptr, KNERF_ERR_HIP, m_);                                                             \
         }                                                                                                        \
     } while (0)
-    CREATECHK(up(ctx->tab.d_fwd, ctx->tab.host.fwd));
-    CREATECHK(up(ctx->tab.d_bias, ctx->tab.host.fwd_bias));
-    CREATECHK(up(ctx->tab.d_bwd, ctx->tab.host.bwd));
-    CREATECHK(up(ctx->tab.d_wgrad, ctx->tab.wgrad));
+    CREATECHK(upload(ctx->tab.d_fwd, ctx->tab.host.fwd));
+    CREATECHK(upload(ctx->tab.d_bias, ctx->tab.host.fwd_bias));
+    CREATECHK(upload(ctx->tab.d_bwd, ctx->tab.host.bwd));
+    CREATECHK(upload(ctx->tab.d_wgrad, ctx->tab.wgrad));
     ctx->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (int r = upload_plan(ctx)) { std::string m_ = ctx->err; knerf_destroy(ctx); return fail(nullptr, r, m_); }
-    CREATECHK(hipMalloc(&ctx->tile_count, (size_t)ctx->tile_counters * sizeof(int)));
-    CREATECHK(hipMemset(ctx->tile_count, 0, (size_t)ctx->tile_counters * sizeof(int)));
-    CREATECHK(hipMalloc(&ctx->tile_stats, 8 * sizeof(long long)));       // per net: live, total, [2], [3]: out-of-range list entries (diagnostic builds)
-    CREATECHK(hipMemset(ctx->tile_stats, 0, 8 * sizeof(long long)));
-    CREATECHK(hipMalloc(&ctx->occ_stats, 4 * sizeof(long long)));
-    CREATECHK(hipMemset(ctx->occ_stats, 0, 4 * sizeof(long long)));
-    CREATECHK(hipMalloc(&ctx->occ_train_stats, 4 * sizeof(long long)));
-    CREATECHK(hipMemset(ctx->occ_train_stats, 0, 4 * sizeof(long long)));
-    CREATECHK(hipMalloc(&ctx->term_stats, 4 * sizeof(long long)));
-    CREATECHK(hipMemset(ctx->term_stats, 0, 4 * sizeof(long long)));
-    CREATECHK(hipMalloc(&ctx->d_diag, 2 * sizeof(unsigned long long)));
+    // everything below is allocated zeroed, on the null stream
+    CREATECHK(ctx->tile_count.grow(knerf_ctx::kTileCounters, nullptr, true));
+    CREATECHK(ctx->tile_stats.grow(8, nullptr, true));       // per net: live, total, [2], [3]: out-of-range list entries (diagnostic builds)
+    CREATECHK(ctx->occ_stats.grow(4, nullptr, true));
+    CREATECHK(ctx->occ_train_stats.grow(4, nullptr, true));
+    CREATECHK(ctx->term_stats.grow(4, nullptr, true));
+    CREATECHK(ctx->d_diag.grow(2, nullptr, true));
     CREATECHK(hipHostMalloc(&ctx->h_diag, 4 * sizeof(long long), hipHostMallocDefault));
     ctx->h_diag[0] = ctx->h_diag[1] = ctx->h_diag[2] = ctx->h_diag[3] = 0;
-    CREATECHK(hipMalloc(&ctx->grads, 2 * NP * sizeof(float)));
-    CREATECHK(hipMemset(ctx->grads, 0, 2 * NP * sizeof(float)));
-    CREATECHK(hipMalloc(&ctx->aux, 2 * (size_t)kAuxCount * sizeof(float)));
-    CREATECHK(hipMemset(ctx->aux, 0, 2 * (size_t)kAuxCount * sizeof(float)));
-    CREATECHK(hipMalloc(&ctx->d_flag, sizeof(int)));
-    CREATECHK(hipMemset(ctx->d_flag, 0, sizeof(int)));
-    CREATECHK(hipMalloc(&ctx->d_step, sizeof(int)));
-    CREATECHK(hipMalloc(&ctx->d_lr_t, sizeof(float)));
+    CREATECHK(ctx->grads.grow(2 * NP, nullptr, true));
+    CREATECHK(ctx->aux.grow(2 * (size_t)kAuxCount, nullptr, true));
+    CREATECHK(ctx->d_flag.grow(1, nullptr, true));
+    CREATECHK(ctx->d_step.grow(1, nullptr, true));
+    CREATECHK(ctx->d_lr_t.grow(1, nullptr, true));
     CREATECHK(launch_step_set(0, ctx->d_step, ctx->d_lr_t, AdamHyper{cfg->lr, cfg->beta1, cfg->beta2}, nullptr));
     CREATECHK(hipHostMalloc(&ctx->h_status, 2 * sizeof(int), hipHostMallocDefault));   // written by the device (optim.hip step_status)
     ctx->h_status[0] = ctx->h_status[1] = 0;
-    CREATECHK(hipMalloc(&ctx->loss_tmp, 2 * sizeof(float)));
-    CREATECHK(hipMalloc(&ctx->d_terms, 8 * sizeof(float)));
-    CREATECHK(hipMemset(ctx->d_terms, 0, 8 * sizeof(float)));
+    CREATECHK(ctx->loss_tmp.grow(2, nullptr, true));
+    CREATECHK(ctx->d_terms.grow(8, nullptr, true));
     for (int n = 0; n < 2; ++n) {
         Net& N = ctx->net[n];
         const size_t NW = ctx->generic ? NP : (size_t)ctx->si.ext_param_count;  // fused path: parameters + composed head (layout.h)
-        CREATECHK(hipMalloc(&N.w, NW * sizeof(float)));
-        CREATECHK(hipMalloc(&N.m, NP * sizeof(float)));
-        CREATECHK(hipMalloc(&N.v, NP * sizeof(float)));
-        CREATECHK(hipMemset(N.w, 0, NW * sizeof(float)));
-        CREATECHK(hipMemset(N.m, 0, NP * sizeof(float)));
-        CREATECHK(hipMemset(N.v, 0, NP * sizeof(float)));
+        CREATECHK(N.w.grow(NW, nullptr, true));
+        CREATECHK(N.m.grow(NP, nullptr, true));
+        CREATECHK(N.v.grow(NP, nullptr, true));
         N.g = ctx->grads + (size_t)n * NP;
         N.aux = ctx->aux + (size_t)n * kAuxCount;
         if (ctx->generic) {
-            CREATECHK(hipMalloc(&ctx->gnet[n].packed, ctx->gplan.packed_elems * sizeof(unsigned short)));
-            CREATECHK(hipMemset(ctx->gnet[n].packed, 0, ctx->gplan.packed_elems * sizeof(unsigned short)));
-            CREATECHK(hipMalloc(&ctx->gnet[n].head, gen::head_floats(ctx->gplan) * sizeof(float)));
-            CREATECHK(hipMemset(ctx->gnet[n].head, 0, gen::head_floats(ctx->gplan) * sizeof(float)));
-            CREATECHK(hipMalloc(&ctx->gnet[n].gaux, gen::aux_floats(ctx->gplan) * sizeof(float)));
-            CREATECHK(hipMemset(ctx->gnet[n].gaux, 0, gen::aux_floats(ctx->gplan) * sizeof(float)));
+            GenNetBufs& b = ctx->gnet_buf[n];
+            CREATECHK(b.packed.grow(ctx->gplan.packed_elems, nullptr, true));
+            CREATECHK(b.head.grow(gen::head_floats(ctx->gplan), nullptr, true));
+            CREATECHK(b.gaux.grow(gen::aux_floats(ctx->gplan), nullptr, true));
+            ctx->gnet[n] = gen::NetDev{b.packed, b.head, b.gaux};
         }
-        CREATECHK(hipMalloc(&N.fwd_stream, stream_bytes(ctx->si.fwd_blocks)));
-        CREATECHK(hipMalloc(&N.bwd_stream, stream_bytes(ctx->si.bwd_blocks)));
-        CREATECHK(hipMemset(N.fwd_stream, 0, stream_bytes(ctx->si.fwd_blocks)));
-        CREATECHK(hipMemset(N.bwd_stream, 0, stream_bytes(ctx->si.bwd_blocks)));
-        CREATECHK(hipMalloc(&N.bias, ctx->si.fwd_bias_tiles * 32 * sizeof(float)));
-        CREATECHK(hipMemset(N.bias, 0, ctx->si.fwd_bias_tiles * 32 * sizeof(float)));
+        CREATECHK(N.fwd_stream.grow(stream_bytes(ctx->si.fwd_blocks), nullptr, true));
+        CREATECHK(N.bwd_stream.grow(stream_bytes(ctx->si.bwd_blocks), nullptr, true));
+        CREATECHK(N.bias.grow((size_t)ctx->si.fwd_bias_tiles * 32, nullptr, true));
     }
+    CREATECHK(hipStreamSynchronize(nullptr));       // the zero-fills are done before any stream of the caller's touches the buffers
 #undef CREATECHK
     *out = ctx;
     return KNERF_OK;
@@ -859,28 +845,13 @@ int knerf_create(const knerf_config* cfg, knerf_ctx** out) {
 
 int knerf_destroy(knerf_ctx* ctx) {
     if (!ctx) return KNERF_OK;
-    for (int n = 0; n < 2; ++n) {
-        Net& N = ctx->net[n];
-        free_dev(N.w); free_dev(N.m); free_dev(N.v); free_dev(N.fwd_stream); free_dev(N.bwd_stream); free_dev(N.bias);
+    if (ctx->h_status) (void)hipHostFree(ctx->h_status);
+    if (ctx->h_diag) (void)hipHostFree(ctx->h_diag);
+    for (auto& r : ctx->prof) {             // events of a profile that was never read
+        if (r.e0) (void)hipEventDestroy(r.e0);
+        if (r.e1) (void)hipEventDestroy(r.e1);
     }
-    free_dev(ctx->grads); free_dev(ctx->aux); free_dev(ctx->d_flag); free_dev(ctx->loss_tmp); free_dev(ctx->d_terms); free_dev(ctx->d_step); free_dev(ctx->d_lr_t);
-    free_dev(ctx->d_opt_f); free_dev(ctx->d_opt_partial); free_dev(ctx->d_opt_tab);
-    if (ctx->h_status) { (void)hipHostFree(ctx->h_status); ctx->h_status = nullptr; }
-    if (ctx->h_diag) { (void)hipHostFree(ctx->h_diag); ctx->h_diag = nullptr; }
-    free_dev(ctx->d_diag); free_dev(ctx->diag_tmp);
-    free_dev(ctx->tab.d_fwd); free_dev(ctx->tab.d_bias); free_dev(ctx->tab.d_bwd); free_dev(ctx->tab.d_wgrad); free_dev(ctx->tab.d_plan);
-    free_dev(ctx->raw); free_dev(ctx->draw); free_dev(ctx->w_c); free_dev(ctx->t_f); free_dev(ctx->img_tmp);
-    free_dev(ctx->act); free_dev(ctx->mask); free_dev(ctx->dz);
-    free_dev(ctx->tile_flags); free_dev(ctx->tile_list); free_dev(ctx->tile_list_g); free_dev(ctx->tile_count); free_dev(ctx->tile_stats);
-    free_dev(ctx->partial); free_dev(ctx->loss_partial); free_dev(ctx->d_job_wg0);
-    free_dev(ctx->occ[0].bits); free_dev(ctx->occ[1].bits); free_dev(ctx->occ_ws); free_dev(ctx->occ_stats);
-    free_dev(ctx->occ_raw_c); free_dev(ctx->occ_draw_c); free_dev(ctx->occ_train_stats);
-    free_dev(ctx->term_ws); free_dev(ctx->term_stats);
-    free_dev(ctx->gws.act); free_dev(ctx->gws.dz); free_dev(ctx->gws.zs); free_dev(ctx->gws.zc); free_dev(ctx->gws.mask);
-    for (int n = 0; n < 2; ++n) { free_dev(ctx->gnet[n].packed); free_dev(ctx->gnet[n].head); free_dev(ctx->gnet[n].gaux); }
-    free_dev(ctx->call_net.head);
-    free_dev(ctx->call_ws.act); free_dev(ctx->call_ws.zs); free_dev(ctx->call_ws.zc); free_dev(ctx->call_net.packed); free_dev(ctx->call_raw); free_dev(ctx->query_tmp);
-    delete ctx;
+    delete ctx;                             // every device buffer goes with its owner (ctx.h DevBuf)
     return KNERF_OK;
 }
 
@@ -928,7 +899,9 @@ int knerf_forward_chunk(knerf_ctx* ctx, void* stream, int net, const float* o, c
     if (!o || !d || !t || !image || n_rays <= 0) return fail(ctx, KNERF_ERR_INVALID, "forward_chunk: null/empty argument");
     if (n_samples < 1 || n_samples > ctx->cfg.n_coarse + ctx->cfg.n_fine) return fail(ctx, KNERF_ERR_INVALID, "forward_chunk: n_samples out of range");
     if (int r = ensure_ws(ctx, n_rays, false, (hipStream_t)stream)) return r;
-    return run_pass(ctx, (hipStream_t)stream, net, o, d, t, n_rays, n_samples, image, depth, weights, nullptr, 1.f, nullptr);
+    Pass p{net, o, d, t, n_rays, n_samples};
+    p.image = image; p.depth = depth; p.weights = weights;
+    return run_pass(ctx, (hipStream_t)stream, p);
 }
 
 int knerf_mlp_call(knerf_ctx* ctx, void* stream, int net, const float* xyz_enc, const float* dir_enc, uint64_t n, float* raw) {
@@ -980,8 +953,8 @@ int knerf_set_occupancy(knerf_ctx* ctx, void* stream, int net, const uint32_t* b
     knerf_ctx::Occ& G = ctx->occ[net];
     if (!bits) {                                        // detach: passes enqueued earlier may still read the old bits
         HIPCHK(hipStreamSynchronize(s));
-        free_dev(G.bits);
-        G = knerf_ctx::Occ{};
+        G.bits.reset();
+        G.grid = OccGrid{};
         return KNERF_OK;
     }
     if (!cells || !lo || !hi) return fail(ctx, KNERF_ERR_INVALID, "set_occupancy: null cells / lo / hi");
@@ -995,46 +968,39 @@ int knerf_set_occupancy(knerf_ctx* ctx, void* stream, int net, const uint32_t* b
         n *= cells[a];
     }
     const size_t words = (size_t)((n + 31) / 32);
-    if (words > G.words) {
-        HIPCHK(hipStreamSynchronize(s));
-        free_dev(G.bits); G.words = 0;
-        HIPCHK(hipMalloc(&G.bits, words * sizeof(uint32_t)));
-        G.words = words;
-    }
+    G.grid.bits = nullptr;
+    HIPCHK(G.bits.grow(words, s));
     HIPCHK(hipMemcpyAsync(G.bits, bits, words * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));     // behind every pass enqueued earlier
-    for (int a = 0; a < 3; ++a) { G.cells[a] = cells[a]; G.lo[a] = lo[a]; G.scale[a] = scale[a]; }
-    G.outside_empty = outside_empty ? 1 : 0;
+    G.grid.bits = G.bits;
+    for (int a = 0; a < 3; ++a) { G.grid.cells[a] = cells[a]; G.grid.lo[a] = lo[a]; G.grid.scale[a] = scale[a]; }
+    G.grid.outside_empty = outside_empty ? 1 : 0;
+    return KNERF_OK;
+}
+
+// [net][k] counters whose first two per net are (live, total): read behind the stream, optionally reset; all: null, or all 2 k <= 8 words
+static int read_stats(knerf_ctx* ctx, void* stream, DevBuf<long long> knerf_ctx::*which, int64_t* live, int64_t* total, int reset, long long* all = nullptr) {
+    if (!ctx || !live || !total) return KNERF_ERR_INVALID;
+    long long own[8];
+    long long* h = all ? all : own;
+    const DevBuf<long long>& words = ctx->*which;
+    const int k = (int)words.size() / 2;
+    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+    HIPCHK(hipMemcpy(h, words, words.bytes(), hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(words, 0, words.bytes()));
+    for (int n = 0; n < 2; ++n) { live[n] = h[k * n]; total[n] = h[k * n + 1]; }
     return KNERF_OK;
 }
 
 int knerf_occupancy_stats(knerf_ctx* ctx, void* stream, int64_t* live, int64_t* total, int reset) {
-    if (!ctx || !live || !total) return KNERF_ERR_INVALID;
-    long long h[4] = {0, 0, 0, 0};
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    HIPCHK(hipMemcpy(h, ctx->occ_stats, sizeof(h), hipMemcpyDeviceToHost));
-    if (reset) HIPCHK(hipMemset(ctx->occ_stats, 0, sizeof(h)));
-    for (int n = 0; n < 2; ++n) { live[n] = h[2 * n]; total[n] = h[2 * n + 1]; }
-    return KNERF_OK;
+    return read_stats(ctx, stream, &knerf_ctx::occ_stats, live, total, reset);
 }
 
 int knerf_occupancy_train_stats(knerf_ctx* ctx, void* stream, int64_t* live, int64_t* total, int reset) {
-    if (!ctx || !live || !total) return KNERF_ERR_INVALID;
-    long long h[4] = {0, 0, 0, 0};
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    HIPCHK(hipMemcpy(h, ctx->occ_train_stats, sizeof(h), hipMemcpyDeviceToHost));
-    if (reset) HIPCHK(hipMemset(ctx->occ_train_stats, 0, sizeof(h)));
-    for (int n = 0; n < 2; ++n) { live[n] = h[2 * n]; total[n] = h[2 * n + 1]; }
-    return KNERF_OK;
+    return read_stats(ctx, stream, &knerf_ctx::occ_train_stats, live, total, reset);
 }
 
 int knerf_termination_stats(knerf_ctx* ctx, void* stream, int64_t* live, int64_t* total, int reset) {
-    if (!ctx || !live || !total) return KNERF_ERR_INVALID;
-    long long h[4] = {0, 0, 0, 0};
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    HIPCHK(hipMemcpy(h, ctx->term_stats, sizeof(h), hipMemcpyDeviceToHost));
-    if (reset) HIPCHK(hipMemset(ctx->term_stats, 0, sizeof(h)));
-    for (int n = 0; n < 2; ++n) { live[n] = h[2 * n]; total[n] = h[2 * n + 1]; }
-    return KNERF_OK;
+    return read_stats(ctx, stream, &knerf_ctx::term_stats, live, total, reset);
 }
 
 int knerf_sample_fine(knerf_ctx* ctx, void* stream, const float* t_coarse, const float* w_coarse, const float* u,
@@ -1057,11 +1023,15 @@ int knerf_render_chunk(knerf_ctx* ctx, void* stream, const float* o, const float
     hipStream_t s = (hipStream_t)stream;
     if (int r = ensure_ws(ctx, n_rays, false, s)) return r;
     const int Nc = ctx->cfg.n_coarse, Na = Nc + ctx->cfg.n_fine;
-    float* wc = c_weights ? c_weights : ctx->w_c;
-    float* tf = t_fine ? t_fine : ctx->t_f;
-    if (int r = run_pass(ctx, s, KNERF_COARSE, o, d, t, n_rays, Nc, c_image, c_depth, wc, nullptr, 1.f, nullptr, 0, true, nullptr, true)) return r;
+    float* wc = c_weights ? c_weights : ctx->w_c.get();
+    float* tf = t_fine ? t_fine : ctx->t_f.get();
+    Pass p{KNERF_COARSE, o, d, t, n_rays, Nc};
+    p.image = c_image; p.depth = c_depth; p.weights = wc; p.render = true;
+    if (int r = run_pass(ctx, s, p)) return r;
     if (int r = knerf_sample_fine(ctx, stream, t, wc, u, seed, 0, ray_offset, n_rays, tf)) return r;
-    return run_pass(ctx, s, KNERF_FINE, o, d, tf, n_rays, Na, f_image, f_depth, f_weights, nullptr, 1.f, nullptr, 0, true, nullptr, true);
+    p.net = KNERF_FINE; p.t = tf; p.S = Na;
+    p.image = f_image; p.depth = f_depth; p.weights = f_weights;
+    return run_pass(ctx, s, p);
 }
 
 int knerf_render_batch(knerf_ctx* ctx, void* stream, const float* o, const float* d, const float* t, const float* u, uint64_t seed,
@@ -1105,7 +1075,7 @@ int knerf_train_chunk(knerf_ctx* ctx, void* stream, const float* o, const float*
     if (ctx->plan_dirty) { if (int r = upload_plan(ctx)) return r; }
     ctx->tile_counter_next = 0;
     if (int r = ensure_ws(ctx, n_rays, true, s)) return r;
-    if (int r = train_chunk_impl(ctx, s, o, d, t, target, u, seed, ray_offset, n_rays, inv_chunks, loss, c_image, f_image)) return r;
+    if (int r = train_chunk_impl(ctx, s, Chunk{o, d, t, target, u, seed, ray_offset, n_rays, inv_chunks, loss, c_image, f_image})) return r;
     return expand_head_grads(ctx, s);
 }
 
@@ -1140,7 +1110,7 @@ int knerf_train_batch(knerf_ctx* ctx, void* stream, const float* o, const float*
         merge = 1;                                                  // the merged launches did not fit either: the caller's own chunks
         ctx->merge_fail_rays = user_chunks; ctx->merge_fail_chunks = n_rays / user_chunks; ++ctx->merge_fallbacks;
     }
-    const size_t tc = tiles_for((long long)ray_chunks * Nc);
+    const size_t tc = ws_sizes(ctx, ray_chunks).tiles_c;
     const bool skip = skipping(ctx);
     // coarse passes on the compacted path (occupancy_train): their flags lie at tile_flags + slot tc, a group's list is compacted from them
     const bool occ_c = !ctx->generic && occ_train_on(ctx, KNERF_COARSE);
@@ -1155,17 +1125,16 @@ int knerf_train_batch(knerf_ctx* ctx, void* stream, const float* o, const float*
             // set the sum of the earlier chunks aside (head sums expanded first: the expansion is linear), so that the accumulator
             // holds the last chunk's gradient alone when it is counted
             if (int r = expand_head_grads(ctx, s)) return r;
-            const size_t nb = 2 * (size_t)ctx->n_params * sizeof(float);
-            if (!ctx->diag_tmp) HIPCHK(hipMalloc(&ctx->diag_tmp, nb));
-            HIPCHK(hipMemcpyAsync(ctx->diag_tmp, ctx->grads, nb, hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemsetAsync(ctx->grads, 0, nb, s));
+            HIPCHK(ctx->diag_tmp.grow(ctx->grads.size(), s));
+            HIPCHK(hipMemcpyAsync(ctx->diag_tmp, ctx->grads, ctx->grads.bytes(), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemsetAsync(ctx->grads, 0, ctx->grads.bytes(), s));
         }
         // default-mode skipping: the coarse passes of a group append their live tiles to the group's list under one counter
         if (append_g && slot == 0) { if (int r = next_tile_counter(ctx, s, &group_count)) return r; }
-        if (int r = train_chunk_impl(ctx, s, o + r0 * 3, d + r0 * 3, t + r0 * Nc, target + r0 * 3, u ? u + r0 * Nf : nullptr, seed,
-                                     (uint64_t)r0, ray_chunks, 1.0f / (float)C, loss, c_image ? c_image + r0 * 3 : nullptr,
-                                     f_image ? f_image + r0 * 3 : nullptr, slot, G, append_g ? group_count : nullptr))
-            return r;
+        Chunk c{o + r0 * 3, d + r0 * 3, t + r0 * Nc, target + r0 * 3, u ? u + r0 * Nf : nullptr, seed, (uint64_t)r0, ray_chunks, 1.0f / (float)C,
+                loss, c_image ? c_image + r0 * 3 : nullptr, f_image ? f_image + r0 * 3 : nullptr};
+        c.slot = slot; c.group = G; c.group_count = append_g ? group_count : nullptr;
+        if (int r = train_chunk_impl(ctx, s, c)) return r;
         if (G > 1 && last) {                                        // the group's coarse weight gradients in one launch
             const int* live = nullptr; int* live_count = nullptr;
             if (occ_c) {                                            // compacted coarse passes: every flag of each region counts (zero past its list)
@@ -1224,12 +1193,10 @@ static int ensure_opt_buffers(knerf_ctx* ctx) {
     const int I = (int)begin.size();
     std::vector<int32_t> tab(off);
     tab.insert(tab.end(), item0.begin(), item0.end()); tab.insert(tab.end(), begin.begin(), begin.end()); tab.insert(tab.end(), end.begin(), end.end());
-    HIPCHK(hipMalloc(&ctx->d_opt_tab, tab.size() * sizeof(int32_t)));
-    HIPCHK(hipMemcpy(ctx->d_opt_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&ctx->d_opt_partial, 2 * (size_t)I * sizeof(double)));
-    HIPCHK(hipMemset(ctx->d_opt_partial, 0, 2 * (size_t)I * sizeof(double)));
-    HIPCHK(hipMalloc(&ctx->d_opt_f, (1 + 2 * (size_t)kOptMaxTensors) * sizeof(float)));
-    HIPCHK(hipMemset(ctx->d_opt_f, 0, (1 + 2 * (size_t)kOptMaxTensors) * sizeof(float)));
+    HIPCHK(ctx->d_opt_partial.grow(2 * (size_t)I, nullptr, true));
+    HIPCHK(ctx->d_opt_f.grow(1 + 2 * (size_t)kOptMaxTensors, nullptr, true));
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(upload(ctx->d_opt_tab, tab));           // last: its presence says that all three are there
     ctx->opt_tensors = T; ctx->opt_items = I;
     return KNERF_OK;
 }
@@ -1343,61 +1310,48 @@ int knerf_set_adam_state(knerf_ctx* ctx, void* stream, int net, const float* m_h
     return KNERF_OK;
 }
 
-// knerf_apply_adam while an optimizer extension is active (knerf_set_optimizer; optim_ext.h): the same sequence with the extended
-// element-wise and step kernels; the norm kinds of clipping replace the finite check by the sum-of-squares pass that contains it and add
-// one launch (the ordered pass that turns the partial sums into factors).
-static int apply_adam_ext(knerf_ctx* ctx, hipStream_t s) {
+// Finite check first, on the device; the Adam kernels read its flag and leave weights and slots untouched when it is set (the
+// reference aborts fit at nerf.py:381-382).  Nothing here waits for the GPU: the outcome reaches the host through a pinned status
+// word (knerf_poll_nonfinite).
+// While an optimizer extension is active (knerf_set_optimizer; optim_ext.h): the same sequence with the extended element-wise and step
+// kernels; the norm kinds of clipping replace the finite check by the sum-of-squares pass that contains it and add one launch (the
+// ordered pass that turns the partial sums into factors).
+int knerf_apply_adam(knerf_ctx* ctx, void* stream) {
+    if (!ctx) return KNERF_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
     const knerf_optimizer& o = ctx->opt;
-    const bool norms = o.clip == KNERF_CLIP_NORM || o.clip == KNERF_CLIP_GLOBAL_NORM;
+    const bool ext = ctx->opt_ext;
     const int T = ctx->opt_tensors, I = ctx->opt_items;
-    const int *tensor_off = ctx->d_opt_tab, *tensor_item0 = tensor_off + T + 1, *item_begin = tensor_item0 + T + 1, *item_end = item_begin + I;
-    float* decay = o.weight_decay > 0 ? ctx->d_opt_f : nullptr;
+    const int* tensor_off = ctx->d_opt_tab;
+    float* decay = ext && o.weight_decay > 0 ? ctx->d_opt_f.get() : nullptr;
     HIPCHK(hipMemsetAsync(ctx->d_flag, 0, sizeof(int), s));
-    if (norms) {
+    if (ext && (o.clip == KNERF_CLIP_NORM || o.clip == KNERF_CLIP_GLOBAL_NORM)) {
+        const int *tensor_item0 = tensor_off + T + 1, *item_begin = tensor_item0 + T + 1, *item_end = item_begin + I;
         HIPCHK(launch_sumsq_partial(ctx->grads, ctx->n_params, item_begin, item_end, I, ctx->d_opt_partial, ctx->d_flag, s));
         HIPCHK(launch_clip_scale(ctx->d_opt_partial, I, tensor_item0, T, o.clip, o.clip_arg, ctx->d_opt_f + 1, s));
     } else {
         HIPCHK(launch_check_finite(ctx->grads, 2 * ctx->n_params, ctx->d_flag, s));
     }
-    ctx->step += 1;
+    ctx->step += 1;           // host mirror: steps enqueued minus the skipped ones that have been polled; Adam's t lives on the device
     ProfScope ps(ctx, s, P_ADAM);
     for (int n = 0; n < 2; ++n) {
         AdamExtArgs x{};
         AdamArgs& a = x.a;
         a.w = ctx->net[n].w; a.m = ctx->net[n].m; a.v = ctx->net[n].v; a.g = ctx->net[n].g; a.n = ctx->n_params;
         a.lr_t = ctx->d_lr_t; a.b1 = ctx->cfg.beta1; a.b2 = ctx->cfg.beta2; a.eps = ctx->cfg.epsilon; a.nonfinite = ctx->d_flag;
-        x.clip = o.clip; x.clip_value = (float)o.clip_arg; x.scale = ctx->d_opt_f + 1 + n * kOptMaxTensors; x.tensor_off = tensor_off; x.n_tensors = T;
-        x.decay = decay;
-        HIPCHK(launch_adam_ext(x, s));
-    }
-    if (!ctx->generic) HIPCHK(launch_head_compose(ctx->net[0].w, ctx->net[1].w, ctx->si.trunk_params, ctx->si.units, ctx->si.trunk_x, ctx->si.trunk_x_slots, ctx->si.dir_dim, ctx->si.dir_slots, s));
-    for (int n = 0; n < 2; ++n)
-        if (int r = repack(ctx, n, s, false)) return r;
-    HIPCHK(launch_step_status_ext(ctx->d_flag, ctx->h_status, ctx->d_step, ctx->d_lr_t, decay, sched_args(ctx), s));
-    return KNERF_OK;
-}
-
-int knerf_apply_adam(knerf_ctx* ctx, void* stream) {
-    if (!ctx) return KNERF_ERR_INVALID;
-    hipStream_t s = (hipStream_t)stream;
-    if (ctx->opt_ext) return apply_adam_ext(ctx, s);
-    // Finite check first, on the device; the Adam kernels read its flag and leave weights and slots untouched when it is
-    // set (the reference aborts fit at nerf.py:381-382).  Nothing here waits for the GPU: the outcome reaches the host through
-    // a pinned status word (knerf_poll_nonfinite).
-    HIPCHK(hipMemsetAsync(ctx->d_flag, 0, sizeof(int), s));
-    HIPCHK(launch_check_finite(ctx->grads, 2 * ctx->n_params, ctx->d_flag, s));
-    ctx->step += 1;           // host mirror: steps enqueued minus the skipped ones that have been polled; Adam's t lives on the device
-    ProfScope ps(ctx, s, P_ADAM);
-    for (int n = 0; n < 2; ++n) {
-        AdamArgs a{};
-        a.w = ctx->net[n].w; a.m = ctx->net[n].m; a.v = ctx->net[n].v; a.g = ctx->net[n].g; a.n = ctx->n_params;
-        a.lr_t = ctx->d_lr_t; a.b1 = ctx->cfg.beta1; a.b2 = ctx->cfg.beta2; a.eps = ctx->cfg.epsilon; a.nonfinite = ctx->d_flag;
-        HIPCHK(launch_adam(a, s));
+        if (ext) {
+            x.clip = o.clip; x.clip_value = (float)o.clip_arg; x.scale = ctx->d_opt_f + 1 + n * kOptMaxTensors; x.tensor_off = tensor_off; x.n_tensors = T;
+            x.decay = decay;
+            HIPCHK(launch_adam_ext(x, s));
+        } else {
+            HIPCHK(launch_adam(a, s));
+        }
     }
     if (!ctx->generic) HIPCHK(launch_head_compose(ctx->net[0].w, ctx->net[1].w, ctx->si.trunk_params, ctx->si.units, ctx->si.trunk_x, ctx->si.trunk_x_slots, ctx->si.dir_dim, ctx->si.dir_slots, s));      // both nets' heads in one launch
     for (int n = 0; n < 2; ++n)
         if (int r = repack(ctx, n, s, false)) return r;
-    HIPCHK(launch_step_status(ctx->d_flag, ctx->h_status, ctx->d_step, ctx->d_lr_t, AdamHyper{ctx->cfg.lr, ctx->cfg.beta1, ctx->cfg.beta2}, s));
+    if (ext) HIPCHK(launch_step_status_ext(ctx->d_flag, ctx->h_status, ctx->d_step, ctx->d_lr_t, decay, sched_args(ctx), s));
+    else HIPCHK(launch_step_status(ctx->d_flag, ctx->h_status, ctx->d_step, ctx->d_lr_t, AdamHyper{ctx->cfg.lr, ctx->cfg.beta1, ctx->cfg.beta2}, s));
     return KNERF_OK;
 }
 
@@ -1489,12 +1443,8 @@ int knerf_get_option(knerf_ctx* ctx, const char* name, double* value) {
 }
 
 int knerf_tile_stats_net(knerf_ctx* ctx, void* stream, int64_t* live, int64_t* total, int reset) {
-    if (!ctx || !live || !total) return KNERF_ERR_INVALID;
-    long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-    HIPCHK(hipMemcpy(h, ctx->tile_stats, sizeof(h), hipMemcpyDeviceToHost));
-    if (reset) HIPCHK(hipMemset(ctx->tile_stats, 0, sizeof(h)));
-    for (int n = 0; n < 2; ++n) { live[n] = h[4 * n]; total[n] = h[4 * n + 1]; }
+    long long h[8];
+    if (int r = read_stats(ctx, stream, &knerf_ctx::tile_stats, live, total, reset, h)) return r;
     if (h[2] || h[3] || h[6] || h[7])      // only a -DKNERF_LIST_GUARD build counts these
         return fail(ctx, KNERF_ERR_HIP, "tile list held " + std::to_string(h[2] + h[6]) + " (dgrad) / " + std::to_string(h[3] + h[7]) + " (wgrad) entries outside their pass");
     return KNERF_OK;
@@ -1538,40 +1488,40 @@ int knerf_set_step_count(knerf_ctx* ctx, int step) {
     return KNERF_OK;
 }
 
-int knerf_generate_rays(knerf_ctx* ctx, void* stream, const float* c2w, const float* noise, uint64_t seed, uint64_t stream_id,
-                        int batch, int height, int width, int n_samples, float focal, float near_plane, float far_plane,
-                        float* o, float* d, float* t) {
+// validation and argument fill shared by each plain ray entry point and its _ext twin; `who` prefixes the messages
+static int raygen_args(knerf_ctx* ctx, const char* who, const float* c2w, const float* noise, uint64_t seed, uint64_t stream_id, int batch, int height,
+                       int width, int n_samples, float focal, float near_plane, float far_plane, float* o, float* d, float* t, RayGenArgs* out) {
     if (!c2w || !o || !d || !t || batch <= 0 || height <= 0 || width <= 0 || n_samples <= 0)
-        return fail(ctx, KNERF_ERR_INVALID, "generate_rays: null/empty argument");
+        return fail(ctx, KNERF_ERR_INVALID, std::string(who) + ": null/empty argument");
     RayGenArgs a{};
     a.c2w = c2w; a.noise = noise; a.o = o; a.d = d; a.t = t; a.B = batch; a.H = height; a.W = width; a.N = n_samples;
     a.focal = focal; a.near_ = near_plane; a.far_ = far_plane; a.seed = seed; a.stream_id = stream_id;
-    if (launch_raygen(a, (hipStream_t)stream) != hipSuccess) return fail(ctx, KNERF_ERR_HIP, "generate_rays: launch failed");
+    *out = a;
     return KNERF_OK;
 }
 
-int knerf_draw_ray_batch(knerf_ctx* ctx, void* stream, const float* images, const float* c2w, int n_views, int height, int width,
-                         int channels, float focal, float near_plane, float far_plane, int n_samples, uint64_t seed, uint64_t epoch,
-                         uint64_t first, int n_rays, const float* noise, uint64_t noise_stream, float* o, float* d, float* t,
-                         float* target, int64_t* index) {
+static int raybatch_args(knerf_ctx* ctx, const char* who, const float* images, const float* c2w, int n_views, int height, int width, int channels,
+                         float focal, float near_plane, float far_plane, int n_samples, uint64_t seed, uint64_t epoch, uint64_t first, int n_rays,
+                         const float* noise, uint64_t noise_stream, float* o, float* d, float* t, float* target, int64_t* index, RayBatchArgs* out) {
+    const std::string w = std::string(who) + ": ";
     if (!images || !c2w || !o || !d || !t || !target || n_views <= 0 || height <= 0 || width <= 0 || n_samples <= 0 || n_rays <= 0)
-        return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch: null/empty argument");
-    if (channels != 3 && channels != 4) return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch: channels must be 3 or 4");
+        return fail(ctx, KNERF_ERR_INVALID, w + "null/empty argument");
+    if (channels != 3 && channels != 4) return fail(ctx, KNERF_ERR_INVALID, w + "channels must be 3 or 4");
     const unsigned long long hw = (unsigned long long)height * (unsigned long long)width;
     if (hw >= (1ull << 31) || hw * (unsigned long long)n_views >= (1ull << 40))
-        return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch: the dataset must hold fewer than 2^40 pixels (2^31 per view)");
+        return fail(ctx, KNERF_ERR_INVALID, w + "the dataset must hold fewer than 2^40 pixels (2^31 per view)");
     const unsigned long long P = hw * (unsigned long long)n_views;
     if (first > P || (unsigned long long)n_rays > P - first)
-        return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch: first + n_rays exceeds the pixels of the dataset");
+        return fail(ctx, KNERF_ERR_INVALID, w + "first + n_rays exceeds the pixels of the dataset");
     if ((unsigned long long)n_rays * (unsigned long long)n_samples >= (1ull << 39))
-        return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch: n_rays x n_samples is too large for one launch");
+        return fail(ctx, KNERF_ERR_INVALID, w + "n_rays x n_samples is too large for one launch");
     RayBatchArgs a{};
     a.images = images; a.c2w = c2w; a.noise = noise; a.o = o; a.d = d; a.t = t; a.target = target; a.index = (long long*)index;
     a.perm = make_pixel_perm(P, seed, epoch);
     a.first = first; a.seed = seed; a.noise_stream = noise_stream;
     a.n_rays = n_rays; a.H = height; a.W = width; a.C = channels; a.N = n_samples;
     a.focal = focal; a.near_ = near_plane; a.far_ = far_plane;
-    if (launch_raybatch(a, (hipStream_t)stream) != hipSuccess) return fail(ctx, KNERF_ERR_HIP, "draw_ray_batch: launch failed");
+    *out = a;
     return KNERF_OK;
 }
 
@@ -1594,19 +1544,36 @@ static int check_ray_model(knerf_ctx* ctx, const char* who, const knerf_ray_mode
     return KNERF_OK;
 }
 
+int knerf_generate_rays(knerf_ctx* ctx, void* stream, const float* c2w, const float* noise, uint64_t seed, uint64_t stream_id,
+                        int batch, int height, int width, int n_samples, float focal, float near_plane, float far_plane,
+                        float* o, float* d, float* t) {
+    RayGenArgs a{};
+    if (int r = raygen_args(ctx, "generate_rays", c2w, noise, seed, stream_id, batch, height, width, n_samples, focal, near_plane, far_plane, o, d, t, &a)) return r;
+    if (launch_raygen(a, (hipStream_t)stream) != hipSuccess) return fail(ctx, KNERF_ERR_HIP, "generate_rays: launch failed");
+    return KNERF_OK;
+}
+
 int knerf_generate_rays_ext(knerf_ctx* ctx, void* stream, const float* c2w, const float* noise, uint64_t seed, uint64_t stream_id,
                             int batch, int height, int width, int n_samples, float focal, float near_plane, float far_plane,
                             float* o, float* d, float* t, const knerf_ray_model* model) {
-    if (!c2w || !o || !d || !t || batch <= 0 || height <= 0 || width <= 0 || n_samples <= 0)
-        return fail(ctx, KNERF_ERR_INVALID, "generate_rays_ext: null/empty argument");
+    RayGenArgs a{};
+    if (int r = raygen_args(ctx, "generate_rays_ext", c2w, noise, seed, stream_id, batch, height, width, n_samples, focal, near_plane, far_plane, o, d, t, &a)) return r;
     if ((unsigned long long)batch * (unsigned long long)height * (unsigned long long)width >= (1ull << 39) / (unsigned long long)n_samples)
         return fail(ctx, KNERF_ERR_INVALID, "generate_rays_ext: batch x height x width x n_samples is too large for one launch");
     RayModel m{};
     if (int r = check_ray_model(ctx, "generate_rays_ext", model, near_plane, far_plane, &m)) return r;
-    RayGenArgs a{};
-    a.c2w = c2w; a.noise = noise; a.o = o; a.d = d; a.t = t; a.B = batch; a.H = height; a.W = width; a.N = n_samples;
-    a.focal = focal; a.near_ = near_plane; a.far_ = far_plane; a.seed = seed; a.stream_id = stream_id;
     if (launch_raygen_ext(a, m, (hipStream_t)stream) != hipSuccess) return fail(ctx, KNERF_ERR_HIP, "generate_rays_ext: launch failed");
+    return KNERF_OK;
+}
+
+int knerf_draw_ray_batch(knerf_ctx* ctx, void* stream, const float* images, const float* c2w, int n_views, int height, int width,
+                         int channels, float focal, float near_plane, float far_plane, int n_samples, uint64_t seed, uint64_t epoch,
+                         uint64_t first, int n_rays, const float* noise, uint64_t noise_stream, float* o, float* d, float* t,
+                         float* target, int64_t* index) {
+    RayBatchArgs a{};
+    if (int r = raybatch_args(ctx, "draw_ray_batch", images, c2w, n_views, height, width, channels, focal, near_plane, far_plane, n_samples, seed, epoch,
+                              first, n_rays, noise, noise_stream, o, d, t, target, index, &a)) return r;
+    if (launch_raybatch(a, (hipStream_t)stream) != hipSuccess) return fail(ctx, KNERF_ERR_HIP, "draw_ray_batch: launch failed");
     return KNERF_OK;
 }
 
@@ -1614,25 +1581,11 @@ int knerf_draw_ray_batch_ext(knerf_ctx* ctx, void* stream, const float* images, 
                              int channels, float focal, float near_plane, float far_plane, int n_samples, uint64_t seed, uint64_t epoch,
                              uint64_t first, int n_rays, const float* noise, uint64_t noise_stream, float* o, float* d, float* t,
                              float* target, int64_t* index, const knerf_ray_model* model) {
-    if (!images || !c2w || !o || !d || !t || !target || n_views <= 0 || height <= 0 || width <= 0 || n_samples <= 0 || n_rays <= 0)
-        return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch_ext: null/empty argument");
-    if (channels != 3 && channels != 4) return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch_ext: channels must be 3 or 4");
-    const unsigned long long hw = (unsigned long long)height * (unsigned long long)width;
-    if (hw >= (1ull << 31) || hw * (unsigned long long)n_views >= (1ull << 40))
-        return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch_ext: the dataset must hold fewer than 2^40 pixels (2^31 per view)");
-    const unsigned long long P = hw * (unsigned long long)n_views;
-    if (first > P || (unsigned long long)n_rays > P - first)
-        return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch_ext: first + n_rays exceeds the pixels of the dataset");
-    if ((unsigned long long)n_rays * (unsigned long long)n_samples >= (1ull << 39))
-        return fail(ctx, KNERF_ERR_INVALID, "draw_ray_batch_ext: n_rays x n_samples is too large for one launch");
+    RayBatchArgs a{};
+    if (int r = raybatch_args(ctx, "draw_ray_batch_ext", images, c2w, n_views, height, width, channels, focal, near_plane, far_plane, n_samples, seed, epoch,
+                              first, n_rays, noise, noise_stream, o, d, t, target, index, &a)) return r;
     RayModel m{};
     if (int r = check_ray_model(ctx, "draw_ray_batch_ext", model, near_plane, far_plane, &m)) return r;
-    RayBatchArgs a{};
-    a.images = images; a.c2w = c2w; a.noise = noise; a.o = o; a.d = d; a.t = t; a.target = target; a.index = (long long*)index;
-    a.perm = make_pixel_perm(P, seed, epoch);
-    a.first = first; a.seed = seed; a.noise_stream = noise_stream;
-    a.n_rays = n_rays; a.H = height; a.W = width; a.C = channels; a.N = n_samples;
-    a.focal = focal; a.near_ = near_plane; a.far_ = far_plane;
     if (launch_raybatch_ext(a, m, (hipStream_t)stream) != hipSuccess) return fail(ctx, KNERF_ERR_HIP, "draw_ray_batch_ext: launch failed");
     return KNERF_OK;
 }
