@@ -514,6 +514,47 @@ int knerf_baked_render(void* stream, const knerf_baked_field* field, const float
                        const float* far, float near_all, float far_all, uint64_t n_rays, float step, float termination, int flags,
                        float* image, float* depth, float* opacity, int64_t* stats);
 
+/* ---- Optimising a baked field against ray batches.  Extension, no reference counterpart (as PlenOctrees and Plenoxels optimise their
+ * grids after conversion).  Two context-free launches; csrc/baked_train.hip, tests/baked_train_reference.py restates them in fp64.
+ * knerf_baked_train: HOST struct.  field: the records (knerf_baked_train_apply WRITES them) and, as bits, the SUPPORT bitfield: the
+ * cells that are ever fetched, fixed while the field is optimised, a superset of the cells with a non-zero sigma; never NULL here.
+ * slot_of: int32 [points], the slot of every lattice point that is a corner of a support cell, -1 elsewhere.  grad: fp32
+ * [n_slots][1 + 3 K] gradient rows in the column order of a record: sigma, then [k][c].  1 <= n_slots <= points. */
+typedef struct knerf_baked_train {
+    knerf_baked_field field;
+    const int32_t* slot_of;      /* DEVICE */
+    float* grad;                 /* DEVICE */
+    uint64_t n_slots;
+} knerf_baked_train;
+/* knerf_baked_train_rays -- extension, no reference counterpart.  ADDS to grad the gradient of
+ *   L = (1 / 3 N) sum_rays sum_c (out_c - target_c)^2,  N = n_norm (0: n_rays),  out = the image of knerf_baked_render
+ * marched with KNERF_BAKED_SKIP_EMPTY over the support bits (always, whether the flag is given or not), same step, termination,
+ * white-background flag and lane variants (flags as knerf_baked_render).  target [n_rays,3].  Each ray is marched twice in the launch:
+ * first the render kernel's arithmetic sample for sample (C = sum w col, O = sum w), then again to scatter.  Both clamps pass the
+ * gradient on the closed interval [0, 1]; the cut of a terminated ray is held fixed; coefficients are differentiated at their stored
+ * fp16 values.  With g_c = 2 (out_c - target_c) / (3 N) [0 <= C_c + bg (1 - O) <= 1], bg = 1 with the white background else 0,
+ * A_j = sum_c g_c (col_jc - bg), delta = step |d| and tau_n the trilinear weights of sample j's 8 corners n:
+ *   grad[n][sigma] += tau_n delta (T_{j+1} A_j - sum_{i>j} w_i A_i)        (no division by 1 - alpha)
+ *   grad[n][k][c]  += tau_n Y_k g_c w_j [0 <= r_jc <= 1]                   r the colour before its clamp
+ * by fp32 atomic adds: the sums depend on arrival order in their last bits.  sq_err: [n_rays] or NULL; the ray's
+ * sum_c (out_c - target_c)^2, a plain store.
+ * KNERF_ERR_INVALID, before any launch: NULL train, records, bits, slot_of, grad, origins, directions or target; n_slots outside
+ * [1, points]; n_norm >= 2^36; and every argument error of knerf_baked_render. */
+int knerf_baked_train_rays(void* stream, const knerf_baked_train* train, const float* origins, const float* directions, const float* near,
+                           const float* far, float near_all, float far_all, const float* target, uint64_t n_rays, uint64_t n_norm,
+                           float step, float termination, int flags, float* sq_err);
+/* knerf_baked_train_apply -- extension, no reference counterpart.  One Adam step over all slots and the records rewritten.
+ * point_of: int32 [n_slots], the lattice point of a slot (the inverse of slot_of); sigma_trainable: uint8 [n_slots]; master, m, v:
+ * fp32 [n_slots][1 + 3 K] like grad.  Per column, Keras form: m += (g - m)(1 - beta_1), v += (g g - v)(1 - beta_2),
+ * w -= rate m / (sqrt(v) + epsilon), rate = rate_sigma for the sigma column and rate_sh for the others: the caller's
+ * learning_rate sqrt(1 - beta_2^t) / (1 - beta_1^t), computed in double from its own step count t.  The sigma column is updated only
+ * where sigma_trainable is set (elsewhere w, m, v keep their values) and projected: w <- max(w, 0).  Then the slot's record is
+ * rewritten (fp32 sigma, coefficients rounded to fp16 to nearest even, zero padding) and the gradient row is zeroed.
+ * KNERF_ERR_INVALID: as above, a NULL point_of, sigma_trainable, master, m or v, a rate that is not finite, a beta outside [0, 1),
+ * epsilon <= 0. */
+int knerf_baked_train_apply(void* stream, const knerf_baked_train* train, const int32_t* point_of, const uint8_t* sigma_trainable,
+                            float* master, float* m, float* v, float rate_sigma, float rate_sh, float beta_1, float beta_2, float epsilon);
+
 /* Diagnostics (layout tables, workspace views, hardware-fact and bandwidth probes) are NOT part of this library: they are
  * declared in include/knerf_debug.h and built into libknerf_probe.so for tests/ and tools/ only. */
 

@@ -44,6 +44,11 @@ class KnerfBakedField(C.Structure):
                 ("lo", C.c_float * 3), ("hi", C.c_float * 3)]
 
 
+class KnerfBakedTrain(C.Structure):
+    """struct knerf_baked_train (include/knerf.h): the field (bits = the support), the slot table, the gradient rows, their count"""
+    _fields_ = [("field", KnerfBakedField), ("slot_of", C.c_void_p), ("grad", C.c_void_p), ("n_slots", C.c_uint64)]
+
+
 BAKED_WHITE_BACKGROUND, BAKED_SKIP_EMPTY, BAKED_LANES_SHIFT = 1, 2, 8
 SPACING_LINEAR, SPACING_DISPARITY = 0, 1
 SPACINGS = {"linear": SPACING_LINEAR, "disparity": SPACING_DISPARITY}
@@ -125,6 +130,10 @@ SIGNATURES = {
     "knerf_baked_pack": (C.c_int, [_P, _F, _F, _F, _P, C.c_uint64, C.c_uint64, C.c_int, _P]),
     "knerf_baked_render": (C.c_int, [_P, C.POINTER(KnerfBakedField), _F, _F, _F, _F, C.c_float, C.c_float, C.c_uint64, C.c_float,
                                      C.c_float, C.c_int, _F, _F, _F, _P]),
+    "knerf_baked_train_rays": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _F, _F, _F, _F, C.c_float, C.c_float, _F, C.c_uint64, C.c_uint64,
+                                         C.c_float, C.c_float, C.c_int, _F]),
+    "knerf_baked_train_apply": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _P, _P, _F, _F, _F, C.c_float, C.c_float, C.c_float, C.c_float,
+                                          C.c_float]),
 }
 
 _lib = None

@@ -1,7 +1,8 @@
 """The baked field: a trained NeRF stored as a voxel grid with spherical-harmonic colour and rendered without the MLP (extension,
 no reference counterpart; PlenOctrees, SNeRG and Plenoxels bake a trained NeRF in this way).
 
-The arithmetic is HIP (csrc/baked.hip: knerf_baked_project, knerf_baked_pack, knerf_baked_render; include/knerf.h holds the contract);
+The arithmetic is HIP (csrc/baked.hip: knerf_baked_project, knerf_baked_pack, knerf_baked_render; include/knerf.h holds the contract;
+BakedField.optimizer and baked_train.py: optimising the records against ray batches, csrc/baked_train.hip);
 torch is used for device memory, streams and the index plumbing of the bake only.  Host-side pieces (basis, fit matrix, record
 layout) are NumPy and need no device.
 """
@@ -175,6 +176,35 @@ def _check(rc, what):
             _lib.KnerfError(f"{what} failed ({rc})")
 
 
+def _ray_args(field, origins, directions, near, far, step):
+    """the rays of a march as the kernels take them: (o [n,3], d [n,3], n, step, (near [n] | None, near_all), (far [n] | None, far_all));
+    ValueError on mismatched counts, a step that is not a positive float32, ends that are not finite, 2^23 samples per ray and more"""
+    from .runtime import _f32
+    dev = field.device
+    o, d = _f32(origins, dev).reshape(-1, 3), _f32(directions, dev).reshape(-1, 3)
+    n = o.shape[0]
+    if d.shape[0] != n:
+        raise ValueError(f"{n} origins for {d.shape[0]} directions")
+    h = float(step) if step is not None else 0.5 * float(min(field.cell_size))
+    if not np.float32(h) > 0:
+        raise ValueError(f"step {h!r} is not a positive float32")
+    ends = []
+    for name, v in (("near", near), ("far", far)):
+        if isinstance(v, (int, float, np.floating, np.integer)):
+            if not np.isfinite(np.float32(v)):
+                raise ValueError(f"{name} must be finite, got {v!r}")
+            ends.append((None, float(v)))
+        else:
+            tv = _f32(v, dev).reshape(-1)
+            if tv.numel() != n:
+                raise ValueError(f"{name} must be a scalar or hold one value per ray ({n}), got {tv.numel()}")
+            ends.append((tv, 0.0))
+    (near_t, near0), (far_t, far0) = ends
+    if near_t is None and far_t is None and (far0 - near0) / h >= float(1 << 23):
+        raise ValueError(f"(far - near) / step = {(far0 - near0) / h:.3g} samples per ray; at most 2^23")
+    return o, d, n, h, ends[0], ends[1]
+
+
 class BakedField:
     """A lattice of (sigma fp32, 3 K fp16 SH coefficients) records over a box plus the occupancy bits of its cells; render() marches
     rays through it on the GPU.  Built by NeRF.bake, BakedField.from_arrays or BakedField.load."""
@@ -308,30 +338,10 @@ class BakedField:
         in summation order only)."""
         import torch
         from . import _lib
-        from .runtime import _f32, _ptr
+        from .runtime import _ptr
         outs = check_render_args(step, termination, outputs, self.sh_degree, lanes_per_ray)
         dev = self.device
-        o, d = _f32(origins, dev).reshape(-1, 3), _f32(directions, dev).reshape(-1, 3)
-        n = o.shape[0]
-        if d.shape[0] != n:
-            raise ValueError(f"{n} origins for {d.shape[0]} directions")
-        h = float(step) if step is not None else 0.5 * float(min(self.cell_size))
-        if not np.float32(h) > 0:
-            raise ValueError(f"step {h!r} is not a positive float32")
-        ends = []
-        for name, v in (("near", near), ("far", far)):
-            if isinstance(v, (int, float, np.floating, np.integer)):
-                if not np.isfinite(np.float32(v)):
-                    raise ValueError(f"{name} must be finite, got {v!r}")
-                ends.append((None, float(v)))
-            else:
-                tv = _f32(v, dev).reshape(-1)
-                if tv.numel() != n:
-                    raise ValueError(f"{name} must be a scalar or hold one value per ray ({n}), got {tv.numel()}")
-                ends.append((tv, 0.0))
-        (near_t, near0), (far_t, far0) = ends
-        if near_t is None and far_t is None and (far0 - near0) / h >= float(1 << 23):
-            raise ValueError(f"(far - near) / step = {(far0 - near0) / h:.3g} samples per ray; at most 2^23")
+        o, d, n, h, (near_t, near0), (far_t, far0) = _ray_args(self, origins, directions, near, far, step)
         e = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)
         res = {"image": e(n, 3) if "image" in outs else None, "depth": e(n) if "depth" in outs else None,
                "opacity": e(n) if "opacity" in outs else None}
@@ -346,6 +356,24 @@ class BakedField:
         if stats:
             out["stats"] = counter
         return out
+
+    # ---- optimisation against ray batches
+    def optimizer(self, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
+                  white_background=False, termination=0.0, lanes_per_ray=0):
+        """A BakedFieldOptimizer (baked_train.py) over a COPY of this field's records: Adam on sigma and the SH coefficients of the
+        lattice points around the occupied cells (grown by `dilation` cells) against batches of rays and their colours; this field
+        itself is left as it is.  step, white_background, termination, lanes_per_ray: how the optimiser marches, as in render()."""
+        from .baked_train import BakedFieldOptimizer
+        return BakedFieldOptimizer(self, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
+                                   termination, lanes_per_ray)
+
+
+def __getattr__(name):
+    """the optimiser's names live in baked_train.py (which imports this module) and are reachable from here as well"""
+    if name in ("BakedFieldOptimizer", "check_optimizer_args", "check_target_shape", "bias_corrected_rate"):
+        from . import baked_train
+        return getattr(baked_train, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def _unpack_words(words, cells):

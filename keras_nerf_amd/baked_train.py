@@ -1,0 +1,198 @@
+"""Optimising a baked field against ray batches (extension, no reference counterpart; PlenOctrees and Plenoxels optimise their grids
+against the photographs after conversion in this way).
+
+The arithmetic is HIP (csrc/baked_train.hip: knerf_baked_train_rays marches a batch, evaluates the squared error and scatters its
+gradient into the lattice; knerf_baked_train_apply is Adam and rewrites the records; include/knerf.h holds the contract).  torch is
+used for device memory, streams and the index plumbing of the construction only.  No step waits for the GPU.
+
+What keeps skipping empty cells exact while the numbers move:
+  support    the field's occupancy bits at the start, grown by `dilation` cells, fixed for the optimiser's lifetime: the bits of every
+             march, of the live field's renders included;
+  slots      the lattice points that are a corner of a support cell; master values, gradients and both Adam moments are rows
+             [n_slots][1 + 3 K] fp32 (sigma, then [k][c]); nothing but the int32 slot table is dense over the lattice;
+  sigma      is trainable only at slots whose 8 adjacent cells all lie in the support (or outside the lattice) and is projected to >= 0:
+             every other point has sigma = 0 and keeps it, so a cell outside the support has sigma = 0 at all 8 corners for ever.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from .baked import BakedField, _check, _ray_args, _stream, _unpack_words, check_render_args, check_threshold, n_coefficients
+
+
+def check_optimizer_args(learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation):
+    """ValueError unless both learning rates and epsilon are finite and > 0, both betas lie in [0, 1) and dilation is an integer 0..8
+    (what knerf_occupancy_from_grid takes); returns them as (float, float, float, float, float, int)"""
+    def number(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not np.isfinite(float(v)):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+        return float(v)
+    lrs, lrc = number("learning_rate_sigma", learning_rate_sigma), number("learning_rate_sh", learning_rate_sh)
+    b1, b2, eps = number("beta_1", beta_1), number("beta_2", beta_2), number("epsilon", epsilon)
+    if not (lrs > 0.0 and lrc > 0.0):
+        raise ValueError(f"learning rates must be > 0, got {learning_rate_sigma!r} and {learning_rate_sh!r}")
+    if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+        raise ValueError(f"beta_1 and beta_2 must lie in [0, 1), got {beta_1!r} and {beta_2!r}")
+    if not np.float32(eps) > 0.0:
+        raise ValueError(f"epsilon must be > 0 (as a float32), got {epsilon!r}")
+    if isinstance(dilation, bool) or not isinstance(dilation, (int, np.integer)) or not 0 <= int(dilation) <= 8:
+        raise ValueError(f"dilation must be an integer 0..8, got {dilation!r}")
+    return lrs, lrc, b1, b2, eps, int(dilation)
+
+
+def check_target_shape(shape, n_rays) -> None:
+    """ValueError unless a target of this shape is [n_rays, 3]"""
+    if len(shape) != 2 or shape[1] != 3 or shape[0] != n_rays:
+        raise ValueError(f"target must be [{n_rays}, 3], one colour per ray; got {tuple(shape)}")
+
+
+def bias_corrected_rate(learning_rate: float, beta_1: float, beta_2: float, t: int) -> float:
+    """Keras-form Adam: learning_rate sqrt(1 - beta_2^t) / (1 - beta_1^t) in double, t the step being applied (from 1)"""
+    return float(learning_rate) * float(np.sqrt(1.0 - float(beta_2) ** t)) / (1.0 - float(beta_1) ** t)
+
+
+class BakedFieldOptimizer:
+    """Adam on the records of a baked field (BakedField.optimizer builds one).  `field` is the live field: it owns the records the
+    optimiser rewrites, its bits are the support, and it can be rendered at any time."""
+
+    def __init__(self, source, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
+                 white_background=False, termination=0.0, lanes_per_ray=0):
+        import torch
+        from . import _lib
+        from .runtime import occupancy_words_from_grid
+        self.learning_rate_sigma, self.learning_rate_sh, self.beta_1, self.beta_2, self.epsilon, self.dilation = \
+            check_optimizer_args(learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation)
+        check_render_args(step, termination, ("image",), source.sh_degree, lanes_per_ray)
+        self.step, self.white_background, self.termination, self.lanes_per_ray = step, bool(white_background), float(termination), \
+            int(lanes_per_ray)
+        dev, res, deg = source.device, source.resolution, source.sh_degree
+        K = n_coefficients(deg)
+        self._width = 1 + 3 * K
+        sigma = source.sigma
+        support = occupancy_words_from_grid(sigma, 0.0, self.dilation, what="BakedField.optimizer")
+        self.field = BakedField(source._records.clone(), support, res, source.bounds, deg, source.sigma_threshold)
+        cells = tuple(r - 1 for r in res)
+        occ = _unpack_words(support, cells)
+        cx, cy, cz = cells
+        touched = torch.zeros(res, device=dev, dtype=torch.bool)
+        # a point's sigma is trainable when none of its 8 adjacent cells is a lattice cell outside the support
+        free = torch.ones(res, device=dev, dtype=torch.bool)
+        for a in (0, 1):
+            for b in (0, 1):
+                for c in (0, 1):
+                    touched[a:a + cx, b:b + cy, c:c + cz] |= occ
+                    free[a:a + cx, b:b + cy, c:c + cz] &= occ
+        index = touched.reshape(-1).nonzero().reshape(-1)                   # int64, ascending: the lattice point of every slot
+        self.n_slots = int(index.numel())                                   # the one host read of the construction
+        if self.n_slots == 0:
+            raise ValueError("the field has no occupied cell: there is nothing to optimise")
+        self._index = index
+        self._point_of = index.to(torch.int32)
+        self._slot_of = torch.full((touched.numel(),), -1, device=dev, dtype=torch.int32)
+        self._slot_of[index] = torch.arange(self.n_slots, device=dev, dtype=torch.int32)
+        self._trainable = free.reshape(-1)[index].to(torch.uint8).contiguous()
+        co = source.coefficients.reshape(-1, 3 * K)[index].to(torch.float32)
+        sg = sigma.reshape(-1)[index] * self._trainable.to(torch.float32)   # elsewhere sigma is 0 by the construction of the bits
+        self._master = torch.cat([sg[:, None], co], dim=1).contiguous()
+        self._grad = torch.zeros_like(self._master)
+        self._m, self._v = torch.zeros_like(self._master), torch.zeros_like(self._master)
+        self.iterations = 0                                                 # steps applied; the host's count, no device read
+        self._c = _lib.KnerfBakedTrain(self.field._c, C.c_void_p(self._slot_of.data_ptr()), C.c_void_p(self._grad.data_ptr()),
+                                       self.n_slots)
+
+    # ---- the two launches
+    def accumulate(self, origins, directions, near, far, target, n_total=None):
+        """knerf_baked_train_rays: adds the gradient of the batch's mean squared error to the gradient rows and returns the loss, a
+        float64 device scalar (the per-ray errors are summed in float64 on the device; nothing waits).  n_total: the N of the loss
+        1 / (3 N) sum (out - target)^2 when the batch is one part of several accumulated before apply() (default: this batch's rays)."""
+        import torch
+        from . import _lib
+        from .runtime import _f32, _ptr
+        f = self.field
+        o, d, n, h, (near_t, near0), (far_t, far0) = _ray_args(f, origins, directions, near, far, self.step)
+        tg = _f32(target, f.device)
+        check_target_shape(tuple(tg.shape), n)
+        norm = n if n_total is None else int(n_total)
+        if norm < 1 and n:
+            raise ValueError(f"n_total must be a positive ray count, got {n_total!r}")
+        sq = torch.empty((n,), device=f.device, dtype=torch.float32)
+        flags = (_lib.BAKED_WHITE_BACKGROUND if self.white_background else 0) | _lib.BAKED_SKIP_EMPTY | \
+            (self.lanes_per_ray << _lib.BAKED_LANES_SHIFT)
+        if n:
+            _check(_lib.load().knerf_baked_train_rays(_stream(f.device), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t), _ptr(far_t),
+                                                      near0, far0, _ptr(tg), n, norm, h, self.termination, flags, _ptr(sq)),
+                   "knerf_baked_train_rays")
+        return sq.to(torch.float64).sum() / (3.0 * max(norm, 1))
+
+    def apply(self):
+        """knerf_baked_train_apply: one Adam step from the accumulated gradient, the records rewritten, the gradient zeroed"""
+        from . import _lib
+        from .runtime import _ptr
+        t = self.iterations + 1
+        _check(_lib.load().knerf_baked_train_apply(
+            _stream(self.field.device), C.byref(self._c), _ptr(self._point_of), _ptr(self._trainable), _ptr(self._master), _ptr(self._m),
+            _ptr(self._v), bias_corrected_rate(self.learning_rate_sigma, self.beta_1, self.beta_2, t),
+            bias_corrected_rate(self.learning_rate_sh, self.beta_1, self.beta_2, t), self.beta_1, self.beta_2, self.epsilon),
+            "knerf_baked_train_apply")
+        self.iterations = t
+
+    def train_step(self, origins, directions, near, far, target):
+        """accumulate + apply; returns the batch's loss before the step (float64 device scalar)"""
+        loss = self.accumulate(origins, directions, near, far, target)
+        self.apply()
+        return loss
+
+    def fit(self, batches, near, far, steps=None):
+        """train_step on every batch of `batches` (each (target [n,3], (origins, directions, t)) as RayBatchDataset yields them; t is
+        not used: the baked march places its own samples), at most `steps` of them.  {"loss": [...]}: read from the device once, after
+        the last step."""
+        import torch
+        if steps is not None and (isinstance(steps, bool) or int(steps) != steps or int(steps) < 0):
+            raise ValueError(f"steps must be a non-negative integer or None, got {steps!r}")
+        losses = []
+        for k, (target, (o, d, _t)) in enumerate(batches):
+            if steps is not None and k >= int(steps):
+                break
+            losses.append(self.train_step(o, d, near, far, target))
+        return {"loss": torch.stack(losses).cpu().tolist() if losses else []}
+
+    # ---- views for tests and tools
+    def gradients(self):
+        """(g_sigma [Rx,Ry,Rz], g_coef [Rx,Ry,Rz,K,3]): dense fp32 copies of the accumulated gradient, zero outside the slots"""
+        import torch
+        res, K = self.field.resolution, n_coefficients(self.field.sh_degree)
+        P = int(np.prod(res))
+        gs = torch.zeros((P,), device=self.field.device, dtype=torch.float32)
+        gc = torch.zeros((P, 3 * K), device=self.field.device, dtype=torch.float32)
+        gs[self._index] = self._grad[:, 0]
+        gc[self._index] = self._grad[:, 1:]
+        return gs.reshape(res), gc.reshape(res + (K, 3))
+
+    @property
+    def slot_mask(self):
+        """bool [Rx,Ry,Rz] on the device: the lattice points that have a slot"""
+        return (self._slot_of >= 0).reshape(self.field.resolution)
+
+    @property
+    def sigma_trainable(self):
+        """bool [Rx,Ry,Rz] on the device: the lattice points whose sigma the optimiser may change"""
+        import torch
+        out = torch.zeros((self._slot_of.numel(),), device=self.field.device, dtype=torch.bool)
+        out[self._index] = self._trainable.bool()
+        return out.reshape(self.field.resolution)
+
+    def finish(self, sigma_threshold=None):
+        """An ordinary BakedField from the live one: every sigma <= sigma_threshold (default: the field's own) stored as 0 and the
+        occupancy bits rebuilt from sigma (a subset of the support, so skipping stays exact).  The optimiser stays usable."""
+        import torch
+        from .runtime import occupancy_words_from_grid
+        f = self.field
+        thr = f.sigma_threshold if sigma_threshold is None else check_threshold(sigma_threshold)
+        sigma = f.sigma
+        sigma = torch.where(sigma > thr, sigma, torch.zeros_like(sigma)).contiguous()
+        records = f._records.clone()
+        records[:, :4] = sigma.reshape(-1, 1).view(torch.uint8)
+        words = occupancy_words_from_grid(sigma, 0.0, 0, what="BakedFieldOptimizer.finish")
+        return BakedField(records, words, f.resolution, f.bounds, f.sh_degree, thr)
