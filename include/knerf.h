@@ -555,6 +555,42 @@ int knerf_baked_train_rays(void* stream, const knerf_baked_train* train, const f
 int knerf_baked_train_apply(void* stream, const knerf_baked_train* train, const int32_t* point_of, const uint8_t* sigma_trainable,
                             float* master, float* m, float* v, float rate_sigma, float rate_sh, float beta_1, float beta_2, float epsilon);
 
+/* ---- Growing a baked field: a total-variation regulariser for the optimiser above and resampling onto another lattice (coarse to
+ * fine).  Extension, no reference counterpart (Plenoxels regularises and refines its grid in this way).  Two context-free launches;
+ * csrc/baked_grow.hip, tests/baked_grow_reference.py restates them in NumPy. */
+/* knerf_baked_train_tv -- extension, no reference counterpart.  ADDS to grad the gradient of
+ *   R = weight_sigma sum_p tv_sigma(p) + weight_sh sum_p sum_{q != sigma} tv_q(p),    p over the slots, q over the columns of a row,
+ *   tv_q(p) = sqrtf(D_x^2 + D_y^2 + D_z^2 + epsilon),   D_a q(p) = v_q(p + e_a) - v_q(p) if p + e_a lies in the lattice AND has a slot,
+ *   otherwise 0;  v_q(p) = master[slot_of[p]][q], the fp32 master value (master, point_of: as knerf_baked_train_apply).  Points without
+ * a slot never enter, whatever their record holds.  The sigma column of a slot that is not trainable takes part as a value (its
+ * master is 0) and its gradient is written like any other: knerf_baked_train_apply ignores it.  The caller passes the weights PER
+ * TERM (the Python package: lambda_sigma / n_slots and lambda_sh / (3 K n_slots), formed in double).
+ * The gradient is a gather: per (slot, column), in fp32,
+ *   g = w [ -sum_a D_a(p) / tv(p) + sum_a D_a(p - e_a) / tv(p - e_a) ],    the second sum over the predecessors that have a slot,
+ * formed in registers and added to grad with ONE fp32 add and no atomics: grad_after = fp32(grad_before + g) exactly, and two calls
+ * from the same state give the same bits.  A weight of exactly 0 leaves the columns of its group untouched, bit for bit.
+ * tv_out: fp32 [n_slots][2] or NULL; [p][0] = tv_sigma(p), [p][1] = sum_{q != sigma} tv_q(p) (summed in double in column order, rounded
+ * once), unweighted, plain stores.  With both weights 0 and tv_out NULL nothing is launched.
+ * KNERF_ERR_INVALID, before any launch: NULL train, point_of or master; epsilon <= 0 or not finite; a weight that is negative or not
+ * finite; every struct error of knerf_baked_train_apply. */
+int knerf_baked_train_tv(void* stream, const knerf_baked_train* train, const int32_t* point_of, const float* master, float weight_sigma,
+                         float weight_sh, float epsilon, float* tv_out);
+/* knerf_baked_resample -- extension, no reference counterpart.  The records of the field src on another lattice dst_resolution (HOST
+ * [3], 2 <= R' <= 1025 per axis, points x record bytes < 2^40) over the same [lo, hi], same sh_degree.  New index i of an axis with R old
+ * and R' new points:  u = (double)i (R - 1) / (R' - 1) in double,  cell = min(floor(u), R - 2),  f = (float)(u - cell).  Every
+ * value is interpolated trilinearly from the 8 old points of the cell, along z, then y, then x, each step
+ *   lerp(a, b, f) = __fadd_rn(__fmul_rn(a, __fsub_rn(1, f)), __fmul_rn(b, f))       (no fused multiply-add)
+ * so that f = 0 returns a and f = 1 returns b exactly.  sigma is interpolated in fp32 and a result <= sigma_threshold is stored as
+ * exactly 0; coefficients go fp16 -> fp32 -> interpolate -> fp16 (nearest even); the padding is written as zeros.  src->bits is not
+ * read.  Consequences: an old cell with sigma = 0 at its 8 corners gives sigma = 0 at every new point inside it, so
+ * knerf_occupancy_from_grid(sigma', 0, 0) yields bits that are exact for skipping; with R' = 2 R - 1 every old point reappears with
+ * its values unchanged as numbers; the first and last point of an axis are kept for every R'.
+ * KNERF_ERR_INVALID, before any launch: NULL src, records, dst_resolution or dst_records; sh_degree outside 0..3; a resolution (old
+ * or new) outside 2..1025; lo / hi not finite or hi <= lo; either table of 2^40 bytes or more; sigma_threshold negative or not
+ * finite; dst_records overlapping the source records. */
+int knerf_baked_resample(void* stream, const knerf_baked_field* src, const int32_t dst_resolution[3], float sigma_threshold,
+                         void* dst_records);
+
 /* Diagnostics (layout tables, workspace views, hardware-fact and bandwidth probes) are NOT part of this library: they are
  * declared in include/knerf_debug.h and built into libknerf_probe.so for tests/ and tools/ only. */
 

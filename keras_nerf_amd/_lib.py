@@ -134,6 +134,8 @@ SIGNATURES = {
                                          C.c_float, C.c_float, C.c_int, _F]),
     "knerf_baked_train_apply": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _P, _P, _F, _F, _F, C.c_float, C.c_float, C.c_float, C.c_float,
                                           C.c_float]),
+    "knerf_baked_train_tv": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _P, _F, C.c_float, C.c_float, C.c_float, _F]),
+    "knerf_baked_resample": (C.c_int, [_P, C.POINTER(KnerfBakedField), C.POINTER(C.c_int32), C.c_float, _P]),
 }
 
 _lib = None

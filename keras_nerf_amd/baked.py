@@ -2,7 +2,8 @@
 no reference counterpart; PlenOctrees, SNeRG and Plenoxels bake a trained NeRF in this way).
 
 The arithmetic is HIP (csrc/baked.hip: knerf_baked_project, knerf_baked_pack, knerf_baked_render; include/knerf.h holds the contract;
-BakedField.optimizer and baked_train.py: optimising the records against ray batches, csrc/baked_train.hip);
+BakedField.optimizer and baked_train.py: optimising the records against ray batches, csrc/baked_train.hip;
+BakedField.resample and the optimiser's TV regulariser: csrc/baked_grow.hip);
 torch is used for device memory, streams and the index plumbing of the bake only.  Host-side pieces (basis, fit matrix, record
 layout) are NumPy and need no device.
 """
@@ -150,6 +151,19 @@ def check_threshold(sigma_threshold) -> float:
     return thr
 
 
+def refined_resolution(resolution):
+    """the lattice of one refinement, 2 r - 1 points per axis (every old point reappears in BakedField.resample, a new one sits in the
+    middle of every old edge); an int or three ints -> a 3-tuple.  ValueError on a resolution outside 2..1025 and past 1025 points"""
+    res = (resolution,) * 3 if isinstance(resolution, (int, np.integer)) and not isinstance(resolution, bool) else \
+        (tuple(resolution) if isinstance(resolution, (tuple, list, np.ndarray)) else ())
+    if len(res) != 3 or any(isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 2 <= int(r) <= 1025 for r in res):
+        raise ValueError(f"resolution must be an int or three ints, each 2..1025 lattice points; got {resolution!r}")
+    out = tuple(2 * int(r) - 1 for r in res)
+    if max(out) > 1025:
+        raise ValueError(f"refining {tuple(int(r) for r in res)} gives {out}: more than 1025 lattice points on an axis")
+    return out
+
+
 def check_render_args(step, termination, outputs, sh_degree=None, lanes_per_ray=0):
     """ValueError on step <= 0, termination outside [0, 1), unknown outputs or a lane count the degree does not have"""
     if step is not None and not (np.isfinite(float(step)) and float(step) > 0.0):
@@ -267,6 +281,53 @@ class BakedField:
             field._pack(sg, acc, None, torch.arange(s0, s0 + acc.shape[0], device=dev, dtype=torch.int64))
         return field
 
+    @classmethod
+    def uniform(cls, resolution, bounds, sh_degree, sigma=0.1, colour=0.5, device=None):
+        """A field with the same record at every lattice point, built on the device: density `sigma` (finite, >= 0) and the grey
+        `colour` in every direction (the DC coefficient is colour 2 sqrt(pi) = colour / Y_0, all other coefficients are 0): what a
+        grid trainer starts from when there is no MLP to bake (baked_train.fit_coarse_to_fine).  sigma_threshold is 0."""
+        import torch
+        from .runtime import occupancy_words_from_grid
+        deg = check_degree(sh_degree)
+        res, lo, hi = check_lattice_spec(resolution, bounds, deg)
+        for name, v in (("sigma", sigma), ("colour", colour)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not np.isfinite(np.float32(v)):
+                raise ValueError(f"{name} must be a finite number, got {v!r}")
+        if float(sigma) < 0.0:
+            raise ValueError(f"sigma must be >= 0, got {sigma!r}")
+        with np.errstate(over="ignore"):
+            dc = np.float16(float(colour) * 2.0 * np.sqrt(np.pi))
+        if not np.isfinite(dc):
+            raise ValueError(f"colour {colour!r} gives a DC coefficient that is no finite float16")
+        K = n_coefficients(deg)
+        co = np.zeros((1, K, 3), dtype=np.float16)
+        co[0, 0, :] = dc
+        one = pack_records(np.full((1,), sigma, dtype=np.float32), co)
+        dev = torch.device(device if device is not None else "cuda")
+        n = res[0] * res[1] * res[2]
+        records = torch.as_tensor(one).to(dev).repeat(n, 1).contiguous()
+        words = occupancy_words_from_grid(torch.full(res, float(np.float32(sigma)), device=dev, dtype=torch.float32), 0.0, 0,
+                                          what="BakedField.uniform")
+        return cls(records, words, res, (lo, hi), deg, 0.0)
+
+    def resample(self, resolution, sigma_threshold=None):
+        """This field on another lattice (an int or three ints, 2..1025 points per axis) over the same box: knerf_baked_resample
+        (trilinear, specified in include/knerf.h), every new sigma <= sigma_threshold (default: the field's own) stored as 0 and the
+        occupancy bits rebuilt from the new sigma.  A cell that was empty stays empty, so skipping stays exact; with
+        refined_resolution(self.resolution) every old lattice point keeps its values.  This field is left as it is."""
+        import torch
+        from . import _lib
+        from .runtime import _ptr, occupancy_words_from_grid
+        res, _, _ = check_lattice_spec(resolution, self.bounds, self.sh_degree)
+        thr = self.sigma_threshold if sigma_threshold is None else check_threshold(sigma_threshold)
+        dev = self.device
+        records = torch.empty((res[0] * res[1] * res[2], record_bytes(self.sh_degree)), device=dev, dtype=torch.uint8)
+        _check(_lib.load().knerf_baked_resample(_stream(dev), C.byref(self._c), (C.c_int32 * 3)(*res), thr, _ptr(records)),
+               "knerf_baked_resample")
+        sigma = records[:, :4].contiguous().view(torch.float32).reshape(res)
+        words = occupancy_words_from_grid(sigma, 0.0, 0, what="BakedField.resample")
+        return BakedField(records, words, res, self.bounds, self.sh_degree, thr)
+
     # ---- the unpacked views
     @property
     def device(self):
@@ -359,18 +420,22 @@ class BakedField:
 
     # ---- optimisation against ray batches
     def optimizer(self, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
-                  white_background=False, termination=0.0, lanes_per_ray=0):
+                  white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6):
         """A BakedFieldOptimizer (baked_train.py) over a COPY of this field's records: Adam on sigma and the SH coefficients of the
         lattice points around the occupied cells (grown by `dilation` cells) against batches of rays and their colours; this field
-        itself is left as it is.  step, white_background, termination, lanes_per_ray: how the optimiser marches, as in render()."""
+        itself is left as it is.  step, white_background, termination, lanes_per_ray: how the optimiser marches, as in render().
+        tv_sigma, tv_sh (>= 0, default off): the weights of the total-variation regulariser on density and on the colour coefficients
+        (knerf_baked_train_tv; each is the weight of the MEAN term over the slots, resp. over the slots and the 3 K coefficient
+        columns), tv_epsilon (> 0) the constant under its root.  With both weights 0 a step is what it is without them."""
         from .baked_train import BakedFieldOptimizer
         return BakedFieldOptimizer(self, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
-                                   termination, lanes_per_ray)
+                                   termination, lanes_per_ray, tv_sigma, tv_sh, tv_epsilon)
 
 
 def __getattr__(name):
     """the optimiser's names live in baked_train.py (which imports this module) and are reachable from here as well"""
-    if name in ("BakedFieldOptimizer", "check_optimizer_args", "check_target_shape", "bias_corrected_rate"):
+    if name in ("BakedFieldOptimizer", "check_optimizer_args", "check_target_shape", "bias_corrected_rate", "check_tv_args",
+                "fit_coarse_to_fine"):
         from . import baked_train
         return getattr(baked_train, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

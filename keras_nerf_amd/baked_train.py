@@ -2,7 +2,8 @@
 against the photographs after conversion in this way).
 
 The arithmetic is HIP (csrc/baked_train.hip: knerf_baked_train_rays marches a batch, evaluates the squared error and scatters its
-gradient into the lattice; knerf_baked_train_apply is Adam and rewrites the records; include/knerf.h holds the contract).  torch is
+gradient into the lattice; knerf_baked_train_apply is Adam and rewrites the records; csrc/baked_grow.hip: knerf_baked_train_tv, the
+optional total-variation regulariser between the two, and the resampling behind fit_coarse_to_fine; include/knerf.h holds the contract).  torch is
 used for device memory, streams and the index plumbing of the construction only.  No step waits for the GPU.
 
 What keeps skipping empty cells exact while the numbers move:
@@ -42,6 +43,21 @@ def check_optimizer_args(learning_rate_sigma, learning_rate_sh, beta_1, beta_2, 
     return lrs, lrc, b1, b2, eps, int(dilation)
 
 
+def check_tv_args(tv_sigma, tv_sh, tv_epsilon):
+    """ValueError unless both total-variation weights are finite and >= 0 and tv_epsilon is finite and > 0 (as a float32); returns
+    them as floats"""
+    out = []
+    for name, v in (("tv_sigma", tv_sigma), ("tv_sh", tv_sh), ("tv_epsilon", tv_epsilon)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not np.isfinite(np.float32(v)):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+        out.append(float(v))
+    if out[0] < 0.0 or out[1] < 0.0:
+        raise ValueError(f"tv_sigma and tv_sh must be >= 0, got {tv_sigma!r} and {tv_sh!r}")
+    if not np.float32(out[2]) > 0.0:
+        raise ValueError(f"tv_epsilon must be > 0 (as a float32), got {tv_epsilon!r}")
+    return tuple(out)
+
+
 def check_target_shape(shape, n_rays) -> None:
     """ValueError unless a target of this shape is [n_rays, 3]"""
     if len(shape) != 2 or shape[1] != 3 or shape[0] != n_rays:
@@ -58,12 +74,14 @@ class BakedFieldOptimizer:
     optimiser rewrites, its bits are the support, and it can be rendered at any time."""
 
     def __init__(self, source, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
-                 white_background=False, termination=0.0, lanes_per_ray=0):
+                 white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6):
         import torch
         from . import _lib
         from .runtime import occupancy_words_from_grid
         self.learning_rate_sigma, self.learning_rate_sh, self.beta_1, self.beta_2, self.epsilon, self.dilation = \
             check_optimizer_args(learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation)
+        self.tv_sigma, self.tv_sh, self.tv_epsilon = check_tv_args(tv_sigma, tv_sh, tv_epsilon)
+        self.last_regularizer = None                                        # what the latest train_step's regularize() returned
         check_render_args(step, termination, ("image",), source.sh_degree, lanes_per_ray)
         self.step, self.white_background, self.termination, self.lanes_per_ray = step, bool(white_background), float(termination), \
             int(lanes_per_ray)
@@ -138,25 +156,59 @@ class BakedFieldOptimizer:
             "knerf_baked_train_apply")
         self.iterations = t
 
+    @property
+    def regularized(self) -> bool:
+        """whether a total-variation weight is > 0: train_step then runs regularize() between accumulate() and apply()"""
+        return self.tv_sigma > 0.0 or self.tv_sh > 0.0
+
+    def tv_weights(self):
+        """the weights per term knerf_baked_train_tv takes, formed in double: tv_sigma / n_slots and tv_sh / (3 K n_slots)"""
+        return self.tv_sigma / float(self.n_slots), self.tv_sh / (float(self._width - 1) * float(self.n_slots))
+
+    def regularize(self):
+        """knerf_baked_train_tv, one launch: adds the gradient of R = tv_sigma mean_p tv_sigma(p) + tv_sh mean_{p,q} tv_q(p) (the total
+        variation of the master values over the slots, include/knerf.h) to the gradient rows and returns the two means, unweighted,
+        as float64 device scalars (the per-slot terms are summed in float64 on the device; nothing waits)."""
+        import torch
+        from . import _lib
+        from .runtime import _ptr
+        dev = self.field.device
+        tv = torch.empty((self.n_slots, 2), device=dev, dtype=torch.float32)
+        ws, wc = self.tv_weights()
+        _check(_lib.load().knerf_baked_train_tv(_stream(dev), C.byref(self._c), _ptr(self._point_of), _ptr(self._master), ws, wc,
+                                                self.tv_epsilon, _ptr(tv)), "knerf_baked_train_tv")
+        total = tv.to(torch.float64).sum(dim=0)
+        return total[0] / float(self.n_slots), total[1] / (float(self._width - 1) * float(self.n_slots))
+
     def train_step(self, origins, directions, near, far, target):
-        """accumulate + apply; returns the batch's loss before the step (float64 device scalar)"""
+        """accumulate, regularize (only when a total-variation weight is > 0; its return value is kept in last_regularizer), apply;
+        returns the batch's loss before the step (float64 device scalar, the data term alone)"""
         loss = self.accumulate(origins, directions, near, far, target)
+        if self.regularized:
+            self.last_regularizer = self.regularize()
         self.apply()
         return loss
 
     def fit(self, batches, near, far, steps=None):
         """train_step on every batch of `batches` (each (target [n,3], (origins, directions, t)) as RayBatchDataset yields them; t is
         not used: the baked march places its own samples), at most `steps` of them.  {"loss": [...]}: read from the device once, after
-        the last step."""
+        the last step.  With a total-variation weight > 0 the dict also holds "tv_sigma" and "tv_sh": regularize()'s two means per
+        step."""
         import torch
         if steps is not None and (isinstance(steps, bool) or int(steps) != steps or int(steps) < 0):
             raise ValueError(f"steps must be a non-negative integer or None, got {steps!r}")
-        losses = []
+        losses, tvs = [], []
         for k, (target, (o, d, _t)) in enumerate(batches):
             if steps is not None and k >= int(steps):
                 break
             losses.append(self.train_step(o, d, near, far, target))
-        return {"loss": torch.stack(losses).cpu().tolist() if losses else []}
+            if self.regularized:
+                tvs.append(torch.stack(self.last_regularizer))
+        out = {"loss": torch.stack(losses).cpu().tolist() if losses else []}
+        if self.regularized:
+            both = torch.stack(tvs).cpu() if tvs else torch.zeros((0, 2))
+            out["tv_sigma"], out["tv_sh"] = both[:, 0].tolist(), both[:, 1].tolist()
+        return out
 
     # ---- views for tests and tools
     def gradients(self):
@@ -196,3 +248,45 @@ class BakedFieldOptimizer:
         records[:, :4] = sigma.reshape(-1, 1).view(torch.uint8)
         words = occupancy_words_from_grid(sigma, 0.0, 0, what="BakedFieldOptimizer.finish")
         return BakedField(records, words, f.resolution, f.bounds, f.sh_degree, thr)
+
+
+def check_stages(stages):
+    """ValueError unless stages is a non-empty sequence of (resolution | None, steps) with steps a non-negative integer; returns
+    them as a list of (resolution | None, int).  The resolutions themselves are checked by BakedField.resample."""
+    try:
+        out = [(r, s) for r, s in stages]
+    except (TypeError, ValueError):
+        raise ValueError(f"stages must be a sequence of (resolution | None, steps), got {stages!r}") from None
+    if not out:
+        raise ValueError("stages must name at least one stage")
+    for r, s in out:
+        if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or int(s) < 0:
+            raise ValueError(f"the steps of a stage must be a non-negative integer, got {s!r}")
+    return [(r, int(s)) for r, s in out]
+
+
+def fit_coarse_to_fine(field, batches, near, far, stages, **optimizer_kwargs):
+    """Coarse-to-fine optimisation of a baked field: for every stage (resolution | None, steps) in turn the field is resampled onto
+    `resolution` (BakedField.resample; None keeps the lattice), an optimiser is built on it (field.optimizer(**optimizer_kwargs):
+    learning rates, dilation, march and total-variation keywords), fit for `steps` batches and finished (finish()).  `batches` is
+    consumed continuously: a stage goes on where the one before stopped, and no batch is dropped in between.
+
+    Adam's moments are NOT carried across stages.  A resample changes the lattice, the support and with them the set of slots, so
+    every stage gets a new slot set and a fresh optimiser whose moments start at zero and whose bias correction starts at t = 1.
+
+    Returns (the finished field of the last stage, history): history["loss"] (and "tv_sigma", "tv_sh" when a weight is > 0) run over
+    all stages, history["stages"] holds one {"resolution", "steps", "n_slots"} per stage (steps: those actually run)."""
+    import itertools
+    todo = check_stages(stages)
+    it = iter(batches)
+    history = {"loss": [], "stages": []}
+    for resolution, steps in todo:
+        if resolution is not None:
+            field = field.resample(resolution)
+        opt = field.optimizer(**optimizer_kwargs)
+        hist = opt.fit(itertools.islice(it, steps), near, far)
+        for key, values in hist.items():
+            history.setdefault(key, []).extend(values)
+        history["stages"].append({"resolution": tuple(field.resolution), "steps": len(hist["loss"]), "n_slots": opt.n_slots})
+        field = opt.finish()
+    return field, history
