@@ -591,6 +591,41 @@ int knerf_baked_train_tv(void* stream, const knerf_baked_train* train, const int
 int knerf_baked_resample(void* stream, const knerf_baked_field* src, const int32_t dst_resolution[3], float sigma_threshold,
                          void* dst_records);
 
+/* ---- The baked field as sparse bricks.  Extension, no reference counterpart (PlenOctrees, SNeRG's macroblock atlas and Plenoxels store
+ * only the occupied part of their grids behind a coarse index).  One context-free launch; csrc/baked_bricks.hip,
+ * tests/baked_bricks_reference.py restates the format in NumPy.
+ * The lattice [Rx,Ry,Rz] of a baked field is cut into bricks of b^3 lattice points, b = 1 << brick_log2 = 4 or 8.  Point (x, y, z)
+ * lies in brick (x >> brick_log2, y >> brick_log2, z >> brick_log2) of the brick grid B_a = ceil(R_a / b), at place
+ * ((x & (b-1)) b + (y & (b-1))) b + (z & (b-1)) inside it.  A brick is STORED iff it holds at least one touched point (a corner of a
+ * cell whose occupancy bit is set); stored bricks are numbered 0..n_bricks-1 in ascending C order of the brick index.
+ *   brick_of: int32 [Bx][By][Bz], the slot of a stored brick, -1 for an absent one;
+ *   records:  [n_bricks][b^3] records in the layout above; a stored brick is a verbatim copy of the dense records of all its points
+ *             (untouched ones included), points of an edge brick outside the lattice are all-zero records;
+ *   bits:     the occupancy bitfield of the dense field, unchanged.
+ * A point of an absent brick reads as an all-zero record.  A brick_of value < 0 or >= n_bricks is treated as absent by the kernel: a
+ * damaged table never becomes an out-of-range read.  n_bricks >= 1: a field without an occupied cell carries one all-zero brick 0 that
+ * no brick_of entry names.  n_bricks x b^3 x record bytes must stay below 2^40; every element offset is computed in 64 bits. */
+typedef struct knerf_baked_bricks {
+    const void* records;         /* DEVICE */
+    const int32_t* brick_of;     /* DEVICE */
+    const uint32_t* bits;        /* DEVICE, may be NULL without KNERF_BAKED_SKIP_EMPTY */
+    int32_t resolution[3];       /* lattice points per axis */
+    int32_t sh_degree;           /* 0..3 */
+    float lo[3], hi[3];
+    int32_t brick_log2;          /* 2 or 3 */
+    uint64_t n_bricks;
+} knerf_baked_bricks;
+/* knerf_baked_render_bricks -- extension, no reference counterpart.  knerf_baked_render through the brick table: the same march (sample
+ * positions, cell lookup, corner order, fused multiply-adds, lane variants, batches of occupancy words, termination, stats), every
+ * argument behind `field` as there.  Only the address of a corner's record differs, so for a brick field that holds the dense field's
+ * stored bricks all outputs and stats are bit-identical to knerf_baked_render's: an absent brick holds no corner of an occupied cell,
+ * the dense sigma there is 0, and a sample whose sigma is 0 adds +0 whatever its colour is.
+ * KNERF_ERR_INVALID, before any launch: everything knerf_baked_render refuses; a NULL brick_of; brick_log2 outside {2, 3}; n_bricks = 0
+ * or above Bx By Bz; n_bricks x b^3 x record bytes >= 2^40. */
+int knerf_baked_render_bricks(void* stream, const knerf_baked_bricks* field, const float* origins, const float* directions,
+                              const float* near, const float* far, float near_all, float far_all, uint64_t n_rays, float step,
+                              float termination, int flags, float* image, float* depth, float* opacity, int64_t* stats);
+
 /* Diagnostics (layout tables, workspace views, hardware-fact and bandwidth probes) are NOT part of this library: they are
  * declared in include/knerf_debug.h and built into libknerf_probe.so for tests/ and tools/ only. */
 

@@ -49,6 +49,14 @@ class KnerfBakedTrain(C.Structure):
     _fields_ = [("field", KnerfBakedField), ("slot_of", C.c_void_p), ("grad", C.c_void_p), ("n_slots", C.c_uint64)]
 
 
+class KnerfBakedBricks(C.Structure):
+    """struct knerf_baked_bricks (include/knerf.h): device brick records, brick table and occupancy bits, the lattice, log2 of the brick
+    edge, the number of stored bricks"""
+    _fields_ = [("records", C.c_void_p), ("brick_of", C.c_void_p), ("bits", C.c_void_p), ("resolution", C.c_int32 * 3),
+                ("sh_degree", C.c_int32), ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("brick_log2", C.c_int32),
+                ("n_bricks", C.c_uint64)]
+
+
 BAKED_WHITE_BACKGROUND, BAKED_SKIP_EMPTY, BAKED_LANES_SHIFT = 1, 2, 8
 SPACING_LINEAR, SPACING_DISPARITY = 0, 1
 SPACINGS = {"linear": SPACING_LINEAR, "disparity": SPACING_DISPARITY}
@@ -136,6 +144,8 @@ SIGNATURES = {
                                           C.c_float]),
     "knerf_baked_train_tv": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _P, _F, C.c_float, C.c_float, C.c_float, _F]),
     "knerf_baked_resample": (C.c_int, [_P, C.POINTER(KnerfBakedField), C.POINTER(C.c_int32), C.c_float, _P]),
+    "knerf_baked_render_bricks": (C.c_int, [_P, C.POINTER(KnerfBakedBricks), _F, _F, _F, _F, C.c_float, C.c_float, C.c_uint64, C.c_float,
+                                            C.c_float, C.c_int, _F, _F, _F, _P]),
 }
 
 _lib = None

@@ -3,7 +3,8 @@ no reference counterpart; PlenOctrees, SNeRG and Plenoxels bake a trained NeRF i
 
 The arithmetic is HIP (csrc/baked.hip: knerf_baked_project, knerf_baked_pack, knerf_baked_render; include/knerf.h holds the contract;
 BakedField.optimizer and baked_train.py: optimising the records against ray batches, csrc/baked_train.hip;
-BakedField.resample and the optimiser's TV regulariser: csrc/baked_grow.hip);
+BakedField.resample and the optimiser's TV regulariser: csrc/baked_grow.hip;
+BrickBakedField, the same field stored as sparse bricks behind an index table, and its renderer: csrc/baked_bricks.hip);
 torch is used for device memory, streams and the index plumbing of the bake only.  Host-side pieces (basis, fit matrix, record
 layout) are NumPy and need no device.
 """
@@ -111,6 +112,82 @@ def unpack_records(records: np.ndarray, sh_degree: int):
     sg = np.ascontiguousarray(rec[:, :4]).view(np.float32).reshape(-1)
     co = np.ascontiguousarray(rec[:, 4:4 + 6 * K]).view(np.float16).reshape(-1, K, 3)
     return sg, co
+
+
+BRICKS = (4, 8)            # lattice points per brick edge a BrickBakedField can have
+DEFAULT_BRICK = 8
+
+
+def check_brick(brick) -> int:
+    if isinstance(brick, bool) or not isinstance(brick, (int, np.integer)) or int(brick) not in BRICKS:
+        raise ValueError(f"brick must be one of {BRICKS} lattice points per edge, got {brick!r}")
+    return int(brick)
+
+
+def brick_grid(resolution, brick: int):
+    """the brick grid of a lattice: ceil(R / b) bricks per axis"""
+    return tuple((int(r) + brick - 1) // brick for r in resolution)
+
+
+def brick_table(occupied, resolution, brick=DEFAULT_BRICK):
+    """NumPy mirror of the brick table (include/knerf.h knerf_baked_bricks): occupied bool [Rx-1,Ry-1,Rz-1] -> (brick_of int32
+    [Bx,By,Bz], n_bricks).  A brick is stored iff it holds a touched point (a corner of an occupied cell); stored bricks are numbered
+    in ascending C order; -1 marks an absent one.  n_bricks >= 1: without an occupied cell brick 0 exists and no entry names it."""
+    b = check_brick(brick)
+    res = tuple(int(r) for r in resolution)
+    occ = np.asarray(occupied, dtype=bool)
+    if occ.shape != tuple(r - 1 for r in res):
+        raise ValueError(f"occupied must be {tuple(r - 1 for r in res)} cells for a {res} lattice, got {occ.shape}")
+    B = brick_grid(res, b)
+    touched = np.zeros(tuple(n * b for n in B), dtype=bool)
+    cx, cy, cz = occ.shape
+    for i in (0, 1):
+        for j in (0, 1):
+            for k in (0, 1):
+                touched[i:i + cx, j:j + cy, k:k + cz] |= occ
+    stored = touched.reshape(B[0], b, B[1], b, B[2], b).any(axis=(1, 3, 5))
+    n = int(stored.sum())
+    brick_of = np.full(B, -1, dtype=np.int32)
+    brick_of[stored] = np.arange(n, dtype=np.int32)
+    return brick_of, max(n, 1)
+
+
+def _brick_points(brick_of, resolution, b):
+    """for the stored bricks of a NumPy table in slot order: (lattice index [n, b^3] int64, clipped into the lattice; inside [n, b^3] bool)"""
+    res = tuple(int(r) for r in resolution)
+    ids = np.argwhere(np.asarray(brick_of) >= 0)                           # ascending C order = slot order
+    ax = np.arange(b)
+    x = (ids[:, 0, None] * b + ax)[:, :, None, None]
+    y = (ids[:, 1, None] * b + ax)[:, None, :, None]
+    z = (ids[:, 2, None] * b + ax)[:, None, None, :]
+    inside = (x < res[0]) & (y < res[1]) & (z < res[2])
+    lin = (np.minimum(x, res[0] - 1) * res[1] + np.minimum(y, res[1] - 1)) * res[2] + np.minimum(z, res[2] - 1)
+    return lin.reshape(len(ids), b ** 3).astype(np.int64), inside.reshape(len(ids), b ** 3)
+
+
+def bricks_from_dense(records, brick_of, n_bricks, resolution, brick=DEFAULT_BRICK):
+    """NumPy mirror of BakedField.compact: dense records uint8 [P, record bytes] -> uint8 [n_bricks, b^3, record bytes]; a stored brick
+    is a verbatim copy of its points' records, points outside the lattice are all-zero"""
+    b = check_brick(brick)
+    rec = np.asarray(records, dtype=np.uint8)
+    out = np.zeros((int(n_bricks), b ** 3, rec.shape[1]), dtype=np.uint8)
+    lin, inside = _brick_points(brick_of, resolution, b)
+    if len(lin):
+        out[:len(lin)] = np.where(inside[:, :, None], rec[lin], 0)
+    return out
+
+
+def dense_from_bricks(brick_records, brick_of, resolution, brick=DEFAULT_BRICK):
+    """NumPy mirror of BrickBakedField.to_dense: uint8 [n_bricks, b^3, record bytes] -> dense uint8 [P, record bytes]; records of
+    absent bricks are all-zero"""
+    b = check_brick(brick)
+    br = np.asarray(brick_records, dtype=np.uint8)
+    res = tuple(int(r) for r in resolution)
+    out = np.zeros((res[0] * res[1] * res[2], br.shape[2]), dtype=np.uint8)
+    lin, inside = _brick_points(brick_of, res, b)
+    if len(lin):
+        out[lin[inside]] = br[:len(lin)][inside]
+    return out
 
 
 def check_table_size(n_points: int, sh_degree: int) -> int:
@@ -431,6 +508,262 @@ class BakedField:
         return BakedFieldOptimizer(self, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
                                    termination, lanes_per_ray, tv_sigma, tv_sh, tv_epsilon)
 
+    # ---- sparse storage
+    def compact(self, brick=DEFAULT_BRICK):
+        """This field as a BrickBakedField: only the bricks of brick^3 lattice points (4 or 8) that hold a corner of an occupied cell
+        are kept, behind an index table (include/knerf.h knerf_baked_bricks).  It renders the same bits.  This field is left as it is."""
+        import torch
+        b = check_brick(brick)
+        brick_of, n = _brick_table_device(self.occupied, self.resolution, b)
+        check_table_size(max(n, 1) * b ** 3, self.sh_degree)
+        records = torch.zeros((max(n, 1), b ** 3, record_bytes(self.sh_degree)), device=self.device, dtype=torch.uint8)
+        _gather_bricks(self._records.view(torch.int32), brick_of, self.resolution, b, records.view(torch.int32))
+        return BrickBakedField(records, brick_of, self._words, self.resolution, self.bounds, self.sh_degree, b, self.sigma_threshold)
+
+
+def _brick_table_device(occupied, resolution, b):
+    """brick_table on the device: occupied bool [Rx-1,Ry-1,Rz-1] -> (brick_of int32 [Bx,By,Bz], number of stored bricks; the one host
+    read)"""
+    import torch
+    B = brick_grid(resolution, b)
+    touched = torch.zeros(tuple(n * b for n in B), device=occupied.device, dtype=torch.bool)
+    cx, cy, cz = occupied.shape
+    for i in (0, 1):
+        for j in (0, 1):
+            for k in (0, 1):
+                touched[i:i + cx, j:j + cy, k:k + cz] |= occupied
+    stored = touched.reshape(B[0], b, B[1], b, B[2], b).any(dim=5).any(dim=3).any(dim=1)
+    slot = torch.cumsum(stored.reshape(-1).to(torch.int32), 0, dtype=torch.int32).reshape(B) - 1
+    return torch.where(stored, slot, torch.full_like(slot, -1)).contiguous(), int(stored.sum())
+
+
+def _brick_points_device(keys, resolution, b):
+    """the lattice points of the bricks `keys` (int64 [m], linear brick indices): (lattice index int64 [m b^3], clipped into the
+    lattice; inside bool [m b^3])"""
+    import torch
+    res, B = resolution, brick_grid(resolution, b)
+    ax = torch.arange(b, device=keys.device, dtype=torch.int64)
+    x = ((keys // (B[1] * B[2])) * b)[:, None] + ax
+    y = (((keys // B[2]) % B[1]) * b)[:, None] + ax
+    z = ((keys % B[2]) * b)[:, None] + ax
+    x, y, z = x[:, :, None, None], y[:, None, :, None], z[:, None, None, :]
+    inside = (x < res[0]) & (y < res[1]) & (z < res[2])
+    lin = (x.clamp(max=res[0] - 1) * res[1] + y.clamp(max=res[1] - 1)) * res[2] + z.clamp(max=res[2] - 1)
+    return lin.reshape(-1), inside.reshape(-1)
+
+
+def _brick_slabs(brick_of, b, row_bytes):
+    """the stored bricks' linear indices (ascending = slot order) in slabs whose rows and index plumbing stay under SLAB_BYTES"""
+    keys = (brick_of.reshape(-1) >= 0).nonzero().reshape(-1)
+    per = max(1, SLAB_BYTES // (b ** 3 * (row_bytes + 24)))
+    return [(s0, keys[s0:s0 + per]) for s0 in range(0, int(keys.numel()), per)]
+
+
+def _gather_bricks(table, brick_of, resolution, b, out):
+    """out[slot][place] = table[point] for every point of every stored brick, zeros outside the lattice; table [P, w], out
+    [n_bricks, b^3, w].  Slab by slab: no second copy of the table is held."""
+    for s0, keys in _brick_slabs(brick_of, b, table.shape[1] * table.element_size()):
+        lin, inside = _brick_points_device(keys, resolution, b)
+        rows = table[lin]
+        rows[~inside] = 0
+        out[s0:s0 + keys.numel()] = rows.reshape(keys.numel(), b ** 3, -1)
+
+
+BRICK_KEYS = ("format", "records", "brick_of", "words", "brick", "resolution", "lo", "hi", "sh_degree", "sigma_threshold")
+
+
+def read_brick_file(path) -> dict:
+    """The arrays of a file BrickBakedField.save wrote (format 2), validated on the host: {"records" uint8 [n_bricks, b^3, record
+    bytes], "brick_of" int32 [Bx,By,Bz], "words" int32, "brick", "n_bricks", "resolution", "lo", "hi", "sh_degree",
+    "sigma_threshold"}.  ValueError on a missing key, another format, a shape or dtype that does not fit, and a brick table whose
+    entries >= 0 are not exactly 0..n_bricks-1 in ascending order (an entry past the records, a repeated slot, slots out of order).
+    No device is touched."""
+    with np.load(path) as z:
+        missing = [k for k in BRICK_KEYS if k not in z.files]
+        if missing:
+            raise ValueError(f"{path}: not a brick baked field (missing {missing})")
+        if np.ndim(z["format"]) != 0 or int(z["format"]) != 2:
+            raise ValueError(f"{path}: baked-field format {z['format']!r} is not the brick format 2")
+        data = {k: z[k] for k in BRICK_KEYS}
+    for k in ("sh_degree", "brick", "sigma_threshold"):
+        if np.ndim(data[k]) != 0:
+            raise ValueError(f"{path}: {k} must be a scalar, got shape {np.shape(data[k])}")
+    for k in ("resolution", "lo", "hi"):
+        if np.shape(data[k]) != (3,):
+            raise ValueError(f"{path}: {k} must hold three values, got shape {np.shape(data[k])}")
+    if data["sh_degree"].dtype.kind not in "iu" or data["brick"].dtype.kind not in "iu" or data["resolution"].dtype.kind not in "iu":
+        raise ValueError(f"{path}: sh_degree, brick and resolution must be integers")
+    deg = check_degree(int(data["sh_degree"]))
+    b = check_brick(int(data["brick"]))
+    res, lo, hi = check_lattice_spec(tuple(int(r) for r in data["resolution"]), (data["lo"], data["hi"]), deg)
+    thr = check_threshold(float(data["sigma_threshold"]))
+    brick_of, records, words = data["brick_of"], data["records"], data["words"]
+    B = brick_grid(res, b)
+    if brick_of.dtype != np.int32 or brick_of.shape != B:
+        raise ValueError(f"{path}: brick table {brick_of.dtype} {brick_of.shape} does not fit the {B} bricks of a {res} lattice")
+    slots = brick_of.reshape(-1)[brick_of.reshape(-1) >= 0]
+    if (brick_of < -1).any() or not np.array_equal(slots, np.arange(slots.size, dtype=np.int32)):
+        raise ValueError(f"{path}: the brick table's slots are not 0..n-1 in ascending order (out of range, repeated or out of order)")
+    n_bricks = max(int(slots.size), 1)
+    cells = int(np.prod([r - 1 for r in res]))
+    if records.dtype != np.uint8 or records.shape != (n_bricks, b ** 3, record_bytes(deg)) or words.dtype != np.int32 or \
+            words.shape != ((cells + 31) // 32,):
+        raise ValueError(f"{path}: records {records.dtype} {records.shape} / bits {words.dtype} {words.shape} do not fit {n_bricks} "
+                         f"bricks of {b}^3 records of degree {deg} on a {res} lattice")
+    check_table_size(n_bricks * b ** 3, deg)
+    return {"records": records, "brick_of": brick_of, "words": words, "brick": b, "n_bricks": n_bricks, "resolution": res, "lo": lo,
+            "hi": hi, "sh_degree": deg, "sigma_threshold": thr}
+
+
+def load_field(path, device=None):
+    """BakedField.load or BrickBakedField.load, whichever wrote `path` (its format says)"""
+    with np.load(path) as z:
+        if "format" not in z.files or np.ndim(z["format"]) != 0:
+            raise ValueError(f"{path}: not a baked field (no format)")
+        fmt = int(z["format"])
+    if fmt == 1:
+        return BakedField.load(path, device)
+    if fmt == 2:
+        return BrickBakedField.load(path, device)
+    raise ValueError(f"{path}: unknown baked-field format {fmt}")
+
+
+class BrickBakedField:
+    """A BakedField stored sparsely (include/knerf.h knerf_baked_bricks): the lattice cut into bricks of brick^3 points, only those with
+    a corner of an occupied cell stored, behind the int32 table brick_of [Bx,By,Bz] (slot or -1); every other record reads as zero.
+    render() marches rays through it on the GPU and gives the bits of the dense field's render().  Built by BakedField.compact,
+    NeRF.bake(bricks=...) or BrickBakedField.load; to_dense() leads back (optimising and resampling work on a BakedField)."""
+
+    def __init__(self, records, brick_of, words, resolution, bounds, sh_degree, brick=DEFAULT_BRICK, sigma_threshold=0.0):
+        # uint8 [n_bricks, b^3, record bytes], int32 [Bx,By,Bz], int32 [ceil(cells / 32)] on the device
+        self._records, self._brick_of, self._words = records, brick_of, words
+        self.resolution = tuple(int(r) for r in resolution)
+        self.bounds = (tuple(float(v) for v in bounds[0]), tuple(float(v) for v in bounds[1]))
+        self.sh_degree = check_degree(sh_degree)
+        self.brick = check_brick(brick)
+        self.sigma_threshold = float(sigma_threshold)
+        if records.dim() != 3 or tuple(records.shape[1:]) != (self.brick ** 3, record_bytes(self.sh_degree)) or records.shape[0] < 1 or \
+                tuple(brick_of.shape) != brick_grid(self.resolution, self.brick):
+            raise ValueError(f"records {tuple(records.shape)} / brick table {tuple(brick_of.shape)} do not fit bricks of {self.brick}^3 "
+                             f"records of degree {self.sh_degree} on a {self.resolution} lattice")
+        self.n_bricks = int(records.shape[0])
+        from . import _lib
+        self._c = _lib.KnerfBakedBricks(C.c_void_p(records.data_ptr()), C.c_void_p(brick_of.data_ptr()), C.c_void_p(words.data_ptr()),
+                                        (C.c_int32 * 3)(*self.resolution), self.sh_degree, (C.c_float * 3)(*self.bounds[0]),
+                                        (C.c_float * 3)(*self.bounds[1]), self.brick.bit_length() - 1, self.n_bricks)
+        self._bake_sigma = None                              # fp32 [n_bricks b^3]: sigma in brick order while a bake fills the records
+
+    # ---- construction by the baker
+    @classmethod
+    def _empty(cls, sigma, resolution, lo, hi, sh_degree, sigma_threshold, brick):
+        """sigma: device fp32 lattice, already thresholded.  The occupancy bits, the brick table, all-zero brick records and sigma in
+        brick order; _pack fills the records in."""
+        import torch
+        from .runtime import occupancy_words_from_grid
+        words = occupancy_words_from_grid(sigma, 0.0, 0, what="BrickBakedField")
+        brick_of, n = _brick_table_device(_unpack_words(words, tuple(r - 1 for r in resolution)), resolution, brick)
+        check_table_size(max(n, 1) * brick ** 3, sh_degree)
+        records = torch.zeros((max(n, 1), brick ** 3, record_bytes(sh_degree)), device=sigma.device, dtype=torch.uint8)
+        field = cls(records, brick_of, words, resolution, (lo, hi), sh_degree, brick, sigma_threshold)
+        field._bake_sigma = torch.zeros((max(n, 1), brick ** 3, 1), device=sigma.device, dtype=torch.float32)
+        _gather_bricks(sigma.reshape(-1, 1), brick_of, field.resolution, brick, field._bake_sigma)
+        return field
+
+    def _pack(self, sigma, acc, comp, index):
+        """BakedField._pack with the destinations in brick order: `index` (int64 [n]) names LATTICE points, all of them in stored bricks;
+        knerf_baked_pack writes record slot b^3 + place of each and takes its sigma from the brick-ordered copy"""
+        from . import _lib
+        from .runtime import _ptr
+        n = int(index.numel())
+        if n:
+            res, b, L = self.resolution, self.brick, self.brick.bit_length() - 1
+            B = brick_grid(res, b)
+            x, y, z = index // (res[1] * res[2]), (index // res[2]) % res[1], index % res[2]
+            slot = self._brick_of.reshape(-1)[((x >> L) * B[1] + (y >> L)) * B[2] + (z >> L)].to(index.dtype)
+            dest = ((slot * b + (x & (b - 1))) * b + (y & (b - 1))) * b + (z & (b - 1))
+            _check(_lib.load().knerf_baked_pack(_stream(sigma.device), _ptr(self._bake_sigma), _ptr(acc), _ptr(comp), _ptr(dest.contiguous()), n,
+                                                self.n_bricks * b ** 3, self.sh_degree, _ptr(self._records)), "knerf_baked_pack")
+
+    @property
+    def device(self):
+        return self._records.device
+
+    @property
+    def brick_of(self):
+        """int32 [Bx,By,Bz] on the device: the slot of every brick, -1 for an absent one"""
+        return self._brick_of
+
+    @property
+    def occupied(self):
+        """bool [Rx-1,Ry-1,Rz-1] on the device: the cells with sigma > 0 at one of their corners"""
+        return _unpack_words(self._words, tuple(r - 1 for r in self.resolution))
+
+    @property
+    def cell_size(self):
+        return tuple((np.float32(h) - np.float32(l)) / (r - 1) for l, h, r in zip(self.bounds[0], self.bounds[1], self.resolution))
+
+    @property
+    def nbytes(self):
+        """bytes on the device: records + brick table + occupancy bits"""
+        return sum(int(t.numel()) * t.element_size() for t in (self._records, self._brick_of, self._words))
+
+    def to_dense(self) -> BakedField:
+        """the BakedField with this field's stored bricks copied back and every other record zero"""
+        import torch
+        res, b = self.resolution, self.brick
+        check_table_size(res[0] * res[1] * res[2], self.sh_degree)
+        records = torch.zeros((res[0] * res[1] * res[2], record_bytes(self.sh_degree)), device=self.device, dtype=torch.uint8)
+        dst, src = records.view(torch.int32), self._records.view(torch.int32)            # rows move as words, not as bytes
+        for s0, keys in _brick_slabs(self._brick_of, b, records.shape[1]):
+            lin, inside = _brick_points_device(keys, res, b)
+            dst[lin[inside]] = src[s0:s0 + keys.numel()].reshape(-1, dst.shape[1])[inside]
+        return BakedField(records, self._words, res, self.bounds, self.sh_degree, self.sigma_threshold)
+
+    # ---- persistence
+    def save(self, path):
+        """one .npz file at exactly `path` (no suffix is appended), format 2: the brick records, the brick table and the bits as they
+        are on the device, the brick edge, and resolution, bounds, degree, threshold as BakedField.save writes them"""
+        with open(path, "wb") as f:
+            np.savez(f, records=self._records.cpu().numpy(), brick_of=self._brick_of.cpu().numpy(), words=self._words.cpu().numpy(),
+                     brick=np.int32(self.brick), resolution=np.asarray(self.resolution, dtype=np.int32),
+                     lo=np.asarray(self.bounds[0], dtype=np.float64), hi=np.asarray(self.bounds[1], dtype=np.float64),
+                     sh_degree=np.int32(self.sh_degree), sigma_threshold=np.float64(self.sigma_threshold), format=np.int32(2))
+
+    @classmethod
+    def load(cls, path, device=None):
+        """the field save(path) wrote; ValueError on a file that is not one (read_brick_file checks it before anything is uploaded)"""
+        import torch
+        d = read_brick_file(path)
+        dev = torch.device(device if device is not None else "cuda")
+        return cls(torch.as_tensor(d["records"]).to(dev), torch.as_tensor(d["brick_of"]).to(dev), torch.as_tensor(d["words"]).to(dev),
+                   d["resolution"], (d["lo"], d["hi"]), d["sh_degree"], d["brick"], d["sigma_threshold"])
+
+    # ---- rendering
+    def render(self, origins, directions, near, far, step=None, white_background=False, termination=0.0,
+               outputs=("image", "depth", "opacity"), skip_empty=True, stats=False, lanes_per_ray=0):
+        """BakedField.render through the brick table (knerf_baked_render_bricks): the same arguments, checks and result dict, and for
+        a field that came from compact() the same bits."""
+        import torch
+        from . import _lib
+        from .runtime import _ptr
+        outs = check_render_args(step, termination, outputs, self.sh_degree, lanes_per_ray)
+        dev = self.device
+        o, d, n, h, (near_t, near0), (far_t, far0) = _ray_args(self, origins, directions, near, far, step)
+        e = lambda *s: torch.empty(s, device=dev, dtype=torch.float32)
+        res = {"image": e(n, 3) if "image" in outs else None, "depth": e(n) if "depth" in outs else None,
+               "opacity": e(n) if "opacity" in outs else None}
+        counter = torch.zeros(2, device=dev, dtype=torch.int64) if stats else None
+        flags = (_lib.BAKED_WHITE_BACKGROUND if white_background else 0) | (_lib.BAKED_SKIP_EMPTY if skip_empty else 0) | \
+            (int(lanes_per_ray) << _lib.BAKED_LANES_SHIFT)
+        if n:
+            _check(_lib.load().knerf_baked_render_bricks(_stream(dev), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t), _ptr(far_t), near0,
+                                                         far0, n, h, float(termination), flags, _ptr(res["image"]), _ptr(res["depth"]),
+                                                         _ptr(res["opacity"]), _ptr(counter)), "knerf_baked_render_bricks")
+        out = {k: v for k, v in res.items() if v is not None}
+        if stats:
+            out["stats"] = counter
+        return out
+
 
 def __getattr__(name):
     """the optimiser's names live in baked_train.py (which imports this module) and are reachable from here as well"""
@@ -451,18 +784,20 @@ def _unpack_words(words, cells):
 
 
 def bake(nerf, resolution=256, bounds=((-1.5,) * 3, (1.5,) * 3), net="fine", sh_degree=2, n_directions=None, sigma_threshold=0.0,
-         slab_bytes=SLAB_BYTES):
+         slab_bytes=SLAB_BYTES, bricks=None):
     """NeRF.bake: see there.  The work list is processed in slabs: accumulator and compensation of ONE slab ([slab, K, 3] fp32 each,
     together at most slab_bytes) are summed over the directions and packed into the records before the next slab starts, so the
     working memory does not grow with the lattice.  Nothing waits for the GPU between slabs and directions; the one host read is the
     length of the work list.  slab_bytes is a tuning / diagnostic knob (tests force several slabs with it), not a promised part of the
-    interface."""
+    interface.  bricks = 4 or 8: the same work list in the same slabs is packed straight into a BrickBakedField (the dense record table
+    is never allocated); the result is bake(...).compact(bricks) byte for byte."""
     import torch
     from .runtime import _ptr, baked_project, occupancy_words_from_grid
     deg = check_degree(sh_degree)
     res, lo, hi = check_lattice_spec(resolution, bounds, deg)
     dirs, P = fit_directions(deg, n_directions)
     thr = check_threshold(sigma_threshold)
+    brick = None if bricks is None else check_brick(bricks)
     if isinstance(slab_bytes, bool) or int(slab_bytes) != slab_bytes or int(slab_bytes) < 1:
         raise ValueError(f"slab_bytes must be a positive integer, got {slab_bytes!r}")
     n_net = nerf._field_net(net)
@@ -471,7 +806,7 @@ def bake(nerf, resolution=256, bounds=((-1.5,) * 3, (1.5,) * 3), net="fine", sh_
     K, D = P.shape
     sigma = nerf.density_grid(res, (lo, hi), net)
     sigma = torch.where(sigma > thr, sigma, torch.zeros_like(sigma))
-    field = BakedField._empty(sigma, res, lo, hi, deg, thr)
+    field = BakedField._empty(sigma, res, lo, hi, deg, thr) if brick is None else BrickBakedField._empty(sigma, res, lo, hi, deg, thr, brick)
     # the work list: lattice points that are a corner of an occupied cell (a cell is occupied when a corner has sigma > 0)
     occ = field.occupied
     touched = torch.zeros(res, device=dev, dtype=torch.bool)
@@ -505,4 +840,6 @@ def bake(nerf, resolution=256, bounds=((-1.5,) * 3, (1.5,) * 3), net="fine", sh_
                 ctx._check(lib.knerf_query_points(ctx._ctx, ctx._stream(), n_net, _ptr(pts), _ptr(dj), 0, m, None, None, _ptr(rgb)))
                 baked_project(rgb[:m], fit, j, a, e)
             field._pack(sigma, a, e, idx)
+    if brick is not None:
+        field._bake_sigma = None
     return field

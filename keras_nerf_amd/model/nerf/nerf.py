@@ -447,15 +447,19 @@ class NeRF:
         colors = self.query(verts, -normals, net)[0]
         return verts, faces, normals, colors
 
-    def bake(self, resolution=256, bounds=((-1.5,) * 3, (1.5,) * 3), net="fine", sh_degree=2, n_directions=None, sigma_threshold=0.0):
+    def bake(self, resolution=256, bounds=((-1.5,) * 3, (1.5,) * 3), net="fine", sh_degree=2, n_directions=None, sigma_threshold=0.0,
+             bricks=None):
         """Bake the trained field into a keras_nerf_amd.baked.BakedField: density_grid(resolution, bounds, net) with every value
         <= sigma_threshold stored as 0, and at every lattice point that touches an occupied cell the colour as a function of the view
         direction, fitted by least squares with real spherical harmonics up to sh_degree (0..3) from the net's colour along
         n_directions Fibonacci-sphere directions (default max(4 K, 16), K = (sh_degree + 1)^2; sh_degree 0: the single zero
         direction).  sigma_threshold must be >= 0.  The fit runs over slabs of the lattice, with about 1 GB of working memory whatever
-        the resolution.  BakedField.render then renders novel views from the grid alone, without the MLP."""
+        the resolution.  BakedField.render then renders novel views from the grid alone, without the MLP.
+        bricks = 4 or 8 (default None: the dense BakedField, as ever): bake straight into a keras_nerf_amd.baked.BrickBakedField that
+        stores only the bricks of bricks^3 lattice points around occupied cells; the dense record table is never allocated and the
+        result is bake(...).compact(bricks) byte for byte."""
         from ...baked import bake
-        return bake(self, resolution, bounds, net, sh_degree, n_directions, sigma_threshold)
+        return bake(self, resolution, bounds, net, sh_degree, n_directions, sigma_threshold, bricks=bricks)
 
     # ------------------------------------------------------------------ empty-space skipping for rendering (extension)
     def build_occupancy_grid(self, resolution=128, bounds=((-1.5,) * 3, (1.5,) * 3), threshold=0.0, dilation=1, outside="occupied"):
