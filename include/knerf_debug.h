@@ -66,6 +66,56 @@ int knerf_debug_composite_objective(void* stream, const float* raw, const float*
  * be null.  list holds up to n entries.  All pointers are device pointers. */
 int knerf_debug_compact_tiles(const int* flags, int n, int period, int real, int* list, int* count, long long* stats, void* stream);
 
+/* ---- the general-shape path's four matmul kernels on caller-made buffers (csrc/generic.hip; tests/test_gpu_generic_gemm.py) ----
+ * Which kernel and grid the launchers pick, from the host arithmetic they use themselves (no device needed).
+ * what 0, a GEMM over (M = m_or_steps, N, K): out = {1 weights-stationary gemm_ws_kernel | 0 streaming gemm_kernel, NT, gx, gy,
+ * LDS bytes, LDS row pitch, 0, 0}; a wave of the persistent kernel walks row tiles w, w + 8 gx, ... of M / 32.
+ * what 1, a weight gradient over (steps = m_or_steps, N, K): out = {1 wgrad_coop_kernel | 0 wgrad_kernel<KT, NT>, gx, gy, gz, KT,
+ * NT, partial slabs per block, floats per slab}; per_wave != 0: the per-wave kernel whatever the product would pick. */
+int knerf_debug_generic_launch(int what, long long m_or_steps, int N, int K, int per_wave, int32_t out[8]);
+/* floats of `partial` a deterministic weight-gradient launch over a [K] x [N] layer needs (any number of steps) */
+int knerf_debug_generic_wgrad_partial_floats(int K, int N, int per_wave, size_t* floats);
+/* One launch_gemm: C[M][N] = A[M][K] . Bt[N][K]^T (+ bias[col < n_real]) (relu) (* relu bit).  bf16 buffers are uint16.  Device
+ * pointers with the element count of each buffer; Cb is the buffer's BASE and the output starts at column c_col0 of its rows.
+ * Exactly one of Cb / Cf; mask_out (forward) or mask_in (dgrad: no bias, no relu) go with Cb.  live: a HOST array of n_live
+ * 32-row tile indices in [0, M / 32), or n_live = -1 for every tile; live_dev: device scratch of at least n_live + 1 int32 that
+ * receives {count, entries}.  Every argument is checked on the host against what the launch can address -- M a multiple of 128,
+ * N and K of 32, leading dimensions of 8 and >= the width, 16-byte aligned bases, ldc and c_col0 multiples of NT, mask_cols >= N / 8,
+ * every buffer long enough for the last row -- and KNERF_ERR_INVALID comes back before any HIP call. */
+typedef struct knerf_debug_gemm {
+    const uint16_t* A; size_t a_elems; int lda;
+    const uint16_t* Bt; size_t bt_elems; int ldb;
+    long long M; int N, K;
+    const float* bias; size_t bias_elems; int n_real;
+    int relu;
+    unsigned char* mask_out; const unsigned char* mask_in; size_t mask_bytes; int mask_cols;
+    uint16_t* Cb; size_t cb_elems; int ldc, c_col0;
+    float* Cf; size_t cf_elems; int ldcf;
+    const int32_t* live; long long n_live; int32_t* live_dev; size_t live_dev_elems;
+} knerf_debug_gemm;
+int knerf_debug_generic_gemm(void* stream, const knerf_debug_gemm* args);
+/* One launch_wgrad (and its ordered reduce pass when `partial` is given): grad[w_off + row n_real + n] += sum_m X[m][k] Z[m][n]
+ * for the kernel rows `row` the segments {buffer col0, width, kernel row0} x n_seg map column k to and n < n_real,
+ * grad[b_off + n] += sum_m Z[m][n]; m over steps x 32 rows or over the live list (as above, entries in [0, steps); strictly ascending
+ * when `partial` is given).  selector 0: the kernel the product picks, 1: the per-wave wgrad_kernel.  partial: null (fp32 atomics)
+ * or at least knerf_debug_generic_wgrad_partial_floats floats.  Checked like knerf_debug_generic_gemm; segments must lie inside K
+ * and every destination inside grad_elems. */
+typedef struct knerf_debug_wgrad {
+    const uint16_t* X; size_t x_elems; int ldx;
+    const uint16_t* Z; size_t z_elems; int ldz;
+    long long steps; int N, K;
+    float* grad; size_t grad_elems;
+    int w_off, b_off, n_real;
+    int n_seg; int seg[6];
+    float* partial; size_t partial_elems;
+    const int32_t* live; long long n_live; int32_t* live_dev; size_t live_dev_elems;
+    int selector;
+} knerf_debug_wgrad;
+int knerf_debug_generic_wgrad(void* stream, const knerf_debug_wgrad* args);
+/* the argument check of the two entry points above on its own (what 0: a knerf_debug_gemm, 1: a knerf_debug_wgrad): KNERF_OK or
+ * KNERF_ERR_INVALID; never touches the device or the pointers' targets other than the host live list */
+int knerf_debug_generic_check(int what, const void* args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -101,6 +101,63 @@ hipError_t backward(const Plan& p, const Workspace& ws, const NetDev& net, const
                     long long* stats = nullptr);
 size_t wgrad_partial_floats(const Plan& p);
 size_t padded_rows(long long n);
+
+// ---- the two matmul launchers on their own (forward / dgrad GEMM, weight gradient): what run_layers() and backward() call once
+// per Dense layer.  Declared here for the operator-level tests (include/knerf_debug.h knerf_debug_generic_gemm / _wgrad).
+// C[M][N] = A[M][K] . Bt[N][K]^T (+bias) (relu) (* relu bits)
+struct GemmArgs {
+    const unsigned short* A; int lda;
+    const unsigned short* Bt; int ldb;
+    long long M; int N, K;
+    const float* bias; int n_real;       // bias[col] for col < n_real (fp32 master weights), else 0
+    int relu;
+    // relu bits of a trunk layer's output, one bit per (row, feature): [32-row tile][feature / 8][32 bytes], the 32 bytes of a
+    // (tile, feature octet) in the order the MFMA accumulator holds the tile's rows -- byte 16 hh + i is row (i & 3) + 8 (i >> 2)
+    // + 4 hh -- so that a lane's sixteen rows are ONE 16-byte access.  The forward GEMM writes them (mask_out; 1/16 of the
+    // activation's bytes), the dgrad GEMM of the same features reads them (mask_in) instead of the saved bf16 activation: a
+    // third of that GEMM's traffic, and its only load with a use right behind it
+    unsigned char* mask_out; const unsigned char* mask_in; int mask_cols;      // mask_cols = padded units / 8
+    unsigned short* Cb; int ldc;         // bf16 output (may be null)
+    float* Cf; int ldcf;                 // fp32 output (may be null)
+    // dead-tile skipping (backward only): the 32-row tiles to process = list entries [0, *n_live) (composite.hip appends the tiles
+    // whose dL/d(rgb, sigma) is not all zero); rows of other tiles are neither read nor written.  null: every tile of M
+    const int* live; const int* n_live;
+};
+// dW[k][n] += sum_m X[m][k] dZ[m][n], db[n] += sum_m dZ[m][n]
+struct WgradArgs {
+    const unsigned short* X; int ldx;
+    const unsigned short* Z; int ldz;
+    long long steps;            // Mp / 32
+    float* grad;                // flat fp32 gradient of the net
+    int w_off, b_off, n_real;
+    int n_seg; Seg seg[2];
+    // deterministic mode (knerf_set_option "deterministic"): no fp32 atomics -- every accumulating unit (a wave of wgrad_kernel, a
+    // workgroup of wgrad_coop_kernel) stores its partial tile to its OWN slab and wgrad_reduce_kernel adds the slabs of a block in
+    // slab order into grad.  The step -> unit assignment is a function of the grid alone, so two launches give the same bits.
+    // Block (bx, by), slab sl: partial + ((bx gy + by) n_sl + sl) tile_floats; a tile is [TK][TN] sums then [bias_halves][TN].
+    float* partial;             // null: atomics
+    const int* live; const int* n_live;     // dead-tile skipping: the 32-sample steps to contract over = list entries [0, *n_live); null: all
+};
+// Which kernel and grid a launch gets: host arithmetic only, and what the launchers themselves go by.
+struct GemmLaunch {
+    int ws;                     // 1: gemm_ws_kernel<nt> (weight slab resident in LDS, persistent over row tiles), 0: gemm_kernel<nt>
+    int nt;                     // 32-column tiles per column block: 1, 2, 4 or 8
+    int gx, gy;                 // row groups (of 8 waves x 32 rows) and column blocks; ws: a wave walks tiles w, w + 8 gx, ...
+    size_t lds; int pitch;      // dynamic LDS bytes; ws: bytes per staged weight row
+};
+GemmLaunch describe_gemm(long long M, int N, int K);
+struct WgradLaunch {
+    int coop;                   // 1: wgrad_coop_kernel (256 x 256 blocks, gz units of samples), 0: wgrad_kernel<kt, nt>
+    int gx, gy, gz;             // blocks over K, over N, units of samples (per-wave kernel: workgroups of 4 waves = 4 units each)
+    int kt, nt;                 // per-wave kernel: 32-wide tiles per block (coop: 8, 8)
+    int n_slabs; size_t slab_floats;     // deterministic mode: partial tiles per block and their size
+};
+// per_wave != 0: the per-wave kernel with the tiles launch_wgrad would give it, whatever coop_serves says (tests only)
+WgradLaunch describe_wgrad(int K, int N, long long steps, int per_wave = 0);
+hipError_t launch_gemm(const GemmArgs& g, hipStream_t s);
+hipError_t launch_wgrad(const WgradArgs& g, int K, int N, hipStream_t s, int per_wave = 0);
+// slab floats one weight-gradient launch over a [K] x [N] layer can need (the grid's upper bound; independent of the sample count)
+size_t wgrad_partial_floats_for(int K, int N, int per_wave = 0);
 size_t relu_bits_bytes_per_row(const Plan& p);          // one bit per padded trunk feature
 size_t relu_bits_bytes(const Plan& p, size_t mp);       // Workspace::mask for mp padded rows
 

@@ -104,24 +104,6 @@ __global__ __launch_bounds__(256) void copy_cols_kernel(const u16* __restrict__ 
 }
 
 // ---- C[M][N] = A[M][K] . Bt[N][K]^T (+bias) (relu) (* relu bits) ------------------------------------------------------
-struct GemmArgs {
-    const u16* A; int lda;
-    const u16* Bt; int ldb;
-    long long M; int N, K;
-    const float* bias; int n_real;       // bias[col] for col < n_real (fp32 master weights), else 0
-    int relu;
-    // relu bits of a trunk layer's output, one bit per (row, feature): [32-row tile][feature / 8][32 bytes], the 32 bytes of a
-    // (tile, feature octet) in the order the MFMA accumulator holds the tile's rows -- byte 16 hh + i is row (i & 3) + 8 (i >> 2)
-    // + 4 hh -- so that a lane's sixteen rows are ONE 16-byte access.  The forward GEMM writes them (mask_out; 1/16 of the
-    // activation's bytes), the dgrad GEMM of the same features reads them (mask_in) instead of the saved bf16 activation: a
-    // third of that GEMM's traffic, and its only load with a use right behind it
-    unsigned char* mask_out; const unsigned char* mask_in; int mask_cols;      // mask_cols = padded units / 8
-    u16* Cb; int ldc;                    // bf16 output (may be null)
-    float* Cf; int ldcf;                 // fp32 output (may be null)
-    // dead-tile skipping (backward only): the 32-row tiles to process = list entries [0, *n_live) (composite.hip appends the tiles
-    // whose dL/d(rgb, sigma) is not all zero); rows of other tiles are neither read nor written.  null: every tile of M
-    const int* live; const int* n_live;
-};
 
 // epilogue shared by the two GEMM kernels: bias, relu, relu mask of the dgrad, bf16 / fp32 stores.
 // Column assignment: column r of the column block's tile t is output feature n0 + NT r + t (the kernels stage weight row
@@ -375,48 +357,70 @@ __global__ __launch_bounds__(kGemmWaves * 64) void gemm_ws_kernel(GemmArgs g, in
 
 constexpr size_t kGemmWsLds = 150 * 1024;
 template <int NT>
-hipError_t launch_gemm_ws(const GemmArgs& g, int gy, hipStream_t s) {
-    const int pitch = (g.K + 63) / 64 * 64 * 2 + 16;
-    const size_t lds = (size_t)NT * 32 * pitch;
+hipError_t launch_gemm_ws(const GemmArgs& g, const GemmLaunch& d, hipStream_t s) {
     static AttrOnce once;
     hipError_t ae = once([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ws_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kGemmWsLds); });
     if (ae != hipSuccess) return ae;
-    long long gx = (g.M / 32 + kGemmWaves - 1) / kGemmWaves;
-    const long long cap = 512 / gy > 0 ? 512 / gy : 1;           // persistent: about two workgroups per CU in all
-    if (gx > cap) gx = cap;
-    if (gy > 1) gx = gx >= 8 ? gx / 8 * 8 : 8;                   // the XCD mapping of the kernel wants whole groups of eight row groups
-    hipLaunchKernelGGL((gemm_ws_kernel<NT>), dim3((unsigned)(gx * gy)), dim3(kGemmWaves * 64), lds, s, g, pitch, (int)gx, gy);
+    hipLaunchKernelGGL((gemm_ws_kernel<NT>), dim3((unsigned)(d.gx * d.gy)), dim3(kGemmWaves * 64), d.lds, s, g, d.pitch, d.gx, d.gy);
     return hipGetLastError();
 }
 
 template <int NT>
-hipError_t launch_gemm_nt(const GemmArgs& g, int gy, hipStream_t s) {
-    const size_t lds = 2 * (size_t)NT * 32 * kGemmRowB;
+hipError_t launch_gemm_nt(const GemmArgs& g, const GemmLaunch& d, hipStream_t s) {
     static AttrOnce once;
-    if (lds > 64 * 1024) {
-        hipError_t ae = once([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
+    if (d.lds > 64 * 1024) {
+        hipError_t ae = once([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)d.lds); });
         if (ae != hipSuccess) return ae;
     }
-    const unsigned gx = (unsigned)((g.M + kGemmWaves * 32 - 1) / (kGemmWaves * 32));
-    hipLaunchKernelGGL((gemm_kernel<NT>), dim3(gx, gy), dim3(kGemmWaves * 64), lds, s, g);
+    hipLaunchKernelGGL((gemm_kernel<NT>), dim3((unsigned)d.gx, d.gy), dim3(kGemmWaves * 64), d.lds, s, g);
     return hipGetLastError();
 }
 
-hipError_t launch_gemm(const GemmArgs& g, hipStream_t s) {
-    const int nt = g.N / 32;
-    const size_t row_bytes = (size_t)(g.K + 63) / 64 * 64 * 2 + 16;
+}  // namespace
+
+GemmLaunch describe_gemm(long long M, int N, int K) {
+    GemmLaunch d{};
+    const int nt = N / 32;
+    const size_t row_bytes = (size_t)(K + 63) / 64 * 64 * 2 + 16;
 #ifndef KNERF_GEN_NO_WS
     // the widest column block whose weight slab fits in LDS, resident for the whole launch
-    if (nt % 8 == 0 && 256 * row_bytes <= kGemmWsLds) return launch_gemm_ws<8>(g, nt / 8, s);
-    if (nt % 4 == 0 && 128 * row_bytes <= kGemmWsLds) return launch_gemm_ws<4>(g, nt / 4, s);
-    if (nt % 2 == 0 && 64 * row_bytes <= kGemmWsLds) return launch_gemm_ws<2>(g, nt / 2, s);
-    if (32 * row_bytes <= kGemmWsLds) return launch_gemm_ws<1>(g, nt, s);
+    if (nt % 8 == 0 && 256 * row_bytes <= kGemmWsLds) { d.ws = 1; d.nt = 8; }
+    else if (nt % 4 == 0 && 128 * row_bytes <= kGemmWsLds) { d.ws = 1; d.nt = 4; }
+    else if (nt % 2 == 0 && 64 * row_bytes <= kGemmWsLds) { d.ws = 1; d.nt = 2; }
+    else if (32 * row_bytes <= kGemmWsLds) { d.ws = 1; d.nt = 1; }
 #endif
-    if (nt % 8 == 0) return launch_gemm_nt<8>(g, nt / 8, s);
-    if (nt % 4 == 0) return launch_gemm_nt<4>(g, nt / 4, s);
-    if (nt % 2 == 0) return launch_gemm_nt<2>(g, nt / 2, s);
-    return launch_gemm_nt<1>(g, nt, s);
+    if (!d.ws) d.nt = nt % 8 == 0 ? 8 : (nt % 4 == 0 ? 4 : (nt % 2 == 0 ? 2 : 1));
+    d.gy = nt / d.nt;
+    if (d.ws) {
+        d.pitch = (int)row_bytes;
+        d.lds = (size_t)d.nt * 32 * d.pitch;
+        long long gx = (M / 32 + kGemmWaves - 1) / kGemmWaves;
+        const long long cap = 512 / d.gy > 0 ? 512 / d.gy : 1;       // persistent: about two workgroups per CU in all
+        if (gx > cap) gx = cap;
+        if (d.gy > 1) gx = gx >= 8 ? gx / 8 * 8 : 8;                 // the XCD mapping of the kernel wants whole groups of eight row groups
+        d.gx = (int)gx;
+    } else {
+        d.lds = 2 * (size_t)d.nt * 32 * kGemmRowB;
+        d.gx = (int)((M + kGemmWaves * 32 - 1) / (kGemmWaves * 32));
+    }
+    return d;
 }
+
+hipError_t launch_gemm(const GemmArgs& g, hipStream_t s) {
+    const GemmLaunch d = describe_gemm(g.M, g.N, g.K);
+    if (d.ws) {
+        if (d.nt == 8) return launch_gemm_ws<8>(g, d, s);
+        if (d.nt == 4) return launch_gemm_ws<4>(g, d, s);
+        if (d.nt == 2) return launch_gemm_ws<2>(g, d, s);
+        return launch_gemm_ws<1>(g, d, s);
+    }
+    if (d.nt == 8) return launch_gemm_nt<8>(g, d, s);
+    if (d.nt == 4) return launch_gemm_nt<4>(g, d, s);
+    if (d.nt == 2) return launch_gemm_nt<2>(g, d, s);
+    return launch_gemm_nt<1>(g, d, s);
+}
+
+namespace {
 // ---- heads ----------------------------------------------------------------------------------------------------------
 // raw[m] = (sigmoid(z[m][0..2]), relu(z[m][3])) from the head GEMM's pre-activations   (mlp.py:42-49)
 __global__ __launch_bounds__(256) void head_fwd_kernel(const float* __restrict__ z, long long n, float* __restrict__ raw) {
@@ -601,20 +605,6 @@ __global__ __launch_bounds__(256) void pack_kernel(PackArgs a) {
 }
 
 // ---- wgrad: dW[k][n] += sum_m X[m][k] dZ[m][n], db[n] += sum_m dZ[m][n] -----------------------------------------------
-struct WgradArgs {
-    const u16* X; int ldx;
-    const u16* Z; int ldz;
-    long long steps;            // Mp / 32
-    float* grad;                // flat fp32 gradient of the net
-    int w_off, b_off, n_real;
-    int n_seg; Seg seg[2];
-    // deterministic mode (knerf_set_option "deterministic"): no fp32 atomics -- every accumulating unit (a wave of wgrad_kernel, a
-    // workgroup of wgrad_coop_kernel) stores its partial tile to its OWN slab and wgrad_reduce_kernel adds the slabs of a block in
-    // slab order into grad.  The step -> unit assignment is a function of the grid alone, so two launches give the same bits.
-    // Block (bx, by), slab sl: partial + ((bx gy + by) n_sl + sl) tile_floats; a tile is [TK][TN] sums then [bias_halves][TN].
-    float* partial;             // null: atomics
-    const int* live; const int* n_live;     // dead-tile skipping: the 32-sample steps to contract over = list entries [0, *n_live); null: all
-};
 
 // 32 samples x 32 features (row-major; raw = the two 16-byte row pieces each lane loaded) -> two operand fragments with
 // lane = feature: f[0] = samples sigma(hh, j) (first 16), f[1] = 16 + sigma(hh, j), sigma(hh, j) = (j&3) + 8(j>>2) + 4hh.
@@ -960,37 +950,21 @@ inline bool coop_serves(int kt, int nt) {
 #endif
 }
 
-// slab floats one weight-gradient launch over a [K] x [N] layer can need (the grid's upper bound; independent of the sample count)
-size_t wgrad_partial_floats_for(int K, int N) {
-    const int kt = K / 32, nt = N / 32;
-    if (coop_serves(kt, nt)) {
-        const long long gx = (K + 255) / 256, gy = (N + 255) / 256;
-        long long gz = KNERF_GEN_COOP_WGS / (gx * gy); if (gz < 1) gz = 1;
-        if (gx * gy > 1 && gz < 8) gz = 8;                       // launch_wgrad's whole groups of eight units
-        return (size_t)(gx * gy * gz) * (256 * 256 + 256);
-    }
-    const int KT = kt % 2 == 0 ? 2 : 1, NT = nt % 4 == 0 ? 4 : (nt % 2 == 0 ? 2 : 1);      // the largest tiles launch_wgrad may pick
-    const long long gx = kt / KT, gy = nt / NT;
-    long long gz = 1024 / (gx * gy); if (gz < 1) gz = 1;
-    return (size_t)(gx * gy * gz * 4) * (KT * 32 * NT * 32 + 2 * NT * 32);
-}
+}  // namespace
 
-hipError_t launch_wgrad(const WgradArgs& g, int K, int N, hipStream_t s) {
+WgradLaunch describe_wgrad(int K, int N, long long steps, int per_wave) {
+    WgradLaunch d{};
     const int kt = K / 32, nt = N / 32;
-    if (coop_serves(kt, nt)) {
-        static AttrOnce once;
-        const size_t lds = (size_t)kCoopDepth * kCoopBuf;
-        hipError_t ae = once([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_coop_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-        if (ae != hipSuccess) return ae;
-        const int gx = (K + 255) / 256, gy = (N + 255) / 256;
-        long long gz = KNERF_GEN_COOP_WGS / ((long long)gx * gy);
-        if (gz > g.steps) gz = g.steps;
+    if (!per_wave && coop_serves(kt, nt)) {
+        d.coop = 1; d.kt = 8; d.nt = 8;
+        d.gx = (K + 255) / 256; d.gy = (N + 255) / 256;
+        long long gz = KNERF_GEN_COOP_WGS / ((long long)d.gx * d.gy);
+        if (gz > steps) gz = steps;
         if (gz < 1) gz = 1;
-        if (gx * gy > 1) gz = gz >= 8 ? gz / 8 * 8 : 8;         // the kernel's XCD mapping wants whole groups of eight units (idle units are harmless)
-        hipLaunchKernelGGL(wgrad_coop_kernel, dim3((unsigned)(gx * gy * gz)), dim3(512), lds, s, g, K, N, gx, gy, (int)gz);
-        if (g.partial)
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((256 * 256 + 256 + 255) / 256, gx * gy), dim3(256), 0, s, g, (int)gz, 256, 256, 1, gy);
-        return hipGetLastError();
+        if (d.gx * d.gy > 1) gz = gz >= 8 ? gz / 8 * 8 : 8;     // the kernel's XCD mapping wants whole groups of eight units (idle units are harmless)
+        d.gz = (int)gz;
+        d.n_slabs = d.gz; d.slab_floats = 256 * 256 + 256;
+        return d;
     }
 #ifndef KNERF_GEN_MAXKT
 #define KNERF_GEN_MAXKT 2
@@ -998,27 +972,51 @@ hipError_t launch_wgrad(const WgradArgs& g, int K, int N, hipStream_t s) {
 #ifndef KNERF_GEN_MAXNT
 #define KNERF_GEN_MAXNT 2      // measured: 2x2 blocks (more waves in flight) 17.6 ms per default-shape chunk, 2x4 19.1, 1x4 18.7
 #endif
-    const int KT = (kt % 2 == 0 && KNERF_GEN_MAXKT >= 2) ? 2 : 1;
-    const int NT = (nt % 4 == 0 && KNERF_GEN_MAXNT >= 4) ? 4 : ((nt % 2 == 0 && KNERF_GEN_MAXNT >= 2) ? 2 : 1);
-    const int gx = kt / KT, gy = nt / NT;
-    long long gz = 1024 / ((long long)gx * gy);
-    const long long max_z = (g.steps + 3) / 4;
+    d.kt = (kt % 2 == 0 && KNERF_GEN_MAXKT >= 2) ? 2 : 1;
+    d.nt = (nt % 4 == 0 && KNERF_GEN_MAXNT >= 4) ? 4 : ((nt % 2 == 0 && KNERF_GEN_MAXNT >= 2) ? 2 : 1);
+    d.gx = kt / d.kt; d.gy = nt / d.nt;
+    long long gz = 1024 / ((long long)d.gx * d.gy);
+    const long long max_z = (steps + 3) / 4;
     if (gz > max_z) gz = max_z;
     if (gz < 1) gz = 1;
-    const dim3 grid(gx, gy, (unsigned)gz), block(256);
+    d.gz = (int)gz;
+    d.n_slabs = d.gz * 4; d.slab_floats = (size_t)d.kt * 32 * d.nt * 32 + 2 * d.nt * 32;
+    return d;
+}
+
+// the grid's upper bound: the grid of a launch over more steps than any kernel has units
+size_t wgrad_partial_floats_for(int K, int N, int per_wave) {
+    const WgradLaunch d = describe_wgrad(K, N, 1ll << 40, per_wave);
+    return (size_t)d.gx * d.gy * d.n_slabs * d.slab_floats;
+}
+
+hipError_t launch_wgrad(const WgradArgs& g, int K, int N, hipStream_t s, int per_wave) {
+    const WgradLaunch d = describe_wgrad(K, N, g.steps, per_wave);
+    if (d.coop) {
+        static AttrOnce once;
+        const size_t lds = (size_t)kCoopDepth * kCoopBuf;
+        hipError_t ae = once([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_coop_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
+        if (ae != hipSuccess) return ae;
+        hipLaunchKernelGGL(wgrad_coop_kernel, dim3((unsigned)(d.gx * d.gy * d.gz)), dim3(512), lds, s, g, K, N, d.gx, d.gy, d.gz);
+        if (g.partial)
+            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((256 * 256 + 256 + 255) / 256, d.gx * d.gy), dim3(256), 0, s, g, d.gz, 256, 256, 1, d.gy);
+        return hipGetLastError();
+    }
+    const dim3 grid(d.gx, d.gy, (unsigned)d.gz), block(256);
 #define KNERF_GEN_WG(KT_, NT_) hipLaunchKernelGGL((wgrad_kernel<KT_, NT_>), grid, block, 0, s, g)
-    if (KT == 2 && NT == 4) KNERF_GEN_WG(2, 4);
-    else if (KT == 2 && NT == 2) KNERF_GEN_WG(2, 2);
-    else if (KT == 2 && NT == 1) KNERF_GEN_WG(2, 1);
-    else if (KT == 1 && NT == 4) KNERF_GEN_WG(1, 4);
-    else if (KT == 1 && NT == 2) KNERF_GEN_WG(1, 2);
+    if (d.kt == 2 && d.nt == 4) KNERF_GEN_WG(2, 4);
+    else if (d.kt == 2 && d.nt == 2) KNERF_GEN_WG(2, 2);
+    else if (d.kt == 2 && d.nt == 1) KNERF_GEN_WG(2, 1);
+    else if (d.kt == 1 && d.nt == 4) KNERF_GEN_WG(1, 4);
+    else if (d.kt == 1 && d.nt == 2) KNERF_GEN_WG(1, 2);
     else KNERF_GEN_WG(1, 1);
 #undef KNERF_GEN_WG
     if (g.partial)
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((KT * 32 * NT * 32 + NT * 32 + 255) / 256, gx * gy), dim3(256), 0, s, g, (int)gz * 4, KT * 32, NT * 32, 2, gy);
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((d.kt * 32 * d.nt * 32 + d.nt * 32 + 255) / 256, d.gx * d.gy), dim3(256), 0, s, g, d.n_slabs, d.kt * 32, d.nt * 32, 2, d.gy);
     return hipGetLastError();
 }
 
+namespace {
 inline unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace

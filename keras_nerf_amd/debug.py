@@ -26,7 +26,38 @@ SIGNATURES = {
     "knerf_debug_composite_objective": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P, _P, _P,
                                                   _P, _P, _P, _P, _P, _P, C.c_int, C.POINTER(_lib.KnerfObjective), C.c_float, _P, _P]),
     "knerf_debug_compact_tiles": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "knerf_debug_generic_launch": (C.c_int, [C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "knerf_debug_generic_wgrad_partial_floats": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "knerf_debug_generic_gemm": (C.c_int, [_P, _P]),
+    "knerf_debug_generic_wgrad": (C.c_int, [_P, _P]),
+    "knerf_debug_generic_check": (C.c_int, [C.c_int, _P]),
 }
+
+
+class DebugGemm(C.Structure):
+    """knerf_debug_gemm of include/knerf_debug.h"""
+    _fields_ = [("A", _P), ("a_elems", C.c_size_t), ("lda", C.c_int),
+                ("Bt", _P), ("bt_elems", C.c_size_t), ("ldb", C.c_int),
+                ("M", C.c_longlong), ("N", C.c_int), ("K", C.c_int),
+                ("bias", _P), ("bias_elems", C.c_size_t), ("n_real", C.c_int),
+                ("relu", C.c_int),
+                ("mask_out", _P), ("mask_in", _P), ("mask_bytes", C.c_size_t), ("mask_cols", C.c_int),
+                ("Cb", _P), ("cb_elems", C.c_size_t), ("ldc", C.c_int), ("c_col0", C.c_int),
+                ("Cf", _P), ("cf_elems", C.c_size_t), ("ldcf", C.c_int),
+                ("live", _P), ("n_live", C.c_longlong), ("live_dev", _P), ("live_dev_elems", C.c_size_t)]
+
+
+class DebugWgrad(C.Structure):
+    """knerf_debug_wgrad of include/knerf_debug.h"""
+    _fields_ = [("X", _P), ("x_elems", C.c_size_t), ("ldx", C.c_int),
+                ("Z", _P), ("z_elems", C.c_size_t), ("ldz", C.c_int),
+                ("steps", C.c_longlong), ("N", C.c_int), ("K", C.c_int),
+                ("grad", _P), ("grad_elems", C.c_size_t),
+                ("w_off", C.c_int), ("b_off", C.c_int), ("n_real", C.c_int),
+                ("n_seg", C.c_int), ("seg", C.c_int * 6),
+                ("partial", _P), ("partial_elems", C.c_size_t),
+                ("live", _P), ("n_live", C.c_longlong), ("live_dev", _P), ("live_dev_elems", C.c_size_t),
+                ("selector", C.c_int)]
 _probe = None
 
 
@@ -160,3 +191,112 @@ def compact_tiles(flags, period=1, real=1, stats=None):
     if rc != 0:
         raise _lib.KnerfError(f"knerf_debug_compact_tiles failed ({rc})")
     return lst, count
+
+
+def gemm_launch(M: int, N: int, K: int) -> dict:
+    """which GEMM kernel and grid launch_gemm picks for (M, N, K) (knerf_debug_generic_launch; no device needed)"""
+    out = (C.c_int32 * 8)()
+    if load().knerf_debug_generic_launch(0, int(M), int(N), int(K), 0, out) != 0:
+        raise ValueError(f"gemm_launch: bad shape {(M, N, K)}")
+    ws, nt, gx, gy, lds, pitch = out[:6]
+    tiles = M // 32
+    return dict(kernel="ws" if ws else "stream", nt=nt, gx=gx, gy=gy, lds=lds, pitch=pitch,
+                tiles_per_wave=-(-tiles // (8 * gx)) if ws else 1)
+
+
+def wgrad_launch(K: int, N: int, steps: int, per_wave: bool = False) -> dict:
+    """which weight-gradient kernel and grid launch_wgrad picks for a [K] x [N] layer over `steps` 32-row steps"""
+    out = (C.c_int32 * 8)()
+    if load().knerf_debug_generic_launch(1, int(steps), int(N), int(K), int(per_wave), out) != 0:
+        raise ValueError(f"wgrad_launch: bad shape {(K, N, steps)}")
+    coop, gx, gy, gz, kt, nt, n_slabs, slab = out[:8]
+    return dict(kernel="coop" if coop else "wave", gx=gx, gy=gy, gz=gz, kt=kt, nt=nt, units=n_slabs, slab_floats=slab)
+
+
+def wgrad_partial_floats(K: int, N: int, per_wave: bool = False) -> int:
+    n = C.c_size_t(0)
+    if load().knerf_debug_generic_wgrad_partial_floats(int(K), int(N), int(per_wave), C.byref(n)) != 0:
+        raise ValueError(f"wgrad_partial_floats: bad shape {(K, N)}")
+    return n.value
+
+
+def _live_fields(args, live, tiles, device, ascending=False):
+    """the live-tile list: a HOST int32 array (or None); checked here as well as in the library, which uploads it.  ascending: the
+    deterministic weight gradient finds a unit's tiles by binary search"""
+    import numpy as np
+    import torch
+    if live is None:
+        args.live, args.n_live, args.live_dev, args.live_dev_elems = None, -1, None, 0
+        return None
+    host = np.ascontiguousarray(np.asarray(live, dtype=np.int32).reshape(-1))
+    if host.size and (host.min() < 0 or host.max() >= tiles):
+        raise ValueError("live list entries must lie in [0, tiles)")
+    if ascending and host.size > 1 and (np.diff(host) <= 0).any():
+        raise ValueError("the deterministic mode wants a strictly ascending live list")
+    scratch = torch.full((host.size + 1,), -1, dtype=torch.int32, device=device)
+    args.live = C.c_void_p(host.ctypes.data) if host.size else None
+    args.n_live, args.live_dev, args.live_dev_elems = host.size, _dev_ptr(scratch), scratch.numel()
+    return host, scratch                     # kept alive by the caller until the launch has been enqueued
+
+
+def _bf16_ok(*ts):
+    import torch
+    return all(t is None or (t.is_cuda and t.dtype == torch.int16 and t.is_contiguous()) for t in ts)
+
+
+def generic_gemm(A, lda, Bt, ldb, M, N, K, bias=None, n_real=0, relu=False, mask_out=None, mask_in=None, mask_cols=0,
+                 Cb=None, ldc=0, c_col0=0, Cf=None, ldcf=0, live=None):
+    """One launch_gemm on caller-made CUDA tensors (knerf_debug_generic_gemm): bf16 buffers are flat int16 tensors (bit patterns),
+    bias / Cf float32, masks uint8.  live: None or a host array of 32-row tile indices.  Outputs are written in place.  Raises
+    ValueError when the library refuses the arguments (nothing has been launched then)."""
+    import torch
+    assert _bf16_ok(A, Bt, Cb)
+    assert all(t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()) for t in (bias, Cf))
+    assert all(t is None or (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()) for t in (mask_out, mask_in))
+    a = DebugGemm()
+    a.A, a.a_elems, a.lda = _dev_ptr(A), A.numel(), int(lda)
+    a.Bt, a.bt_elems, a.ldb = _dev_ptr(Bt), Bt.numel(), int(ldb)
+    a.M, a.N, a.K = int(M), int(N), int(K)
+    a.bias, a.bias_elems, a.n_real = _dev_ptr(bias), 0 if bias is None else bias.numel(), int(n_real)
+    a.relu = int(bool(relu))
+    mk = mask_out if mask_out is not None else mask_in
+    a.mask_out, a.mask_in, a.mask_bytes, a.mask_cols = _dev_ptr(mask_out), _dev_ptr(mask_in), 0 if mk is None else mk.numel(), int(mask_cols)
+    a.Cb, a.cb_elems, a.ldc, a.c_col0 = _dev_ptr(Cb), 0 if Cb is None else Cb.numel(), int(ldc), int(c_col0)
+    a.Cf, a.cf_elems, a.ldcf = _dev_ptr(Cf), 0 if Cf is None else Cf.numel(), int(ldcf)
+    keep = _live_fields(a, live, int(M) // 32, A.device)
+    stream = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+    rc = load().knerf_debug_generic_gemm(stream, C.byref(a))
+    del keep
+    if rc == _lib.KNERF_ERR_INVALID:
+        raise ValueError("knerf_debug_generic_gemm refused its arguments")
+    if rc != 0:
+        raise _lib.KnerfError(f"knerf_debug_generic_gemm failed ({rc})")
+
+
+def generic_wgrad(X, ldx, Z, ldz, steps, K, N, grad, w_off, b_off, n_real, segs, partial=None, live=None, per_wave=False):
+    """One launch_wgrad (+ the ordered reduce pass when `partial`, a float32 CUDA tensor of wgrad_partial_floats, is given) on
+    caller-made CUDA tensors (knerf_debug_generic_wgrad).  segs: one or two (buffer col0, width, kernel row0).  grad is added to in
+    place.  Raises ValueError when the library refuses the arguments."""
+    import torch
+    assert _bf16_ok(X, Z)
+    assert all(t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()) for t in (grad, partial))
+    a = DebugWgrad()
+    a.X, a.x_elems, a.ldx = _dev_ptr(X), X.numel(), int(ldx)
+    a.Z, a.z_elems, a.ldz = _dev_ptr(Z), Z.numel(), int(ldz)
+    a.steps, a.N, a.K = int(steps), int(N), int(K)
+    a.grad, a.grad_elems = _dev_ptr(grad), grad.numel()
+    a.w_off, a.b_off, a.n_real = int(w_off), int(b_off), int(n_real)
+    a.n_seg = len(segs)
+    for i, sg in enumerate(segs[:2]):
+        for j in range(3):
+            a.seg[3 * i + j] = int(sg[j])
+    a.partial, a.partial_elems = _dev_ptr(partial), 0 if partial is None else partial.numel()
+    keep = _live_fields(a, live, int(steps), X.device, ascending=partial is not None)
+    a.selector = int(bool(per_wave))
+    stream = C.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
+    rc = load().knerf_debug_generic_wgrad(stream, C.byref(a))
+    del keep
+    if rc == _lib.KNERF_ERR_INVALID:
+        raise ValueError("knerf_debug_generic_wgrad refused its arguments")
+    if rc != 0:
+        raise _lib.KnerfError(f"knerf_debug_generic_wgrad failed ({rc})")
