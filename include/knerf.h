@@ -626,6 +626,39 @@ int knerf_baked_render_bricks(void* stream, const knerf_baked_bricks* field, con
                               const float* near, const float* far, float near_all, float far_all, uint64_t n_rays, float step,
                               float termination, int flags, float* image, float* depth, float* opacity, int64_t* stats);
 
+/* ---- Optimising a brick field as it is.  Extension, no reference counterpart.  The two launches of "Optimising a baked field" above on
+ * the brick layout, so that no table of the dense lattice's size exists at any point; csrc/baked_bricks_train.hip.  The NumPy reference of
+ * a brick optimiser over a field F is tests/baked_train_reference.py on the dense arrays of F (absent bricks read as zero);
+ * tests/baked_bricks_train_reference.py restates the brick set, the flags and the row order.
+ * knerf_baked_bricks_train: HOST struct.  field: the optimiser's OWN brick set -- every brick that holds a corner of a SUPPORT cell,
+ * numbered as knerf_baked_bricks numbers stored bricks; records: knerf_baked_bricks_train_apply WRITES them; bits: the SUPPORT bitfield
+ * (as knerf_baked_train: the cells that are ever fetched, fixed while the field is optimised), never NULL here.  There is no slot table:
+ * grad, and master, m, v below, hold one row per STORED RECORD, fp32 [n_bricks b^3][1 + 3 K] in the column order of a record (sigma, then
+ * [k][c]), and a row's index is the record's index: slot b^3 + place.  Rows of records that are no corner of a support cell (and of places
+ * past the lattice) exist and stay zero. */
+typedef struct knerf_baked_bricks_train {
+    knerf_baked_bricks field;
+    float* grad;                 /* DEVICE */
+} knerf_baked_bricks_train;
+/* knerf_baked_bricks_train_rays -- extension, no reference counterpart.  knerf_baked_train_rays through the brick table: the same two
+ * marches, loss, gradient formulas, atomic adds and sq_err, every argument behind `train` as there.  Only a corner's address differs
+ * (formed as in knerf_baked_render_bricks).  A corner whose brick_of entry is < 0 or >= n_bricks reads as a zero record and NOTHING is
+ * added for it: a damaged table never becomes an out-of-range read or write.  For a brick set that holds every corner of every support
+ * cell the sums a row receives are those of knerf_baked_train_rays on the dense field, addend for addend.
+ * Lane variants: those of knerf_baked_train_rays (all of them build without scratch; 0 in the flags picks the library's default).
+ * KNERF_ERR_INVALID, before any launch: everything knerf_baked_render_bricks refuses of its field, NULL bits or grad, every argument error
+ * of knerf_baked_train_rays, a lane count the degree does not have among them. */
+int knerf_baked_bricks_train_rays(void* stream, const knerf_baked_bricks_train* train, const float* origins, const float* directions,
+                                  const float* near, const float* far, float near_all, float far_all, const float* target,
+                                  uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags, float* sq_err);
+/* knerf_baked_bricks_train_apply -- extension, no reference counterpart.  knerf_baked_train_apply over the stored records: the same Adam
+ * step, projection, record rewrite (fp32 sigma, coefficients to fp16 to nearest even, zero padding) and zeroing of the gradient row.
+ * flags: uint8 [n_bricks b^3]; bit 0: the record is a slot (a corner of a support cell), bit 1: its sigma is trainable.  A record without
+ * bit 0 is skipped entirely: its record, master, m, v and grad keep their bytes.  master, m, v: fp32 rows like grad.
+ * KNERF_ERR_INVALID: as above, a NULL flags, master, m or v, a rate that is not finite, a beta outside [0, 1), epsilon <= 0. */
+int knerf_baked_bricks_train_apply(void* stream, const knerf_baked_bricks_train* train, const uint8_t* flags, float* master, float* m,
+                                   float* v, float rate_sigma, float rate_sh, float beta_1, float beta_2, float epsilon);
+
 /* Diagnostics (layout tables, workspace views, hardware-fact and bandwidth probes) are NOT part of this library: they are
  * declared in include/knerf_debug.h and built into libknerf_probe.so for tests/ and tools/ only. */
 

@@ -57,6 +57,12 @@ class KnerfBakedBricks(C.Structure):
                 ("n_bricks", C.c_uint64)]
 
 
+class KnerfBakedBricksTrain(C.Structure):
+    """struct knerf_baked_bricks_train (include/knerf.h): the optimiser's brick field (bits = the support) and the gradient rows, one
+    per stored record"""
+    _fields_ = [("field", KnerfBakedBricks), ("grad", C.c_void_p)]
+
+
 BAKED_WHITE_BACKGROUND, BAKED_SKIP_EMPTY, BAKED_LANES_SHIFT = 1, 2, 8
 SPACING_LINEAR, SPACING_DISPARITY = 0, 1
 SPACINGS = {"linear": SPACING_LINEAR, "disparity": SPACING_DISPARITY}
@@ -146,6 +152,10 @@ SIGNATURES = {
     "knerf_baked_resample": (C.c_int, [_P, C.POINTER(KnerfBakedField), C.POINTER(C.c_int32), C.c_float, _P]),
     "knerf_baked_render_bricks": (C.c_int, [_P, C.POINTER(KnerfBakedBricks), _F, _F, _F, _F, C.c_float, C.c_float, C.c_uint64, C.c_float,
                                             C.c_float, C.c_int, _F, _F, _F, _P]),
+    "knerf_baked_bricks_train_rays": (C.c_int, [_P, C.POINTER(KnerfBakedBricksTrain), _F, _F, _F, _F, C.c_float, C.c_float, _F, C.c_uint64,
+                                                C.c_uint64, C.c_float, C.c_float, C.c_int, _F]),
+    "knerf_baked_bricks_train_apply": (C.c_int, [_P, C.POINTER(KnerfBakedBricksTrain), _P, _F, _F, _F, C.c_float, C.c_float, C.c_float,
+                                                 C.c_float, C.c_float]),
 }
 
 _lib = None

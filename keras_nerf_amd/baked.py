@@ -632,7 +632,8 @@ class BrickBakedField:
     """A BakedField stored sparsely (include/knerf.h knerf_baked_bricks): the lattice cut into bricks of brick^3 points, only those with
     a corner of an occupied cell stored, behind the int32 table brick_of [Bx,By,Bz] (slot or -1); every other record reads as zero.
     render() marches rays through it on the GPU and gives the bits of the dense field's render().  Built by BakedField.compact,
-    NeRF.bake(bricks=...) or BrickBakedField.load; to_dense() leads back (optimising and resampling work on a BakedField)."""
+    NeRF.bake(bricks=...) or BrickBakedField.load; to_dense() leads back.  baked_train.brick_optimizer(field, ...) optimises it as it
+    is; resampling, the total-variation regulariser and fit_coarse_to_fine work on a BakedField."""
 
     def __init__(self, records, brick_of, words, resolution, bounds, sh_degree, brick=DEFAULT_BRICK, sigma_threshold=0.0):
         # uint8 [n_bricks, b^3, record bytes], int32 [Bx,By,Bz], int32 [ceil(cells / 32)] on the device
@@ -768,7 +769,7 @@ class BrickBakedField:
 def __getattr__(name):
     """the optimiser's names live in baked_train.py (which imports this module) and are reachable from here as well"""
     if name in ("BakedFieldOptimizer", "check_optimizer_args", "check_target_shape", "bias_corrected_rate", "check_tv_args",
-                "fit_coarse_to_fine"):
+                "fit_coarse_to_fine", "BrickFieldOptimizer", "brick_optimizer", "BRICK_TRAIN_VARIANTS"):
         from . import baked_train
         return getattr(baked_train, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -250,6 +250,25 @@ class BakedFieldOptimizer:
         return BakedField(records, words, f.resolution, f.bounds, f.sh_degree, thr)
 
 
+def brick_optimizer(field, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
+                    white_background=False, termination=0.0, lanes_per_ray=0):
+    """A BrickFieldOptimizer (baked_bricks_train.py) over a COPY of a BrickBakedField's bricks: BakedField.optimizer for a field
+    stored as sparse bricks, with the same arguments and meaning, optimised as it is (no table of the dense lattice's size is formed;
+    finish() gives a BrickBakedField).  There is no total-variation regulariser here: tv_sigma, tv_sh and tv_epsilon belong to the
+    dense optimiser (field.to_dense().optimizer(...)), as resampling and fit_coarse_to_fine do."""
+    from .baked_bricks_train import BrickFieldOptimizer
+    return BrickFieldOptimizer(field, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
+                               termination, lanes_per_ray)
+
+
+def __getattr__(name):
+    """the brick optimiser's names live in baked_bricks_train.py (which imports this module) and are reachable from here as well"""
+    if name in ("BrickFieldOptimizer", "BRICK_TRAIN_VARIANTS"):
+        from . import baked_bricks_train
+        return getattr(baked_bricks_train, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def check_stages(stages):
     """ValueError unless stages is a non-empty sequence of (resolution | None, steps) with steps a non-negative integer; returns
     them as a list of (resolution | None, int).  The resolutions themselves are checked by BakedField.resample."""
