@@ -659,6 +659,53 @@ int knerf_baked_bricks_train_rays(void* stream, const knerf_baked_bricks_train* 
 int knerf_baked_bricks_train_apply(void* stream, const knerf_baked_bricks_train* train, const uint8_t* flags, float* master, float* m,
                                    float* v, float rate_sigma, float rate_sh, float beta_1, float beta_2, float epsilon);
 
+/* ---- Refining camera poses against a baked field.  Extension, no reference counterpart (BARF, NeRF-- and the current toolkits optimise
+ * their cameras with the field).  Three context-free launches; csrc/baked_pose.hip, tests/baked_pose_reference.py restates them in fp64,
+ * DESIGN.md 2.24 has the derivation.  The MLP path has no input gradient; NDC rays are not covered (the pose does not enter them as
+ * o = t, d = R cam). */
+/* knerf_baked_ray_gradients -- extension, no reference counterpart.  The gradient of the objective of knerf_baked_train_rays,
+ *   L = (1 / 3 N) sum_rays sum_c (out_c - target_c)^2,  N = n_norm (0: n_rays),
+ * with respect to every ray's origin and direction.  field->bits is the support that is marched (never NULL here); rays, near / far,
+ * target, n_norm, step, termination and flags are those of knerf_baked_train_rays, and so are the forward march, both clamps, the
+ * white background, the termination cut and dsig_j = dL/dsigma_j, dr_jc = dL/dr_jc (total minus prefix).  With t_j the sample's ray
+ * parameter, u = d / |d|, delta = step |d|, fr the fractions of the sample in its cell, scale_a = (R_a - 1) / (hi_a - lo_a):
+ *   G_j            = scale * (dsig_j grad_fr sigma + sum_c dr_jc grad_fr r_c)      grad_fr: the trilinear weights' derivative, the 8 corners
+ *                                                                                 with one factor replaced by +-1; r_c of a corner = sum_k Y_k(u) coef_kc
+ *   grad_origin    = sum_j G_j
+ *   grad_direction = sum_j t_j G_j + (sum_j dsig_j sigma_j) (step / delta) u + (1 / |d|) (I - u u^T) sum_j sum_c dr_jc sum_k cf_jkc grad Y_k(u)
+ * grad Y_k: the gradient of the polynomials of sh_eval as written (the projection removes the choice of extension off the sphere).
+ * The discontinuities carry no gradient (a sample entering or leaving the box, the window or a cell's support, the termination cut,
+ * the clamps): the convention of knerf_baked_train_rays.  |d| = 0: both gradients are zero.
+ * grad_origin, grad_direction: fp32 [n_rays,3], WRITTEN for every ray (zeros where nothing contributes), each ray's by its own lane
+ * group, once: no atomics, no scratch buffer, the same bits on every launch.  sq_err: [n_rays] or NULL, as knerf_baked_train_rays.
+ * Lane variants: those of knerf_baked_train_rays (they differ in summation order only).
+ * KNERF_ERR_INVALID, before any launch: NULL field, records, bits, origins, directions, target, grad_origin or grad_direction; and every
+ * argument error of knerf_baked_train_rays. */
+int knerf_baked_ray_gradients(void* stream, const knerf_baked_field* field, const float* origins, const float* directions,
+                              const float* near, const float* far, float near_all, float far_all, const float* target, uint64_t n_rays,
+                              uint64_t n_norm, float step, float termination, int flags, float* grad_origin, float* grad_direction,
+                              float* sq_err);
+/* knerf_baked_ray_gradients_bricks -- extension, no reference counterpart.  knerf_baked_ray_gradients through the brick table: the same
+ * kernel, only a corner's address differs (formed as in knerf_baked_render_bricks; a brick_of entry < 0 or >= n_bricks reads as a zero
+ * record, never as an out-of-range address).  For a brick field that holds the dense field's stored bricks the outputs are
+ * bit-identical to knerf_baked_ray_gradients' at the same lane variant.
+ * KNERF_ERR_INVALID, before any launch: as above, and everything knerf_baked_render_bricks refuses of its field. */
+int knerf_baked_ray_gradients_bricks(void* stream, const knerf_baked_bricks* field, const float* origins, const float* directions,
+                                     const float* near, const float* far, float near_all, float far_all, const float* target,
+                                     uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags, float* grad_origin,
+                                     float* grad_direction, float* sq_err);
+/* knerf_pose_gradients -- extension, no reference counterpart.  Per-ray gradients summed to one rigid-motion gradient per camera:
+ *   out[v][0..2] = sum_{view[i] = v} grad_origin[i]                        (tau)
+ *   out[v][3..5] = sum_{view[i] = v} directions[i] x grad_direction[i]     (omega)
+ * the derivative at 0 of R <- exp(omega^) R, t <- t + tau for rays o = t, d = R cam (normalised or not): it needs neither the
+ * camera-space direction nor the focal length.  view: int32 [n_rays], the camera of every ray (the Python package divides the flat
+ * pixel index of knerf_draw_ray_batch by the pixels per view); an index outside [0, n_views) is skipped.  out: DOUBLE [n_views][6],
+ * written whole (a view without a ray gets zeros).  The sums are formed in double in a fixed order without atomics: two launches on
+ * the same inputs give the same bits.
+ * KNERF_ERR_INVALID, before any launch: a NULL pointer; n_rays >= 2^36; n_views >= 2^31. */
+int knerf_pose_gradients(void* stream, const float* grad_origin, const float* grad_direction, const float* directions,
+                         const int32_t* view, uint64_t n_rays, uint64_t n_views, double* out);
+
 /* Diagnostics (layout tables, workspace views, hardware-fact and bandwidth probes) are NOT part of this library: they are
  * declared in include/knerf_debug.h and built into libknerf_probe.so for tests/ and tools/ only. */
 

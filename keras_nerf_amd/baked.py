@@ -508,6 +508,13 @@ class BakedField:
         return BakedFieldOptimizer(self, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
                                    termination, lanes_per_ray, tv_sigma, tv_sh, tv_epsilon)
 
+    # ---- how the objective moves when a ray moves (baked_pose.py: refining camera poses)
+    def ray_gradients(self, origins, directions, near, far, target, step=None, white_background=False, termination=0.0, n_total=None,
+                      lanes_per_ray=0):
+        """baked_pose.ray_gradients(self, ...): (grad_origin [N,3], grad_direction [N,3], loss) of the squared error against `target`"""
+        from .baked_pose import ray_gradients
+        return ray_gradients(self, origins, directions, near, far, target, step, white_background, termination, n_total, lanes_per_ray)
+
     # ---- sparse storage
     def compact(self, brick=DEFAULT_BRICK):
         """This field as a BrickBakedField: only the bricks of brick^3 lattice points (4 or 8) that hold a corner of an occupied cell
@@ -764,6 +771,13 @@ class BrickBakedField:
         if stats:
             out["stats"] = counter
         return out
+
+    # ---- how the objective moves when a ray moves (baked_pose.py: refining camera poses)
+    def ray_gradients(self, origins, directions, near, far, target, step=None, white_background=False, termination=0.0, n_total=None,
+                      lanes_per_ray=0):
+        """baked_pose.ray_gradients(self, ...): (grad_origin [N,3], grad_direction [N,3], loss) of the squared error against `target`"""
+        from .baked_pose import ray_gradients
+        return ray_gradients(self, origins, directions, near, far, target, step, white_background, termination, n_total, lanes_per_ray)
 
 
 def __getattr__(name):

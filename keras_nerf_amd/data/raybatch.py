@@ -111,6 +111,24 @@ class RayBatchDataset:
             raise ValueError("steps_per_epoch must be positive")
         self._perm, self._step, self._drawn = 0, 0, 0          # permutation in use, steps taken from it, batches drawn in all
         self._rg, self.last_draw = None, None
+        self._cameras, self.last_view = None, None             # set_cameras: who says where the cameras stand; the rays' views
+
+    def set_cameras(self, provider):
+        """provider: None (default: the dataset's own camera matrices, and the batches are what they always were) or a callable
+        returning the [V,4,4] float32 device tensor of camera-to-world matrices to draw the NEXT batch with, asked once per batch
+        (baked_pose.PoseOptimizer.poses while the poses are refined).  With a provider every draw also leaves the camera of each ray
+        in `last_view` (int32 [n] on the device): the flat pixel index of knerf_draw_ray_batch over the pixels per view."""
+        if provider is not None and not callable(provider):
+            raise ValueError(f"cameras must be None or a callable returning a [V,4,4] device tensor, got {provider!r}")
+        self._cameras = provider
+        if provider is None:
+            self.last_view = None
+
+    def ray_model(self):
+        """the struct knerf_ray_model the batches are drawn with, None for the plain pinhole rays (the ray generator's own answer)"""
+        if self._rg is None:
+            self._rg = self._images._rg_factory(self._images._placement()[0])
+        return getattr(self._rg, "ray_model", None)
 
     def __len__(self):
         return self.steps_per_epoch if self.steps_per_epoch is not None else self.n_pixels // self.rays_per_step
@@ -173,7 +191,17 @@ class RayBatchDataset:
                 stream = self._drawn * world + rank
                 self._drawn += 1
                 self.last_draw = (perm, first, n)              # what the batch just yielded holds: positions [first, first + n) of `perm`
-                o, d, t, target = draw_ray_batch(dev, cams, rg.focal_length, rg.near, rg.far, rg.n_sample, self.seed, perm, first, n,
-                                                 noise_stream=stream, **extra)
+                if self._cameras is None:
+                    o, d, t, target = draw_ray_batch(dev, cams, rg.focal_length, rg.near, rg.far, rg.n_sample, self.seed, perm, first, n,
+                                                     noise_stream=stream, **extra)
+                else:
+                    import torch
+                    now = self._cameras()
+                    if tuple(now.shape) != tuple(cams.shape) or now.dtype != cams.dtype or now.device != cams.device:
+                        raise ValueError(f"the camera provider returned {tuple(now.shape)} {now.dtype} on {now.device}; the dataset "
+                                         f"draws from {tuple(cams.shape)} {cams.dtype} on {cams.device}")
+                    o, d, t, target, index = draw_ray_batch(dev, now.contiguous(), rg.focal_length, rg.near, rg.far, rg.n_sample,
+                                                            self.seed, perm, first, n, noise_stream=stream, want_index=True, **extra)
+                    self.last_view = torch.div(index, self._rows * self._cols, rounding_mode="floor").to(torch.int32)
                 yield target, (o, d, t)
         return gen()
