@@ -706,6 +706,58 @@ int knerf_baked_ray_gradients_bricks(void* stream, const knerf_baked_bricks* fie
 int knerf_pose_gradients(void* stream, const float* grad_origin, const float* grad_direction, const float* directions,
                          const int32_t* view, uint64_t n_rays, uint64_t n_views, double* out);
 
+/* ---- The brick baked field with 8-bit SH coefficients.  Extension, no reference counterpart (PlenOctrees and SNeRG ship their SH
+ * coefficients as 8-bit values with a scale).  Three context-free launches; csrc/baked_quant.hip, tests/baked_quant_reference.py restates
+ * the format in NumPy, DESIGN.md 2.25 has the exactness argument.
+ * SOURCE: any knerf_baked_bricks set: records [n_bricks][b^3], b = 4 or 8, degree 0..3, K = (degree + 1)^2 coefficients [k][c].
+ * BANDS: coefficient k belongs to SH band l = floor(sqrt(k)).
+ * EXPONENT: one exponent e per stored brick s and band l <= degree.  M = the maximum of |c| over all b^3 places of the brick, all k of
+ *   band l and all three channels (untouched points and the zero places past the lattice included), the values read as their stored
+ *   fp16 bits, a NaN counting as 0.  e = the smallest integer in [-24, 9] with 127 2^e >= M; if there is none, e = 9; M = 0 gives
+ *   e = -24.  Stored as uint32 exponents[n_bricks]: byte l (bits 8l..8l+7) holds e as a two's-complement int8; bytes of bands above the
+ *   degree are written 0 and are never trusted by a reader.
+ * COEFFICIENT: q = clamp(rint(c 2^-e), -127, 127): the product is exact in fp32 and rounded to nearest even; NaN becomes 0; +-inf and
+ *   magnitudes above 65024 saturate to +-127 at e = 9.  q is stored as a two's-complement int8.  Decoded value: dec = (float)q 2^e,
+ *   exact in fp32 and exactly representable in fp16: 127 x 2^9 <= 65504, so decoding never overflows, and e >= -24, so every decoded
+ *   value is a multiple of the fp16 subnormal spacing.  For |c| <= 65024: |c - dec| <= 2^(e-1), which for e > -24 is < M / 127.
+ * RECORD: 8 / 16 / 32 / 64 bytes for degree 0 / 1 / 2 / 3.  Bytes 0..3: the fp32 sigma, copied bit for bit; byte 4 + 3 k + c: q[k][c];
+ *   zero padding fills the rest and a reader never trusts it.  A zero record decodes to zeros, so absent bricks and places past the
+ *   lattice behave as they do in knerf_baked_bricks.  brick_of, the occupancy bits, resolution, bounds, brick size are the source
+ *   field's, unchanged (the quantised field may share the source's brick_of and bits): empty-space skipping stays bit-exact.
+ * Consequences: quantising the dequantised records gives the quantised records and exponents back byte for byte; the dequantised
+ * records are an ordinary knerf_baked_bricks set, and knerf_baked_render_qbricks with one ray per lane gives the bits of
+ * knerf_baked_render_bricks with one ray per lane on them. */
+typedef struct knerf_baked_qbricks {
+    knerf_baked_bricks bricks;   /* bricks.records: the QUANTISED records, DEVICE */
+    const uint32_t* exponents;   /* DEVICE, [n_bricks] */
+} knerf_baked_qbricks;
+/* knerf_baked_quantize_bricks -- extension, no reference counterpart.  Encodes the records of src: dst_exponents [n_bricks] and
+ * dst_records [n_bricks][b^3] quantised records are WRITTEN whole (padding and unused exponent bytes as zeros).  One workgroup per stored
+ * brick; the band maxima are order-independent, so two launches give the same bytes; no atomics, no host read.  src->brick_of and
+ * src->bits are not read and may be NULL.
+ * KNERF_ERR_INVALID, before any launch: NULL src, records, dst_records or dst_exponents; everything knerf_baked_render_bricks refuses of
+ * its field (degree, brick_log2, resolution, bounds, n_bricks, n_bricks x b^3 x either record size >= 2^40); destination records or
+ * exponents that overlap the source records or each other. */
+int knerf_baked_quantize_bricks(void* stream, const knerf_baked_bricks* src, void* dst_records, uint32_t* dst_exponents);
+/* knerf_baked_dequantize_bricks -- extension, no reference counterpart.  dst_records [n_bricks][b^3] ordinary brick records: the sigma
+ * bits copied, the coefficients dec rounded to fp16 (exact), zero padding.  An exponent byte outside [-24, 9] is clamped into it.
+ * KNERF_ERR_INVALID, before any launch: as above with NULL exponents; dst_records overlapping the source records or exponents. */
+int knerf_baked_dequantize_bricks(void* stream, const knerf_baked_qbricks* src, void* dst_records);
+/* knerf_baked_render_qbricks -- extension, no reference counterpart.  knerf_baked_render_bricks on the quantised records as they are:
+ * the same march, every argument behind `field` as there.  Only the fetch differs: the record has the size above, the exponent word of a
+ * corner's brick is read by slot, and every corner's coefficients are decoded to fp32 before they enter the trilinear sum (the 8 corners
+ * may lie in 8 bricks with 8 exponents; the group variants multiply the corner's weight by 2^e instead, which is exact short of
+ * underflow and gives fma the same exact product).  A brick_of value < 0 or >= n_bricks reads as a zero record; an exponent byte outside [-24, 9]
+ * is clamped into it: a damaged table never becomes an out-of-range read or a value that is not finite.
+ * Lanes per ray (bits 8..11 of flags): 0 = the library's choice, 1 = one ray per lane (every degree; the sums run in the order of
+ * knerf_baked_render_bricks' one-ray-per-lane variant), 2 (degree 2) / 4 (degree 3) = every lane of a group reads one 16-byte chunk of a
+ * record; the choices differ in summation order only.
+ * KNERF_ERR_INVALID, before any launch: everything knerf_baked_render_bricks refuses; NULL exponents; a lane count the degree does not
+ * have. */
+int knerf_baked_render_qbricks(void* stream, const knerf_baked_qbricks* field, const float* origins, const float* directions,
+                               const float* near, const float* far, float near_all, float far_all, uint64_t n_rays, float step,
+                               float termination, int flags, float* image, float* depth, float* opacity, int64_t* stats);
+
 /* Diagnostics (layout tables, workspace views, hardware-fact and bandwidth probes) are NOT part of this library: they are
  * declared in include/knerf_debug.h and built into libknerf_probe.so for tests/ and tools/ only. */
 

@@ -57,6 +57,11 @@ class KnerfBakedBricks(C.Structure):
                 ("n_bricks", C.c_uint64)]
 
 
+class KnerfBakedQBricks(C.Structure):
+    """struct knerf_baked_qbricks (include/knerf.h): a brick set whose records are the quantised ones, and the exponent word per brick"""
+    _fields_ = [("bricks", KnerfBakedBricks), ("exponents", C.c_void_p)]
+
+
 class KnerfBakedBricksTrain(C.Structure):
     """struct knerf_baked_bricks_train (include/knerf.h): the optimiser's brick field (bits = the support) and the gradient rows, one
     per stored record"""
@@ -161,6 +166,10 @@ SIGNATURES = {
     "knerf_baked_ray_gradients_bricks": (C.c_int, [_P, C.POINTER(KnerfBakedBricks), _F, _F, _F, _F, C.c_float, C.c_float, _F, C.c_uint64,
                                                    C.c_uint64, C.c_float, C.c_float, C.c_int, _F, _F, _F]),
     "knerf_pose_gradients": (C.c_int, [_P, _F, _F, _F, _P, C.c_uint64, C.c_uint64, _P]),
+    "knerf_baked_quantize_bricks": (C.c_int, [_P, C.POINTER(KnerfBakedBricks), _P, _P]),
+    "knerf_baked_dequantize_bricks": (C.c_int, [_P, C.POINTER(KnerfBakedQBricks), _P]),
+    "knerf_baked_render_qbricks": (C.c_int, [_P, C.POINTER(KnerfBakedQBricks), _F, _F, _F, _F, C.c_float, C.c_float, C.c_uint64, C.c_float,
+                                             C.c_float, C.c_int, _F, _F, _F, _P]),
 }
 
 _lib = None

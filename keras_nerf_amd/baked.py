@@ -4,7 +4,8 @@ no reference counterpart; PlenOctrees, SNeRG and Plenoxels bake a trained NeRF i
 The arithmetic is HIP (csrc/baked.hip: knerf_baked_project, knerf_baked_pack, knerf_baked_render; include/knerf.h holds the contract;
 BakedField.optimizer and baked_train.py: optimising the records against ray batches, csrc/baked_train.hip;
 BakedField.resample and the optimiser's TV regulariser: csrc/baked_grow.hip;
-BrickBakedField, the same field stored as sparse bricks behind an index table, and its renderer: csrc/baked_bricks.hip);
+BrickBakedField, the same field stored as sparse bricks behind an index table, and its renderer: csrc/baked_bricks.hip;
+baked_quant.py QuantizedBrickField, the brick field with 8-bit SH coefficients, its codec and renderer: csrc/baked_quant.hip);
 torch is used for device memory, streams and the index plumbing of the bake only.  Host-side pieces (basis, fit matrix, record
 layout) are NumPy and need no device.
 """
@@ -527,6 +528,10 @@ class BakedField:
         _gather_bricks(self._records.view(torch.int32), brick_of, self.resolution, b, records.view(torch.int32))
         return BrickBakedField(records, brick_of, self._words, self.resolution, self.bounds, self.sh_degree, b, self.sigma_threshold)
 
+    def quantize(self, brick=DEFAULT_BRICK, bits=8):
+        """compact(brick).quantize(bits): this field as a baked_quant.QuantizedBrickField"""
+        return self.compact(brick).quantize(bits)
+
 
 def _brick_table_device(occupied, resolution, b):
     """brick_table on the device: occupied bool [Rx-1,Ry-1,Rz-1] -> (brick_of int32 [Bx,By,Bz], number of stored bricks; the one host
@@ -623,7 +628,7 @@ def read_brick_file(path) -> dict:
 
 
 def load_field(path, device=None):
-    """BakedField.load or BrickBakedField.load, whichever wrote `path` (its format says)"""
+    """BakedField.load, BrickBakedField.load or QuantizedBrickField.load, whichever wrote `path` (its format says)"""
     with np.load(path) as z:
         if "format" not in z.files or np.ndim(z["format"]) != 0:
             raise ValueError(f"{path}: not a baked field (no format)")
@@ -632,6 +637,9 @@ def load_field(path, device=None):
         return BakedField.load(path, device)
     if fmt == 2:
         return BrickBakedField.load(path, device)
+    if fmt == 3:
+        from .baked_quant import QuantizedBrickField
+        return QuantizedBrickField.load(path, device)
     raise ValueError(f"{path}: unknown baked-field format {fmt}")
 
 
@@ -779,6 +787,15 @@ class BrickBakedField:
         from .baked_pose import ray_gradients
         return ray_gradients(self, origins, directions, near, far, target, step, white_background, termination, n_total, lanes_per_ray)
 
+    # ---- 8-bit SH coefficients
+    def quantize(self, bits=8):
+        """This field as a baked_quant.QuantizedBrickField (knerf_baked_quantize_bricks; the format is stated in include/knerf.h
+        knerf_baked_qbricks): the SH coefficients as 8-bit values with one power-of-two scale per brick and SH band, records of
+        8 / 16 / 32 / 64 bytes; density, the brick table and the occupancy bits are shared with this field, which is left as it is.
+        bits: only 8 exists."""
+        from .baked_quant import quantize_field
+        return quantize_field(self, bits)
+
 
 def __getattr__(name):
     """the optimiser's names live in baked_train.py (which imports this module) and are reachable from here as well"""
@@ -786,6 +803,9 @@ def __getattr__(name):
                 "fit_coarse_to_fine", "BrickFieldOptimizer", "brick_optimizer", "BRICK_TRAIN_VARIANTS"):
         from . import baked_train
         return getattr(baked_train, name)
+    if name in ("QuantizedBrickField", "quantized_record_bytes", "quantize_bricks", "dequantize_bricks", "read_quantized_brick_file"):
+        from . import baked_quant          # (it imports this module)
+        return getattr(baked_quant, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
@@ -799,13 +819,14 @@ def _unpack_words(words, cells):
 
 
 def bake(nerf, resolution=256, bounds=((-1.5,) * 3, (1.5,) * 3), net="fine", sh_degree=2, n_directions=None, sigma_threshold=0.0,
-         slab_bytes=SLAB_BYTES, bricks=None):
+         slab_bytes=SLAB_BYTES, bricks=None, quantize=False):
     """NeRF.bake: see there.  The work list is processed in slabs: accumulator and compensation of ONE slab ([slab, K, 3] fp32 each,
     together at most slab_bytes) are summed over the directions and packed into the records before the next slab starts, so the
     working memory does not grow with the lattice.  Nothing waits for the GPU between slabs and directions; the one host read is the
     length of the work list.  slab_bytes is a tuning / diagnostic knob (tests force several slabs with it), not a promised part of the
     interface.  bricks = 4 or 8: the same work list in the same slabs is packed straight into a BrickBakedField (the dense record table
-    is never allocated); the result is bake(...).compact(bricks) byte for byte."""
+    is never allocated); the result is bake(...).compact(bricks) byte for byte.  quantize=True (needs bricks): the QuantizedBrickField
+    bake(bricks=b).quantize(), byte for byte; the unquantised brick field exists transiently."""
     import torch
     from .runtime import _ptr, baked_project, occupancy_words_from_grid
     deg = check_degree(sh_degree)
@@ -813,6 +834,8 @@ def bake(nerf, resolution=256, bounds=((-1.5,) * 3, (1.5,) * 3), net="fine", sh_
     dirs, P = fit_directions(deg, n_directions)
     thr = check_threshold(sigma_threshold)
     brick = None if bricks is None else check_brick(bricks)
+    if quantize and brick is None:
+        raise ValueError("quantize=True needs bricks = 4 or 8: only a brick field can be quantised")
     if isinstance(slab_bytes, bool) or int(slab_bytes) != slab_bytes or int(slab_bytes) < 1:
         raise ValueError(f"slab_bytes must be a positive integer, got {slab_bytes!r}")
     n_net = nerf._field_net(net)
@@ -857,4 +880,4 @@ def bake(nerf, resolution=256, bounds=((-1.5,) * 3, (1.5,) * 3), net="fine", sh_
             field._pack(sigma, a, e, idx)
     if brick is not None:
         field._bake_sigma = None
-    return field
+    return field.quantize() if quantize else field

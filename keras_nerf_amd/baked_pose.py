@@ -37,6 +37,8 @@ def ray_gradients(field, origins, directions, near, far, target, step=None, whit
     import torch
     from . import _lib
     from .runtime import _f32, _ptr
+    if hasattr(field, "dequantize"):
+        raise ValueError("ray_gradients needs a BakedField or a BrickBakedField, got a QuantizedBrickField: dequantize() gives one")
     if not isinstance(field, (BakedField, BrickBakedField)):
         raise ValueError(f"ray_gradients needs a BakedField or a BrickBakedField, got {type(field).__name__}")
     check_render_args(step, termination, ("image",), field.sh_degree, lanes_per_ray)

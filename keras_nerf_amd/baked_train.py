@@ -257,6 +257,9 @@ def brick_optimizer(field, learning_rate_sigma, learning_rate_sh, beta_1=0.9, be
     finish() gives a BrickBakedField).  There is no total-variation regulariser here: tv_sigma, tv_sh and tv_epsilon belong to the
     dense optimiser (field.to_dense().optimizer(...)), as resampling and fit_coarse_to_fine do."""
     from .baked_bricks_train import BrickFieldOptimizer
+    from .baked_quant import QuantizedBrickField
+    if isinstance(field, QuantizedBrickField):
+        raise ValueError("a brick optimiser is built on a BrickBakedField, got a QuantizedBrickField: dequantize() gives one")
     return BrickFieldOptimizer(field, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
                                termination, lanes_per_ray)
 

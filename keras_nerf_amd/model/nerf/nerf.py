@@ -448,7 +448,7 @@ class NeRF:
         return verts, faces, normals, colors
 
     def bake(self, resolution=256, bounds=((-1.5,) * 3, (1.5,) * 3), net="fine", sh_degree=2, n_directions=None, sigma_threshold=0.0,
-             bricks=None):
+             bricks=None, quantize=False):
         """Bake the trained field into a keras_nerf_amd.baked.BakedField: density_grid(resolution, bounds, net) with every value
         <= sigma_threshold stored as 0, and at every lattice point that touches an occupied cell the colour as a function of the view
         direction, fitted by least squares with real spherical harmonics up to sh_degree (0..3) from the net's colour along
@@ -457,9 +457,12 @@ class NeRF:
         the resolution.  BakedField.render then renders novel views from the grid alone, without the MLP.
         bricks = 4 or 8 (default None: the dense BakedField, as ever): bake straight into a keras_nerf_amd.baked.BrickBakedField that
         stores only the bricks of bricks^3 lattice points around occupied cells; the dense record table is never allocated and the
-        result is bake(...).compact(bricks) byte for byte."""
+        result is bake(...).compact(bricks) byte for byte.
+        quantize=True (default False; needs bricks, ValueError otherwise): the keras_nerf_amd.baked_quant.QuantizedBrickField
+        bake(bricks=bricks).quantize(), byte for byte -- SH coefficients as 8-bit values with a scale per brick and SH band, records
+        of half the size.  The unquantised brick field exists transiently while the result is formed."""
         from ...baked import bake
-        return bake(self, resolution, bounds, net, sh_degree, n_directions, sigma_threshold, bricks=bricks)
+        return bake(self, resolution, bounds, net, sh_degree, n_directions, sigma_threshold, bricks=bricks, quantize=quantize)
 
     # ------------------------------------------------------------------ empty-space skipping for rendering (extension)
     def build_occupancy_grid(self, resolution=128, bounds=((-1.5,) * 3, (1.5,) * 3), threshold=0.0, dilation=1, outside="occupied"):
