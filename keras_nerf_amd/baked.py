@@ -4,7 +4,7 @@ no reference counterpart; PlenOctrees, SNeRG and Plenoxels bake a trained NeRF i
 The arithmetic is HIP (csrc/baked.hip: knerf_baked_project, knerf_baked_pack, knerf_baked_render; include/knerf.h holds the contract;
 BakedField.optimizer and baked_train.py: optimising the records against ray batches, csrc/baked_train.hip;
 BakedField.resample and the optimiser's TV regulariser: csrc/baked_grow.hip;
-BrickBakedField, the same field stored as sparse bricks behind an index table, and its renderer: csrc/baked_bricks.hip;
+BrickBakedField, the same field stored as sparse bricks behind an index table, and its renderer: csrc/baked.hip;
 baked_quant.py QuantizedBrickField, the brick field with 8-bit SH coefficients, its codec and renderer: csrc/baked_quant.hip);
 torch is used for device memory, streams and the index plumbing of the bake only.  Host-side pieces (basis, fit matrix, record
 layout) are NumPy and need no device.

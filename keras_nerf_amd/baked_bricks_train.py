@@ -1,7 +1,7 @@
 """Optimising a brick baked field as it is (extension, no reference counterpart): BakedFieldOptimizer (baked_train.py) on the brick
 layout of BrickBakedField, so that bake(bricks=) -> fine-tune -> finish() -> save never forms a tensor of the dense record table's size.
 
-The arithmetic is HIP (csrc/baked_bricks_train.hip: knerf_baked_bricks_train_rays is knerf_baked_train_rays with a corner's address
+The arithmetic is HIP (csrc/baked_train.hip: knerf_baked_bricks_train_rays is knerf_baked_train_rays with a corner's address
 formed through the brick table, knerf_baked_bricks_train_apply is knerf_baked_train_apply over the stored records; include/knerf.h holds
 the contract).  torch is used for device memory, streams and the index plumbing of construction and finish() only; that plumbing works
 brick slab by brick slab (baked._brick_slabs) and on dense per-point SCALARS of at most 4 bytes (sigma, bool masks), never on dense

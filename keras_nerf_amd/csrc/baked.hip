@@ -1,5 +1,7 @@
-// baked.hip -- the trained field baked into a voxel grid with spherical-harmonic colour, and its renderer (gfx950), context-free.
-// Extension: the reference has nothing of the kind (PlenOctrees / SNeRG / Plenoxels bake a trained NeRF in this way).
+// baked.hip -- the trained field baked into a voxel grid with spherical-harmonic colour, and its renderer for dense and for brick
+// storage (gfx950), context-free.  Extension: the reference has nothing of the kind (PlenOctrees / SNeRG / Plenoxels bake a trained NeRF
+// in this way, and store only the occupied part of their grids behind a coarse index).  What the file shares with the other
+// baked*.hip files is in baked_common.h.
 //
 // Lattice [Rx][Ry][Rz] (C order, z fastest) placed as in knerf_query_grid.  One RECORD per lattice point (include/knerf.h):
 //   bytes 0..3   fp32 sigma (after ReLU; values <= the bake's threshold are stored as 0)
@@ -7,15 +9,28 @@
 //   zero padding to a multiple of 16 bytes: 16 / 32 / 64 / 112 bytes for degree 0 / 1 / 2 / 3
 // A record is read in 16-byte CHUNKS (8 half slots each); chunk 0 starts with sigma.
 //
+// Brick storage: the lattice is cut into BRICKS of b^3 lattice points, b = 1 << brick_log2 = 4 or 8: point (x, y, z) lies in brick
+// (x >> L, y >> L, z >> L) of the brick grid B_a = ceil(R_a / b), at place ((x & (b-1)) b + (y & (b-1))) b + (z & (b-1)) in it.
+//   brick_of  int32 [Bx][By][Bz]: the slot of a stored brick, -1 for an absent one
+//   records   [n_bricks][b^3] records in the layout above
+// A point of an absent brick reads as an all-zero record.  A brick_of value outside [0, n_bricks) counts as absent: a damaged table
+// never becomes an out-of-range read.  The occupancy bits are those of the dense field.
+//
 //   baked_project_kernel   acc[n][k][c] += P[k][j] rgb[n][c]: one direction of the least-squares SH fit; one fused multiply-add, or with
 //                          a second buffer a compensated sum (the rounding errors of product and sum, both exact, are kept beside it)
 //   baked_pack_kernel      acc (+ comp) -> fp16 (round to nearest even), sigma and coefficients scattered into the records
-//   baked_render_kernel    <DEG, G>: G lanes march one ray; lane `sub` of the group owns chunks sub, sub + G, ... of every record it
+//   baked_render_kernel    <DEG, G, Args>: G lanes march one ray; lane `sub` of the group owns chunks sub, sub + G, ... of every record it
 //                          meets.  G = 1 is one ray per lane (8 corners x record bytes per lane and sample); with G = record chunks
 //                          the group reads each corner as ONE contiguous record.  Every lane of a group runs the whole march on the
 //                          same numbers (same control flow); the three channel sums are added across the group with DPP quad
 //                          permutes and sigma comes from the lane that owns chunk 0.  One ray's samples are never split across lanes:
 //                          compositing is strictly in ascending sample order, so skipping empty cells is exact (see below).
+//                          Args = RenderArgs (dense) or BrickRenderArgs: ONE march for both storages, so every sample's arithmetic
+//                          is the same and the outputs are bit-identical (tests/test_gpu_baked_bricks.py holds the two in step).
+//                          Only the record address differs (Args::kBrick): the dense address is plain arithmetic formed at its load;
+//                          the 8 brick addresses are formed through brick_of in front of the record loads, so the
+//                          loads still issue together (the march is bound by memory latency).  With b = 8 about two thirds of the
+//                          samples have all 8 corners in the brick the lane looked up last, so most samples need no table read.
 //
 // The march of one ray (include/knerf.h knerf_baked_render restates it; tests/baked_reference.py is the fp64 restatement):
 //   S = ceil((far - near) / step) in double; t_i = near + (i + 0.5) step; p = __fadd_rn(o, __fmul_rn(d, t_i)).
@@ -26,25 +41,10 @@
 //   memory latency, and a dependent bit load per sample cost more than it saved), then the samples to fetch are composited in order.
 //   An empty cell has sigma = 0 at all 8 corners: trilinear sigma = 0 exactly, alpha = 0, w = 0, T unchanged; not fetching the sample
 //   gives the same bits.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/knerf.h"
+#include "baked_common.h"
 
 namespace knerf {
 namespace baked {
-
-constexpr int kBlock = 256;
-constexpr int kBatch = 8;                           // samples whose occupancy bits are looked up together
-constexpr int kMaxSamples = 1 << 23;               // (float)i + 0.5f is exact below this
-constexpr unsigned long long kMaxBytes = 1ull << 40;
-
-__host__ __device__ constexpr int n_coeff(int deg) { return (deg + 1) * (deg + 1); }
-__host__ __device__ constexpr int rec_bytes(int deg) { return (4 + 6 * n_coeff(deg) + 15) / 16 * 16; }
-
-__device__ __forceinline__ float half_bits_to_float(unsigned h) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(h & 0xffffu)); }
-__device__ __forceinline__ unsigned float_to_half_bits(float f) { return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)f); }   // round to nearest even
 
 // ---- bake: projection onto the SH basis and packing
 __global__ void baked_project_kernel(const float* __restrict__ rgb, const float* __restrict__ fit, int K, int D, int j, long long n,
@@ -90,6 +90,7 @@ __global__ void baked_pack_kernel(const float* __restrict__ sigma, const float* 
 
 // ---- render
 struct RenderArgs {
+    static constexpr bool kBrick = false;
     const uint4* rec;
     const unsigned* bits;
     int R[3];
@@ -103,74 +104,28 @@ struct RenderArgs {
     unsigned long long* stats;
 };
 
-// the orthonormal real spherical harmonics of a unit vector, index k = l (l + 1) + m, no Condon-Shortley phase
-template <int DEG>
-__device__ __forceinline__ void sh_eval(float x, float y, float z, float (&Y)[n_coeff(DEG)]) {
-    Y[0] = 0.28209479177387814f;
-    if constexpr (DEG >= 1) {
-        Y[1] = 0.4886025119029199f * y;
-        Y[2] = 0.4886025119029199f * z;
-        Y[3] = 0.4886025119029199f * x;
-    }
-    if constexpr (DEG >= 2) {
-        const float xx = x * x, yy = y * y, zz = z * z;
-        Y[4] = 1.0925484305920792f * (x * y);
-        Y[5] = 1.0925484305920792f * (y * z);
-        Y[6] = 0.31539156525252005f * (3.f * zz - 1.f);
-        Y[7] = 1.0925484305920792f * (x * z);
-        Y[8] = 0.5462742152960396f * (xx - yy);
-        if constexpr (DEG >= 3) {
-            Y[9] = 0.5900435899266435f * (y * (3.f * xx - yy));
-            Y[10] = 2.890611442640554f * (x * y * z);
-            Y[11] = 0.4570457994644658f * (y * (5.f * zz - 1.f));
-            Y[12] = 0.3731763325901154f * (z * (5.f * zz - 3.f));
-            Y[13] = 0.4570457994644658f * (x * (5.f * zz - 1.f));
-            Y[14] = 1.445305721320277f * (z * (xx - yy));
-            Y[15] = 0.5900435899266435f * (x * (xx - 3.f * yy));
-        }
-    }
-}
+struct BrickRenderArgs {
+    static constexpr bool kBrick = true;
+    const uint4* rec;
+    const int* brick_of;
+    const unsigned* bits;
+    int R[3];
+    int L, By, Bz;                                  // log2 of the brick edge; the brick grid's y and z extents
+    long long n_bricks;
+    float lo[3], hi[3], scale[3];
+    const float *o, *d, *near, *far;
+    float near0, far0;
+    long long n;
+    float step, eps;
+    int white, skip;
+    float *image, *depth, *opacity;
+    unsigned long long* stats;
+};
 
-template <int CTRL>
-__device__ __forceinline__ float dpp(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, false));
-}
-// sum over the G lanes of a group (G = 2: lane pairs, G = 4: quads); every lane ends with the same bits
-template <int G>
-__device__ __forceinline__ float group_sum(float x) {
-    if constexpr (G >= 2) x = x + dpp<0xB1>(x);        // quad_perm [1,0,3,2]
-    if constexpr (G >= 4) x = x + dpp<0x4E>(x);        // quad_perm [2,3,0,1]
-    return x;
-}
-template <int G>
-__device__ __forceinline__ float group_first(float x) {
-    if constexpr (G == 2) return dpp<0xA0>(x);         // quad_perm [0,0,2,2]
-    if constexpr (G == 4) return dpp<0x00>(x);         // quad_perm [0,0,0,0]
-    return x;
-}
-
-// sample i of a ray: t_i, and if the sample lies inside the box (the return value) its cell and the trilinear fractions
-__device__ __forceinline__ bool locate(const RenderArgs& a, float near, const float (&o3)[3], const float (&d3)[3], int i, float& t,
-                                       int (&ci)[3], float (&fr)[3]) {
-    t = __fadd_rn(near, __fmul_rn((float)i + 0.5f, a.step));
-    bool inside = true;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float p = __fadd_rn(o3[c], __fmul_rn(d3[c], t));
-        const float u = __fmul_rn(__fsub_rn(p, a.lo[c]), a.scale[c]);
-        const int cells = a.R[c] - 1;
-        const bool in = u >= 0.f && u <= (float)cells;
-        inside = inside && in;
-        const int f = in ? (int)__builtin_floorf(u) : 0;
-        ci[c] = f < cells ? f : cells - 1;
-        fr[c] = __fsub_rn(u, (float)ci[c]);
-    }
-    return inside;
-}
-
-template <int DEG, int G>
-__global__ __launch_bounds__(kBlock) void baked_render_kernel(RenderArgs a) {
+template <int DEG, int G, class Args>
+__global__ __launch_bounds__(kBlock) void baked_render_kernel(Args a) {
     constexpr int K = n_coeff(DEG), NCH = rec_bytes(DEG) / 16, CPL = (NCH + G - 1) / G;     // chunks per record / per lane
+    constexpr bool BRICK = Args::kBrick;
     static_assert(G == 1 || G == 2 || G == 4, "a group is a lane, a pair or a quad");
     const long long gid = (long long)blockIdx.x * kBlock + threadIdx.x;
     const long long ray = gid / G;
@@ -224,8 +179,12 @@ __global__ __launch_bounds__(kBlock) void baked_render_kernel(RenderArgs a) {
             i1 = (int)fmin(fmax(a1, 0.0), (double)S);
         }
         const float delta = a.step * nrm;
-        const long long sy = a.R[2], sx = (long long)a.R[1] * a.R[2];
+        [[maybe_unused]] const long long sy = a.R[2], sx = (long long)a.R[1] * a.R[2];     // dense: the lattice's strides
         const int cyc = a.R[1] - 1, czc = a.R[2] - 1;
+        [[maybe_unused]] const int L = brick_log2(a), inm = (1 << L) - 1;
+        // BRICK: the brick this lane looked up last (linear brick index and slot): consecutive samples mostly stay in one brick.  (One
+        // entry per corner was measured too: 26 more VGPRs, a wave per SIMD fewer, 9 % slower.)
+        [[maybe_unused]] int last_key = -1, last_slot = -1;
         float T = 1.f, img0 = 0.f, img1 = 0.f, img2 = 0.f, dep = 0.f, opa = 0.f;
         bool done = false;
         for (; i < i1 && !done; i += kBatch) {
@@ -247,7 +206,30 @@ __global__ __launch_bounds__(kBlock) void baked_render_kernel(RenderArgs a) {
             float fr[3], t;
             locate(a, near, o3, d3, i + kk, t, ci, fr);
             if (sub == 0) ++fetched;
-            const long long base = (long long)ci[0] * sx + (long long)ci[1] * sy + ci[2];
+            // The dense address is plain arithmetic and is formed at its load: put in front as well it cost time (measured in the
+            // ray-gradient kernels, 3.8 against 3.0 ms).  BRICK: the 8 corner records through the brick table, in front of the loads, so
+            // that the loads still issue together: at[cn] < 0 = a point of an absent brick
+            [[maybe_unused]] const long long base = (long long)ci[0] * sx + (long long)ci[1] * sy + ci[2];
+            [[maybe_unused]] int at[8];
+            if constexpr (BRICK) {
+                int key[8], slot[8];
+#pragma unroll
+                for (int cn = 0; cn < 8; ++cn) {
+                    const int x = ci[0] + ((cn >> 2) & 1), y = ci[1] + ((cn >> 1) & 1), z = ci[2] + (cn & 1);
+                    key[cn] = ((x >> L) * a.By + (y >> L)) * a.Bz + (z >> L);
+                }
+#pragma unroll
+                for (int cn = 0; cn < 8; ++cn) slot[cn] = key[cn] == last_key ? last_slot : a.brick_of[key[cn]];
+                last_key = key[0]; last_slot = slot[0];
+                // a record's index fits 32 bits (n_bricks <= Bx By Bz, so at most 1032^3 records); its byte offset is formed in 64
+#pragma unroll
+                for (int cn = 0; cn < 8; ++cn) {
+                    const int x = ci[0] + ((cn >> 2) & 1), y = ci[1] + ((cn >> 1) & 1), z = ci[2] + (cn & 1);
+                    const int in = ((((x & inm) << L) | (y & inm)) << L) | (z & inm);
+                    const bool stored = slot[cn] >= 0 && (long long)slot[cn] < a.n_bricks;
+                    at[cn] = stored ? (int)(((unsigned)slot[cn] << (3 * L)) + (unsigned)in) : -1;
+                }
+            }
             float sig = 0.f, cf[CPL][8];
 #pragma unroll
             for (int j = 0; j < CPL; ++j)
@@ -256,12 +238,14 @@ __global__ __launch_bounds__(kBlock) void baked_render_kernel(RenderArgs a) {
 #pragma unroll
             for (int cn = 0; cn < 8; ++cn) {
                 const float w = ((cn & 4) ? fr[0] : 1.f - fr[0]) * ((cn & 2) ? fr[1] : 1.f - fr[1]) * ((cn & 1) ? fr[2] : 1.f - fr[2]);
-                const long long pt = base + ((cn & 4) ? sx : 0) + ((cn & 2) ? sy : 0) + (cn & 1);
+                long long pt;
+                if constexpr (BRICK) pt = at[cn];                   // (sign-extended: -1 stays -1)
+                else pt = base + ((cn & 4) ? sx : 0) + ((cn & 2) ? sy : 0) + (cn & 1);
                 uint4 v[CPL];
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) {
                     const int qc = sub + j * G;
-                    v[j] = qc < NCH ? a.rec[pt * NCH + qc] : make_uint4(0u, 0u, 0u, 0u);
+                    v[j] = (qc < NCH && (!BRICK || pt >= 0)) ? a.rec[pt * NCH + qc] : make_uint4(0u, 0u, 0u, 0u);
                 }
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) {
@@ -343,11 +327,36 @@ __global__ __launch_bounds__(kBlock) void baked_render_kernel(RenderArgs a) {
     }
 }
 
-template <int DEG, int G>
-hipError_t launch_render(const RenderArgs& a, hipStream_t s) {
-    const long long lanes = a.n * G, blocks = (lanes + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL((baked_render_kernel<DEG, G>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
+template <class Args>
+hipError_t launch_render(int deg, int lanes, const Args& a, hipStream_t s) {
+    return dispatch_deg_lanes(deg, lanes, [&](auto DEG, auto G) {
+        const long long blocks = (a.n * G + kBlock - 1) / kBlock;
+        hipLaunchKernelGGL((baked_render_kernel<DEG, G, Args>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+        return hipGetLastError();
+    });
+}
+
+// what both renderers check of their arguments beside the field; lanes comes back resolved.  n_rays = 0 is for the caller
+static bool check_render(int deg, const unsigned* bits, const float* origins, const float* directions, const float* near,
+                         const float* far, float near_all, float far_all, uint64_t n_rays, float step, float termination, int flags,
+                         const float* image, const float* depth, const float* opacity, const int64_t* stats, int& lanes) {
+    if (!origins || !directions) return false;
+    if (!image && !depth && !opacity && !stats) return false;
+    if (!check_rays(near, far, near_all, far_all, n_rays, step, termination, flags)) return false;
+    if ((flags & KNERF_BAKED_SKIP_EMPTY) && !bits) return false;
+    lanes = pick_lanes(deg, flags, kLaneGroups);
+    return lanes != 0;
+}
+
+// the ray arguments and outputs, the same fields in both argument structs
+template <class Args>
+static void set_rays(Args& a, const float* origins, const float* directions, const float* near, const float* far, float near_all,
+                     float far_all, uint64_t n_rays, float step, float termination, int flags, float* image, float* depth,
+                     float* opacity, int64_t* stats) {
+    a.o = origins; a.d = directions; a.near = near; a.far = far; a.near0 = near_all; a.far0 = far_all;
+    a.n = (long long)n_rays; a.step = step; a.eps = termination;
+    a.white = (flags & KNERF_BAKED_WHITE_BACKGROUND) ? 1 : 0; a.skip = (flags & KNERF_BAKED_SKIP_EMPTY) ? 1 : 0;
+    a.image = image; a.depth = depth; a.opacity = opacity; a.stats = reinterpret_cast<unsigned long long*>(stats);
 }
 
 }  // namespace baked
@@ -387,47 +396,40 @@ extern "C" int knerf_baked_pack(void* stream, const float* sigma, const float* a
 extern "C" int knerf_baked_render(void* stream, const knerf_baked_field* field, const float* origins, const float* directions,
                                   const float* near, const float* far, float near_all, float far_all, uint64_t n_rays, float step,
                                   float termination, int flags, float* image, float* depth, float* opacity, int64_t* stats) {
-    if (!field || !field->records || !origins || !directions) return KNERF_ERR_INVALID;
-    if (!image && !depth && !opacity && !stats) return KNERF_ERR_INVALID;
-    const int deg = field->sh_degree;
-    if (deg < 0 || deg > 3) return KNERF_ERR_INVALID;
-    if (flags & ~(KNERF_BAKED_WHITE_BACKGROUND | KNERF_BAKED_SKIP_EMPTY | KNERF_BAKED_LANES_MASK)) return KNERF_ERR_INVALID;
-    if ((flags & KNERF_BAKED_SKIP_EMPTY) && !field->bits) return KNERF_ERR_INVALID;
-    if (!(step > 0.f) || !std::isfinite(step) || !(termination >= 0.f) || !(termination < 1.f)) return KNERF_ERR_INVALID;
-    if ((!near && !std::isfinite(near_all)) || (!far && !std::isfinite(far_all))) return KNERF_ERR_INVALID;
+    if (!field || !field->records) return KNERF_ERR_INVALID;
     baked::RenderArgs a{};
-    unsigned long long points = 1;
-    for (int c = 0; c < 3; ++c) {
-        const int r = field->resolution[c];
-        if (r < 2 || r > 1025) return KNERF_ERR_INVALID;
-        if (!std::isfinite(field->lo[c]) || !std::isfinite(field->hi[c]) || !(field->hi[c] > field->lo[c])) return KNERF_ERR_INVALID;
-        a.R[c] = r; a.lo[c] = field->lo[c]; a.hi[c] = field->hi[c];
-        a.scale[c] = (float)((double)(r - 1) / ((double)field->hi[c] - (double)field->lo[c]));
-        if (!std::isfinite(a.scale[c])) return KNERF_ERR_INVALID;
-        points *= (unsigned)r;
-    }
-    if (points >= baked::kMaxBytes / (unsigned)baked::rec_bytes(deg)) return KNERF_ERR_INVALID;
-    int lanes = (flags & KNERF_BAKED_LANES_MASK) >> KNERF_BAKED_LANES_SHIFT;
-    if (lanes == 0) lanes = deg == 0 ? 1 : (deg == 1 ? 2 : 4);
-    if (!(lanes == 1 || (lanes == 2 && deg == 1) || (lanes == 4 && deg >= 2))) return KNERF_ERR_INVALID;
-    if (n_rays >= (1ull << 36)) return KNERF_ERR_INVALID;
+    unsigned long long points = 0;
+    int lanes = 0;
+    const int deg = field->sh_degree;
+    if (!baked::check_lattice(field->resolution, field->lo, field->hi, deg, a.scale, points)) return KNERF_ERR_INVALID;
+    if (!baked::check_render(deg, field->bits, origins, directions, near, far, near_all, far_all, n_rays, step, termination, flags, image,
+                             depth, opacity, stats, lanes))
+        return KNERF_ERR_INVALID;
     if (n_rays == 0) return KNERF_OK;
+    for (int c = 0; c < 3; ++c) { a.R[c] = field->resolution[c]; a.lo[c] = field->lo[c]; a.hi[c] = field->hi[c]; }
     a.rec = static_cast<const uint4*>(field->records); a.bits = field->bits;
-    a.o = origins; a.d = directions; a.near = near; a.far = far; a.near0 = near_all; a.far0 = far_all;
-    a.n = (long long)n_rays; a.step = step; a.eps = termination;
-    a.white = (flags & KNERF_BAKED_WHITE_BACKGROUND) ? 1 : 0; a.skip = (flags & KNERF_BAKED_SKIP_EMPTY) ? 1 : 0;
-    a.image = image; a.depth = depth; a.opacity = opacity; a.stats = reinterpret_cast<unsigned long long*>(stats);
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipErrorInvalidValue;
-    switch (deg * 8 + lanes) {
-        case 0 * 8 + 1: e = baked::launch_render<0, 1>(a, s); break;
-        case 1 * 8 + 1: e = baked::launch_render<1, 1>(a, s); break;
-        case 1 * 8 + 2: e = baked::launch_render<1, 2>(a, s); break;
-        case 2 * 8 + 1: e = baked::launch_render<2, 1>(a, s); break;
-        case 2 * 8 + 4: e = baked::launch_render<2, 4>(a, s); break;
-        case 3 * 8 + 1: e = baked::launch_render<3, 1>(a, s); break;
-        case 3 * 8 + 4: e = baked::launch_render<3, 4>(a, s); break;
-        default: return KNERF_ERR_INVALID;
-    }
-    return e == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
+    baked::set_rays(a, origins, directions, near, far, near_all, far_all, n_rays, step, termination, flags, image, depth, opacity, stats);
+    return baked::launch_render(deg, lanes, a, (hipStream_t)stream) == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
+}
+
+extern "C" int knerf_baked_render_bricks(void* stream, const knerf_baked_bricks* field, const float* origins, const float* directions,
+                                         const float* near, const float* far, float near_all, float far_all, uint64_t n_rays, float step,
+                                         float termination, int flags, float* image, float* depth, float* opacity, int64_t* stats) {
+    if (!field || !field->records || !field->brick_of) return KNERF_ERR_INVALID;
+    baked::BrickRenderArgs a{};
+    unsigned long long points = 0;
+    int lanes = 0, B[3];
+    const int deg = field->sh_degree;
+    // what knerf_baked_render refuses for the same lattice is refused here as well, although the dense table is never formed
+    if (!baked::check_lattice(field->resolution, field->lo, field->hi, deg, a.scale, points)) return KNERF_ERR_INVALID;
+    if (!baked::check_brick_grid(field->resolution, deg, field->brick_log2, field->n_bricks, B)) return KNERF_ERR_INVALID;
+    if (!baked::check_render(deg, field->bits, origins, directions, near, far, near_all, far_all, n_rays, step, termination, flags, image,
+                             depth, opacity, stats, lanes))
+        return KNERF_ERR_INVALID;
+    if (n_rays == 0) return KNERF_OK;
+    for (int c = 0; c < 3; ++c) { a.R[c] = field->resolution[c]; a.lo[c] = field->lo[c]; a.hi[c] = field->hi[c]; }
+    a.rec = static_cast<const uint4*>(field->records); a.brick_of = field->brick_of; a.bits = field->bits;
+    a.L = field->brick_log2; a.By = B[1]; a.Bz = B[2]; a.n_bricks = (long long)field->n_bricks;
+    baked::set_rays(a, origins, directions, near, far, near_all, far_all, n_rays, step, termination, flags, image, depth, opacity, stats);
+    return baked::launch_render(deg, lanes, a, (hipStream_t)stream) == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
 }

@@ -1,7 +1,8 @@
 // baked_grow.hip -- what turns the fine-tuner of baked_train.hip into a grid trainer (gfx950), context-free: a total-variation
 // regulariser over the slots of an optimiser and the resampling of a field onto another lattice (coarse to fine).  Extension: the
 // reference has nothing of the kind (Plenoxels and its kin regularise and refine their grids in this way).  include/knerf.h holds
-// the contract; tests/baked_grow_reference.py is its NumPy restatement.  baked.hip and baked_train.hip are not touched.
+// the contract; tests/baked_grow_reference.py is its NumPy restatement.  The record's sizes and codec and the lattice check are those
+// of baked_common.h.
 //
 //   baked_tv_kernel <W>       one lane per (slot, column) of the rows [n_slots][W], W = 1 + 3 K = 4 / 13 / 28 / 49.  A block of 256
 //                             lanes holds floor(256 / W) WHOLE rows (256 / 247 / 252 / 245 lanes at work), so that consecutive lanes
@@ -13,23 +14,11 @@
 //   baked_resample_kernel     one lane per (new point, 16-byte chunk), as baked_train_apply_kernel: the chunk of the 8 surrounding old
 //                             records, trilinear z, y, x with lerp(a, b, f) = a (1 - f) + b f in separate roundings (f = 0 returns a,
 //                             f = 1 returns b, exactly), the position of the new point on each axis computed in double.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/knerf.h"
+#include "baked_common.h"
 
 namespace knerf {
 namespace baked_grow {
-
-constexpr int kBlock = 256;
-constexpr unsigned long long kMaxBytes = 1ull << 40;
-
-__host__ __device__ constexpr int n_coeff(int deg) { return (deg + 1) * (deg + 1); }
-__host__ __device__ constexpr int rec_bytes(int deg) { return (4 + 6 * n_coeff(deg) + 15) / 16 * 16; }
-
-__device__ __forceinline__ float half_bits_to_float(unsigned h) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(h & 0xffffu)); }
-__device__ __forceinline__ unsigned float_to_half_bits(float f) { return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)f); }   // round to nearest even
+using namespace baked;
 
 struct TvArgs {
     const int* slot_of;
@@ -192,23 +181,6 @@ __global__ __launch_bounds__(kBlock) void baked_resample_kernel(ResampleArgs a) 
     a.dst[idx] = out;
 }
 
-// a lattice knerf_baked_render takes: degree, resolution, box, table size; its points in `points`
-static bool check_lattice(int deg, const int32_t* res, unsigned long long& points) {
-    if (deg < 0 || deg > 3) return false;
-    points = 1;
-    for (int c = 0; c < 3; ++c) {
-        if (res[c] < 2 || res[c] > 1025) return false;
-        points *= (unsigned)res[c];
-    }
-    return points < kMaxBytes / (unsigned)rec_bytes(deg);
-}
-
-static bool check_box(const knerf_baked_field* f) {
-    for (int c = 0; c < 3; ++c)
-        if (!std::isfinite(f->lo[c]) || !std::isfinite(f->hi[c]) || !(f->hi[c] > f->lo[c])) return false;
-    return true;
-}
-
 }  // namespace baked_grow
 }  // namespace knerf
 
@@ -220,7 +192,7 @@ extern "C" int knerf_baked_train_tv(void* stream, const knerf_baked_train* train
     if (!train || !train->field.records || !train->field.bits || !train->slot_of || !train->grad || !point_of || !master)
         return KNERF_ERR_INVALID;
     unsigned long long points = 0;
-    if (!baked_grow::check_lattice(train->field.sh_degree, train->field.resolution, points) || !baked_grow::check_box(&train->field))
+    if (!baked::check_lattice(train->field.resolution, train->field.lo, train->field.hi, train->field.sh_degree, nullptr, points))
         return KNERF_ERR_INVALID;
     if (train->n_slots < 1 || train->n_slots > points) return KNERF_ERR_INVALID;
     if (!(epsilon > 0.f) || !std::isfinite(epsilon)) return KNERF_ERR_INVALID;
@@ -247,19 +219,19 @@ extern "C" int knerf_baked_resample(void* stream, const knerf_baked_field* src, 
     if (!src || !src->records || !dst_resolution || !dst_records) return KNERF_ERR_INVALID;
     unsigned long long points = 0, points_new = 0;
     const int deg = src->sh_degree;
-    if (!baked_grow::check_lattice(deg, src->resolution, points) || !baked_grow::check_box(src)) return KNERF_ERR_INVALID;
-    if (!baked_grow::check_lattice(deg, dst_resolution, points_new)) return KNERF_ERR_INVALID;
+    if (!baked::check_lattice(src->resolution, src->lo, src->hi, deg, nullptr, points)) return KNERF_ERR_INVALID;
+    if (!baked::check_lattice(dst_resolution, src->lo, src->hi, deg, nullptr, points_new)) return KNERF_ERR_INVALID;     // (the same box)
     if (!(sigma_threshold >= 0.f) || !std::isfinite(sigma_threshold)) return KNERF_ERR_INVALID;
-    const unsigned long long rb = (unsigned)baked_grow::rec_bytes(deg);
+    const unsigned long long rb = (unsigned)baked::rec_bytes(deg);
     const uintptr_t s0 = (uintptr_t)src->records, d0 = (uintptr_t)dst_records;
     if (s0 < d0 + points_new * rb && d0 < s0 + points * rb) return KNERF_ERR_INVALID;      // the tables overlap
     baked_grow::ResampleArgs a{};
     a.src = static_cast<const uint4*>(src->records); a.dst = static_cast<uint4*>(dst_records);
     for (int c = 0; c < 3; ++c) { a.R[c] = src->resolution[c]; a.Rn[c] = dst_resolution[c]; }
-    a.K = baked_grow::n_coeff(deg); a.nch = (int)(rb / 16);
+    a.K = baked::n_coeff(deg); a.nch = (int)(rb / 16);
     a.n_new = (long long)points_new; a.threshold = sigma_threshold;
-    const unsigned long long blocks = (points_new * (unsigned)a.nch + baked_grow::kBlock - 1) / baked_grow::kBlock;
+    const unsigned long long blocks = (points_new * (unsigned)a.nch + baked::kBlock - 1) / baked::kBlock;
     if (blocks >= (1ull << 31)) return KNERF_ERR_INVALID;
-    hipLaunchKernelGGL(baked_grow::baked_resample_kernel, dim3((unsigned)blocks), dim3(baked_grow::kBlock), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(baked_grow::baked_resample_kernel, dim3((unsigned)blocks), dim3(baked::kBlock), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
 }

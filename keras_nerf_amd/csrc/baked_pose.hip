@@ -2,8 +2,7 @@
 // baked_train.hip with respect to every ray's origin and direction, for dense and for brick fields, and the reduction of those per-ray
 // gradients to one rigid-motion gradient per camera.  Extension: the reference has nothing of the kind (BARF, NeRF-- and every current
 // toolkit refine their cameras with the field in this way).  include/knerf.h holds the contract; tests/baked_pose_reference.py is its
-// fp64 restatement; DESIGN.md 2.24 has the derivation.  No other kernel file is touched: the helpers of the march are restated here
-// (same constants, same operations, same order), as baked_train.hip restates baked.hip.
+// fp64 restatement; DESIGN.md 2.24 has the derivation.  What the file shares with the other baked*.hip files is in baked_common.h.
 //
 //   baked_ray_gradients_kernel  <DEG, G, BRICK>, the lane variants of baked_train_rays_kernel: G lanes march one ray, lane `sub` owns chunks
 //                             sub, sub + G, ... of every record.  The two marches are those of baked_train.hip sample for sample: the
@@ -21,31 +20,18 @@
 //                                 grad_direction = scale * sum_j t_j G_j + (sum_j dsig_j sigma_j) (step / delta) u
 //                                                  + (1 / |d|) (I - u u^T) sum_kc q[k][c] grad Y_k(u)
 //                             once: no atomics, no scratch buffer.  A ray that misses, has |d| = 0 or an all-zero g stores zeros.
-//                             BRICK: a corner's record address goes through brick_of as in baked_bricks_train.hip (an entry < 0 or >= n_bricks
+//                             BRICK: a corner's record address goes through brick_of as in baked_train.hip (an entry < 0 or >= n_bricks
 //                             counts as absent before any address is formed and reads as a zero record); nothing else differs, so a brick
 //                             field gives the bits of its dense field.
 //   pose_gradients_kernel     one block per view: the lanes stride over ALL rays in a fixed order, add those of their view in double
 //                             (tau: grad_origin; omega: d x grad_direction) and the block adds its 256 partial sums in a fixed tree.
 //                             No atomics: two launches on the same inputs give the same bits.  A view index outside [0, V) matches no
 //                             block and is never written through.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/knerf.h"
+#include "baked_common.h"
 
 namespace knerf {
 namespace baked_pose {
-
-constexpr int kBlock = 256;
-constexpr int kBatch = 8;                           // as baked.hip: samples whose support bits are looked up together
-constexpr int kMaxSamples = 1 << 23;
-constexpr unsigned long long kMaxBytes = 1ull << 40;
-
-__host__ __device__ constexpr int n_coeff(int deg) { return (deg + 1) * (deg + 1); }
-__host__ __device__ constexpr int rec_bytes(int deg) { return (4 + 6 * n_coeff(deg) + 15) / 16 * 16; }
-
-__device__ __forceinline__ float half_bits_to_float(unsigned h) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(h & 0xffffu)); }
+using namespace baked;
 
 struct PoseArgs {
     const uint4* rec;
@@ -63,35 +49,7 @@ struct PoseArgs {
     float *grad_o, *grad_d, *sq_err;
 };
 
-// the basis of baked.hip sh_eval
-template <int DEG>
-__device__ __forceinline__ void sh_eval(float x, float y, float z, float (&Y)[n_coeff(DEG)]) {
-    Y[0] = 0.28209479177387814f;
-    if constexpr (DEG >= 1) {
-        Y[1] = 0.4886025119029199f * y;
-        Y[2] = 0.4886025119029199f * z;
-        Y[3] = 0.4886025119029199f * x;
-    }
-    if constexpr (DEG >= 2) {
-        const float xx = x * x, yy = y * y, zz = z * z;
-        Y[4] = 1.0925484305920792f * (x * y);
-        Y[5] = 1.0925484305920792f * (y * z);
-        Y[6] = 0.31539156525252005f * (3.f * zz - 1.f);
-        Y[7] = 1.0925484305920792f * (x * z);
-        Y[8] = 0.5462742152960396f * (xx - yy);
-        if constexpr (DEG >= 3) {
-            Y[9] = 0.5900435899266435f * (y * (3.f * xx - yy));
-            Y[10] = 2.890611442640554f * (x * y * z);
-            Y[11] = 0.4570457994644658f * (y * (5.f * zz - 1.f));
-            Y[12] = 0.3731763325901154f * (z * (5.f * zz - 3.f));
-            Y[13] = 0.4570457994644658f * (x * (5.f * zz - 1.f));
-            Y[14] = 1.445305721320277f * (z * (xx - yy));
-            Y[15] = 0.5900435899266435f * (x * (xx - 3.f * yy));
-        }
-    }
-}
-
-// the gradient of those polynomials as they are written (their extension off the sphere; the caller projects it away): D[k] = (d/dx, d/dy, d/dz)
+// the gradient of the polynomials of sh_eval as they are written (their extension off the sphere; the caller projects it away): D[k] = (d/dx, d/dy, d/dz)
 template <int DEG>
 __device__ __forceinline__ void sh_grad(float x, float y, float z, float (&D)[n_coeff(DEG)][3]) {
 #pragma unroll
@@ -123,41 +81,6 @@ __device__ __forceinline__ void sh_grad(float x, float y, float z, float (&D)[n_
     }
 }
 
-template <int CTRL>
-__device__ __forceinline__ float dpp(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, false));
-}
-template <int G>
-__device__ __forceinline__ float group_sum(float x) {
-    if constexpr (G >= 2) x = x + dpp<0xB1>(x);        // quad_perm [1,0,3,2]
-    if constexpr (G >= 4) x = x + dpp<0x4E>(x);        // quad_perm [2,3,0,1]
-    return x;
-}
-template <int G>
-__device__ __forceinline__ float group_first(float x) {
-    if constexpr (G == 2) return dpp<0xA0>(x);         // quad_perm [0,0,2,2]
-    if constexpr (G == 4) return dpp<0x00>(x);         // quad_perm [0,0,0,0]
-    return x;
-}
-
-__device__ __forceinline__ bool locate(const PoseArgs& a, float near, const float (&o3)[3], const float (&d3)[3], int i, float& t,
-                                       int (&ci)[3], float (&fr)[3]) {
-    t = __fadd_rn(near, __fmul_rn((float)i + 0.5f, a.step));
-    bool inside = true;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float p = __fadd_rn(o3[c], __fmul_rn(d3[c], t));
-        const float u = __fmul_rn(__fsub_rn(p, a.lo[c]), a.scale[c]);
-        const int cells = a.R[c] - 1;
-        const bool in = u >= 0.f && u <= (float)cells;
-        inside = inside && in;
-        const int f = in ? (int)__builtin_floorf(u) : 0;
-        ci[c] = f < cells ? f : cells - 1;
-        fr[c] = __fsub_rn(u, (float)ci[c]);
-    }
-    return inside;
-}
-
 // what the second march needs from the first: g = dL/dout (already gated by the output clamp) and the totals
 struct Totals {
     float g[3], img[3], opa, bg;
@@ -186,7 +109,7 @@ __device__ __forceinline__ void march(const PoseArgs& a, const float (&o3)[3], c
     [[maybe_unused]] const long long sy = a.R[2], sx = (long long)a.R[1] * a.R[2];
     const int cyc = a.R[1] - 1, czc = a.R[2] - 1;
     [[maybe_unused]] const int L = a.L, inm = (1 << L) - 1;
-    [[maybe_unused]] int last_key = -1, last_slot = -1;     // BRICK: the brick this lane looked up last, as baked_bricks.hip
+    [[maybe_unused]] int last_key = -1, last_slot = -1;     // BRICK: the brick this lane looked up last, as baked.hip
     float T = 1.f;
     img[0] = img[1] = img[2] = 0.f;
     opa = 0.f;
@@ -209,7 +132,7 @@ __device__ __forceinline__ void march(const PoseArgs& a, const float (&o3)[3], c
             float fr[3], t;
             locate(a, near, o3, d3, i + kk, t, ci, fr);
             // a corner's record index, or -1 for a point of an absent brick (BRICK only: through the table, with the lane's one-entry
-            // cache of the brick it looked up last, as baked_bricks.hip).  A record's index fits 32 bits (n_bricks <= Bx By Bz, so
+            // cache of the brick it looked up last, as baked.hip).  A record's index fits 32 bits (n_bricks <= Bx By Bz, so
             // at most 1032^3 records); byte offsets are formed in 64
             [[maybe_unused]] const long long base = (long long)ci[0] * sx + (long long)ci[1] * sy + ci[2];
             auto record_of = [&](int cn) -> long long {
@@ -236,7 +159,7 @@ __device__ __forceinline__ void march(const PoseArgs& a, const float (&o3)[3], c
             // sums, and the kernel leaves the register file (degree 3: 584 bytes of scratch per lane).  The arithmetic is the same.
             constexpr int kCornerUnroll = (BWD && G == 1 && DEG >= 2) ? 1 : 8;
             // BRICK, unrolled: the 8 addresses in front of the loads, so that the loads issue together; the table is then read against
-            // the brick of the sample BEFORE, as baked_bricks.hip does, and the 8 lookups do not wait for each other (measured on an
+            // the brick of the sample BEFORE, as baked.hip does, and the 8 lookups do not wait for each other (measured on an
             // MI355X at 256^3, degree 2: 3.7 against 5.5 ms a launch).  The dense address is plain arithmetic and is formed at its
             // load: put in front as well it cost time (3.8 against 3.0 ms)
             constexpr bool kInFront = BRICK && kCornerUnroll == 8;
@@ -501,57 +424,32 @@ __global__ __launch_bounds__(kBlock) void baked_ray_gradients_kernel(PoseArgs a)
     }
 }
 
-template <int DEG, int G, bool BRICK>
-hipError_t launch_rays(const PoseArgs& a, hipStream_t s) {
-    const long long lanes = a.n * G, blocks = (lanes + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL((baked_ray_gradients_kernel<DEG, G, BRICK>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-}
-
 template <bool BRICK>
-hipError_t dispatch(int deg, int lanes, const PoseArgs& a, hipStream_t s) {
-    switch (deg * 8 + lanes) {
-        case 0 * 8 + 1: return launch_rays<0, 1, BRICK>(a, s);
-        case 1 * 8 + 1: return launch_rays<1, 1, BRICK>(a, s);
-        case 1 * 8 + 2: return launch_rays<1, 2, BRICK>(a, s);
-        case 2 * 8 + 1: return launch_rays<2, 1, BRICK>(a, s);
-        case 2 * 8 + 4: return launch_rays<2, 4, BRICK>(a, s);
-        case 3 * 8 + 1: return launch_rays<3, 1, BRICK>(a, s);
-        case 3 * 8 + 4: return launch_rays<3, 4, BRICK>(a, s);
-        default: return hipErrorInvalidValue;
-    }
+hipError_t launch_rays(int deg, int lanes, const PoseArgs& a, hipStream_t s) {
+    return dispatch_deg_lanes(deg, lanes, [&](auto DEG, auto G) {
+        const long long blocks = (a.n * G + kBlock - 1) / kBlock;
+        hipLaunchKernelGGL((baked_ray_gradients_kernel<DEG, G, BRICK>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 // the lattice of either field struct: what knerf_baked_render refuses of it, and the scale of locate
-static bool check_lattice(const void* records, const unsigned* bits, const int32_t (&res)[3], int deg, const float (&lo)[3],
-                          const float (&hi)[3], PoseArgs& a, unsigned long long& points) {
-    if (!records || !bits) return false;
-    if (deg < 0 || deg > 3) return false;
-    points = 1;
-    for (int c = 0; c < 3; ++c) {
-        const int r = res[c];
-        if (r < 2 || r > 1025) return false;
-        if (!std::isfinite(lo[c]) || !std::isfinite(hi[c]) || !(hi[c] > lo[c])) return false;
-        points *= (unsigned)r;
-        a.R[c] = r; a.lo[c] = lo[c]; a.hi[c] = hi[c];
-        a.scale[c] = (float)((double)(r - 1) / ((double)hi[c] - (double)lo[c]));
-        if (!std::isfinite(a.scale[c])) return false;
-    }
-    return points < kMaxBytes / (unsigned)rec_bytes(deg);
+static bool check_field(const void* records, const unsigned* bits, const int32_t (&res)[3], int deg, const float (&lo)[3],
+                        const float (&hi)[3], PoseArgs& a) {
+    unsigned long long points = 0;
+    if (!records || !bits || !check_lattice(res, lo, hi, deg, a.scale, points)) return false;
+    for (int c = 0; c < 3; ++c) { a.R[c] = res[c]; a.lo[c] = lo[c]; a.hi[c] = hi[c]; }
+    return true;
 }
 
 // the ray arguments of knerf_baked_train_rays, checked as there; lanes comes back resolved.  n_rays = 0 is for the caller
-static bool check_rays(int deg, const float* origins, const float* directions, const float* near, const float* far, float near_all,
-                       float far_all, const float* target, uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags,
-                       float* grad_origin, float* grad_direction, float* sq_err, PoseArgs& a, int& lanes) {
+static bool check_pose_rays(int deg, const float* origins, const float* directions, const float* near, const float* far, float near_all,
+                            float far_all, const float* target, uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags,
+                            float* grad_origin, float* grad_direction, float* sq_err, PoseArgs& a, int& lanes) {
     if (!origins || !directions || !target || !grad_origin || !grad_direction) return false;
-    if (flags & ~(KNERF_BAKED_WHITE_BACKGROUND | KNERF_BAKED_SKIP_EMPTY | KNERF_BAKED_LANES_MASK)) return false;
-    if (!(step > 0.f) || !std::isfinite(step) || !(termination >= 0.f) || !(termination < 1.f)) return false;
-    if ((!near && !std::isfinite(near_all)) || (!far && !std::isfinite(far_all))) return false;
-    lanes = (flags & KNERF_BAKED_LANES_MASK) >> KNERF_BAKED_LANES_SHIFT;
-    if (lanes == 0) lanes = deg == 0 ? 1 : (deg == 1 ? 2 : 4);
-    if (!(lanes == 1 || (lanes == 2 && deg == 1) || (lanes == 4 && deg >= 2))) return false;
-    if (n_rays >= (1ull << 36) || n_norm >= (1ull << 36)) return false;
+    if (!check_rays(near, far, near_all, far_all, n_rays, step, termination, flags) || n_norm >= (1ull << 36)) return false;
+    lanes = pick_lanes(deg, flags, kLaneGroups);
+    if (!lanes) return false;
     a.o = origins; a.d = directions; a.near = near; a.far = far; a.near0 = near_all; a.far0 = far_all; a.target = target;
     a.n = (long long)n_rays; a.step = step; a.eps = termination;
     a.gscale = (float)(2.0 / (3.0 * (double)(n_norm ? n_norm : (n_rays ? n_rays : 1))));
@@ -600,16 +498,15 @@ extern "C" int knerf_baked_ray_gradients(void* stream, const knerf_baked_field* 
                                          uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags, float* grad_origin,
                                          float* grad_direction, float* sq_err) {
     baked_pose::PoseArgs a{};
-    unsigned long long points = 0;
     int lanes = 0;
-    if (!field || !baked_pose::check_lattice(field->records, field->bits, field->resolution, field->sh_degree, field->lo, field->hi, a, points))
+    if (!field || !baked_pose::check_field(field->records, field->bits, field->resolution, field->sh_degree, field->lo, field->hi, a))
         return KNERF_ERR_INVALID;
-    if (!baked_pose::check_rays(field->sh_degree, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step,
-                                termination, flags, grad_origin, grad_direction, sq_err, a, lanes))
+    if (!baked_pose::check_pose_rays(field->sh_degree, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step,
+                                     termination, flags, grad_origin, grad_direction, sq_err, a, lanes))
         return KNERF_ERR_INVALID;
     if (n_rays == 0) return KNERF_OK;
     a.rec = static_cast<const uint4*>(field->records); a.bits = field->bits;
-    const hipError_t e = baked_pose::dispatch<false>(field->sh_degree, lanes, a, (hipStream_t)stream);
+    const hipError_t e = baked_pose::launch_rays<false>(field->sh_degree, lanes, a, (hipStream_t)stream);
     return e == hipSuccess ? KNERF_OK : (e == hipErrorInvalidValue ? KNERF_ERR_INVALID : KNERF_ERR_HIP);
 }
 
@@ -618,28 +515,19 @@ extern "C" int knerf_baked_ray_gradients_bricks(void* stream, const knerf_baked_
                                                 const float* target, uint64_t n_rays, uint64_t n_norm, float step, float termination,
                                                 int flags, float* grad_origin, float* grad_direction, float* sq_err) {
     baked_pose::PoseArgs a{};
-    unsigned long long points = 0;
-    int lanes = 0;
+    int lanes = 0, B[3];
     if (!field || !field->brick_of ||
-        !baked_pose::check_lattice(field->records, field->bits, field->resolution, field->sh_degree, field->lo, field->hi, a, points))
+        !baked_pose::check_field(field->records, field->bits, field->resolution, field->sh_degree, field->lo, field->hi, a))
         return KNERF_ERR_INVALID;
-    const int L = field->brick_log2, deg = field->sh_degree;
-    if (L != 2 && L != 3) return KNERF_ERR_INVALID;
-    unsigned long long grid = 1;
-    int B[3];
-    for (int c = 0; c < 3; ++c) {
-        B[c] = (field->resolution[c] + (1 << L) - 1) >> L;
-        grid *= (unsigned)B[c];
-    }
-    if (field->n_bricks == 0 || field->n_bricks > grid) return KNERF_ERR_INVALID;
-    if ((field->n_bricks << (3 * L)) >= baked_pose::kMaxBytes / (unsigned)baked_pose::rec_bytes(deg)) return KNERF_ERR_INVALID;
-    if (!baked_pose::check_rays(deg, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination, flags,
-                                grad_origin, grad_direction, sq_err, a, lanes))
+    const int deg = field->sh_degree;
+    if (!baked::check_brick_grid(field->resolution, deg, field->brick_log2, field->n_bricks, B)) return KNERF_ERR_INVALID;
+    if (!baked_pose::check_pose_rays(deg, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination,
+                                     flags, grad_origin, grad_direction, sq_err, a, lanes))
         return KNERF_ERR_INVALID;
     if (n_rays == 0) return KNERF_OK;
     a.rec = static_cast<const uint4*>(field->records); a.brick_of = field->brick_of; a.bits = field->bits;
-    a.L = L; a.By = B[1]; a.Bz = B[2]; a.n_bricks = (long long)field->n_bricks;
-    const hipError_t e = baked_pose::dispatch<true>(deg, lanes, a, (hipStream_t)stream);
+    a.L = field->brick_log2; a.By = B[1]; a.Bz = B[2]; a.n_bricks = (long long)field->n_bricks;
+    const hipError_t e = baked_pose::launch_rays<true>(deg, lanes, a, (hipStream_t)stream);
     return e == hipSuccess ? KNERF_OK : (e == hipErrorInvalidValue ? KNERF_ERR_INVALID : KNERF_ERR_HIP);
 }
 

@@ -1,7 +1,7 @@
 // baked_quant.hip -- the brick baked field with 8-bit SH coefficients: its codec and its renderer (gfx950), context-free.
 // Extension: the reference has nothing of the kind (PlenOctrees and SNeRG ship their SH coefficients as 8-bit values with a scale).
-// include/knerf.h holds the format (knerf_baked_qbricks); tests/baked_quant_reference.py restates it in NumPy.  No other .hip file is
-// touched: what the march needs of baked_bricks.hip (sh_eval, the DPP sums, locate) is restated here.
+// include/knerf.h holds the format (knerf_baked_qbricks); tests/baked_quant_reference.py restates it in NumPy.  What the file shares
+// with the other baked*.hip files (sh_eval, the DPP sums, locate, the argument checks) is in baked_common.h.
 //
 // A quantised record is fp32 sigma + 3 K int8 [k][c], padded with zeros to 8 / 16 / 32 / 64 bytes (degree 0 / 1 / 2 / 3); coefficient
 // e = 3 k + c is byte 4 + e.  One exponent per stored brick and SH band l = floor(sqrt(k)), byte l of the brick's exponent word:
@@ -13,41 +13,31 @@
 //                          atomics, no host read.  Every lane then forms the exponents, lane 0 writes the word, and the records are
 //                          read again (from L2) and written quantised.
 //   baked_dequantize_bricks_kernel <DEG>: one lane per record: sigma's bits, the coefficients as q 2^e in fp16 (exact), zero padding.
-//   baked_render_qbricks_kernel    <DEG, G>: the march of baked_render_bricks_kernel (baked_bricks.hip) restated word for word -- sample
+//   baked_render_qbricks_kernel    <DEG, G>: the march of baked_render_kernel (baked.hip) on brick storage, word for word -- sample
 //                          positions, locate, corner order, the table lookup with its range guard and one-entry cache, batches of kBatch
 //                          occupancy words, termination, stats, clamps, the fused multiply-adds -- with another fetch: the record is
 //                          8 .. 64 bytes, the exponent word of a corner's brick is loaded by slot beside the record (and cached with the
 //                          slot), and every corner's coefficients are decoded to fp32 BEFORE they enter fma(w, coeff, acc): the 8 corners
 //                          may lie in 8 bricks with 8 different exponents.  G = 1 accumulates in ascending e = 3 k + c exactly as
-//                          baked_render_bricks_kernel<DEG, 1> does, so it gives the bits of that kernel on the dequantised field
+//                          baked_render_kernel<DEG, 1, BrickRenderArgs> does, so it gives the bits of that kernel on the dequantised field
 //                          (tests/test_gpu_baked_quant.py holds the two in step).  G = 2 (degree 2) / 4 (degree 3): every lane of a
 //                          group takes one 16-byte chunk of the record and folds the power of two into the corner's weight (w 2^e is
 //                          exact, so fma(q, w 2^e, acc) rounds the same exact product once); the channel sums go through the DPP
 //                          pattern.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/knerf.h"
+#include "baked_common.h"
 
 namespace knerf {
 namespace quant {
+using namespace baked;
 
-constexpr int kBlock = 256;
-constexpr int kBatch = 8;                           // samples whose occupancy bits are looked up together
-constexpr int kMaxSamples = 1 << 23;               // (float)i + 0.5f is exact below this
-constexpr unsigned long long kMaxBytes = 1ull << 40;
 constexpr int kExpMin = -24, kExpMax = 9;           // 2^-24: the fp16 subnormal spacing; 127 x 2^9 = 65024 <= 65504
 
-__host__ __device__ constexpr int n_coeff(int deg) { return (deg + 1) * (deg + 1); }
-__host__ __device__ constexpr int rec_bytes(int deg) { return (4 + 6 * n_coeff(deg) + 15) / 16 * 16; }
 __host__ __device__ constexpr int qrec_bytes(int deg) { return deg == 0 ? 8 : (deg == 1 ? 16 : (deg == 2 ? 32 : 64)); }
 // the SH band of coefficient slot e = 3 k + c: floor(sqrt(k))
 __host__ __device__ constexpr int band_of(int e) { return (e >= 3) + (e >= 12) + (e >= 27); }
 static_assert(qrec_bytes(0) >= 4 + 3 * n_coeff(0) && qrec_bytes(1) >= 4 + 3 * n_coeff(1) && qrec_bytes(2) >= 4 + 3 * n_coeff(2) &&
               qrec_bytes(3) >= 4 + 3 * n_coeff(3), "a quantised record holds sigma and 3 K bytes");
 
-__device__ __forceinline__ float half_bits_to_float(unsigned h) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(h & 0xffffu)); }
 __device__ __forceinline__ float pow2(int e) { return __int_as_float((e + 127) << 23); }            // -126 <= e <= 127
 // 2^e of the exponent byte at bit `shift` of a brick's exponent word; a byte outside [-24, 9] (a damaged table) is clamped into it, so
 // that every decoded value stays finite
@@ -192,71 +182,6 @@ struct RenderArgs {
     float *image, *depth, *opacity;
     unsigned long long* stats;
 };
-
-// the orthonormal real spherical harmonics of a unit vector, index k = l (l + 1) + m, no Condon-Shortley phase
-template <int DEG>
-__device__ __forceinline__ void sh_eval(float x, float y, float z, float (&Y)[n_coeff(DEG)]) {
-    Y[0] = 0.28209479177387814f;
-    if constexpr (DEG >= 1) {
-        Y[1] = 0.4886025119029199f * y;
-        Y[2] = 0.4886025119029199f * z;
-        Y[3] = 0.4886025119029199f * x;
-    }
-    if constexpr (DEG >= 2) {
-        const float xx = x * x, yy = y * y, zz = z * z;
-        Y[4] = 1.0925484305920792f * (x * y);
-        Y[5] = 1.0925484305920792f * (y * z);
-        Y[6] = 0.31539156525252005f * (3.f * zz - 1.f);
-        Y[7] = 1.0925484305920792f * (x * z);
-        Y[8] = 0.5462742152960396f * (xx - yy);
-        if constexpr (DEG >= 3) {
-            Y[9] = 0.5900435899266435f * (y * (3.f * xx - yy));
-            Y[10] = 2.890611442640554f * (x * y * z);
-            Y[11] = 0.4570457994644658f * (y * (5.f * zz - 1.f));
-            Y[12] = 0.3731763325901154f * (z * (5.f * zz - 3.f));
-            Y[13] = 0.4570457994644658f * (x * (5.f * zz - 1.f));
-            Y[14] = 1.445305721320277f * (z * (xx - yy));
-            Y[15] = 0.5900435899266435f * (x * (xx - 3.f * yy));
-        }
-    }
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, false));
-}
-// sum over the G lanes of a group (G = 2: lane pairs, G = 4: quads); every lane ends with the same bits
-template <int G>
-__device__ __forceinline__ float group_sum(float x) {
-    if constexpr (G >= 2) x = x + dpp<0xB1>(x);        // quad_perm [1,0,3,2]
-    if constexpr (G >= 4) x = x + dpp<0x4E>(x);        // quad_perm [2,3,0,1]
-    return x;
-}
-template <int G>
-__device__ __forceinline__ float group_first(float x) {
-    if constexpr (G == 2) return dpp<0xA0>(x);         // quad_perm [0,0,2,2]
-    if constexpr (G == 4) return dpp<0x00>(x);         // quad_perm [0,0,0,0]
-    return x;
-}
-
-// sample i of a ray: t_i, and if the sample lies inside the box (the return value) its cell and the trilinear fractions
-__device__ __forceinline__ bool locate(const RenderArgs& a, float near, const float (&o3)[3], const float (&d3)[3], int i, float& t,
-                                       int (&ci)[3], float (&fr)[3]) {
-    t = __fadd_rn(near, __fmul_rn((float)i + 0.5f, a.step));
-    bool inside = true;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float p = __fadd_rn(o3[c], __fmul_rn(d3[c], t));
-        const float u = __fmul_rn(__fsub_rn(p, a.lo[c]), a.scale[c]);
-        const int cells = a.R[c] - 1;
-        const bool in = u >= 0.f && u <= (float)cells;
-        inside = inside && in;
-        const int f = in ? (int)__builtin_floorf(u) : 0;
-        ci[c] = f < cells ? f : cells - 1;
-        fr[c] = __fsub_rn(u, (float)ci[c]);
-    }
-    return inside;
-}
 
 // A lane of a group holds bytes 16 sub .. 16 sub + 15 of the record, coefficient slots e = 16 sub - 4 + s.  Its 16 bytes fall into three
 // runs, [0, 7), [7, 15) and [15, 16), inside each of which every coefficient slot of every lane has ONE band (lane 0: bands 0, 1, 1;
@@ -495,30 +420,17 @@ hipError_t launch_render(const RenderArgs& a, hipStream_t s) {
 // scale: cells / (hi - lo) per axis
 static bool check_bricks(const knerf_baked_bricks* f, int (&B)[3], float (&scale)[3]) {
     if (!f || !f->records) return false;
-    const int deg = f->sh_degree, L = f->brick_log2;
-    if (deg < 0 || deg > 3 || (L != 2 && L != 3)) return false;
-    unsigned long long points = 1, grid = 1;
-    for (int c = 0; c < 3; ++c) {
-        const int r = f->resolution[c];
-        if (r < 2 || r > 1025) return false;
-        if (!std::isfinite(f->lo[c]) || !std::isfinite(f->hi[c]) || !(f->hi[c] > f->lo[c])) return false;
-        scale[c] = (float)((double)(r - 1) / ((double)f->hi[c] - (double)f->lo[c]));
-        if (!std::isfinite(scale[c])) return false;
-        points *= (unsigned)r;
-        B[c] = (r + (1 << L) - 1) >> L;
-        grid *= (unsigned)B[c];
-    }
     // the unquantised record is the larger of the two: its bound covers both tables
     static_assert(rec_bytes(0) >= qrec_bytes(0) && rec_bytes(1) >= qrec_bytes(1) && rec_bytes(2) >= qrec_bytes(2) &&
                   rec_bytes(3) >= qrec_bytes(3), "the quantised record is the smaller one");
-    if (points >= kMaxBytes / (unsigned)rec_bytes(deg)) return false;
-    if (f->n_bricks == 0 || f->n_bricks > grid) return false;
-    if ((f->n_bricks << (3 * L)) >= kMaxBytes / (unsigned)rec_bytes(deg)) return false;
-    return true;
+    unsigned long long points = 0;
+    return check_lattice(f->resolution, f->lo, f->hi, f->sh_degree, scale, points) &&
+           check_brick_grid(f->resolution, f->sh_degree, f->brick_log2, f->n_bricks, B);
 }
 
-// lanes per ray when the flags leave the choice to the library: the fastest variant measured
-static int default_lanes(int deg) { return deg == 2 ? 2 : (deg == 3 ? 4 : 1); }
+// the group variant of each degree, which is also the one the library picks when the flags leave the choice to it: the fastest variant
+// measured
+constexpr int kQuantLaneGroups[4] = {1, 1, 2, 4};
 
 static bool overlap(const void* p, unsigned long long np, const void* q, unsigned long long nq) {
     const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
@@ -536,7 +448,7 @@ extern "C" int knerf_baked_quantize_bricks(void* stream, const knerf_baked_brick
     if (!quant::check_bricks(src, B, scale) || !dst_records || !dst_exponents) return KNERF_ERR_INVALID;
     const int deg = src->sh_degree, L = src->brick_log2;
     const unsigned long long n_records = (unsigned long long)src->n_bricks << (3 * L);
-    const unsigned long long src_bytes = n_records * (unsigned)quant::rec_bytes(deg), dst_bytes = n_records * (unsigned)quant::qrec_bytes(deg);
+    const unsigned long long src_bytes = n_records * (unsigned)baked::rec_bytes(deg), dst_bytes = n_records * (unsigned)quant::qrec_bytes(deg);
     if (quant::overlap(src->records, src_bytes, dst_records, dst_bytes)) return KNERF_ERR_INVALID;
     if (quant::overlap(src->records, src_bytes, dst_exponents, 4ull * src->n_bricks) ||
         quant::overlap(dst_records, dst_bytes, dst_exponents, 4ull * src->n_bricks)) return KNERF_ERR_INVALID;
@@ -560,7 +472,7 @@ extern "C" int knerf_baked_dequantize_bricks(void* stream, const knerf_baked_qbr
     if (!src || !src->exponents || !quant::check_bricks(&src->bricks, B, scale) || !dst_records) return KNERF_ERR_INVALID;
     const int deg = src->bricks.sh_degree, L = src->bricks.brick_log2;
     const unsigned long long n_records = (unsigned long long)src->bricks.n_bricks << (3 * L);
-    const unsigned long long src_bytes = n_records * (unsigned)quant::qrec_bytes(deg), dst_bytes = n_records * (unsigned)quant::rec_bytes(deg);
+    const unsigned long long src_bytes = n_records * (unsigned)quant::qrec_bytes(deg), dst_bytes = n_records * (unsigned)baked::rec_bytes(deg);
     if (quant::overlap(src->bricks.records, src_bytes, dst_records, dst_bytes)) return KNERF_ERR_INVALID;
     if (quant::overlap(src->exponents, 4ull * src->bricks.n_bricks, dst_records, dst_bytes)) return KNERF_ERR_INVALID;
     const unsigned* s = static_cast<const unsigned*>(src->bricks.records);
@@ -587,14 +499,10 @@ extern "C" int knerf_baked_render_qbricks(void* stream, const knerf_baked_qbrick
     if (!quant::check_bricks(field, B, a.scale)) return KNERF_ERR_INVALID;
     if (!image && !depth && !opacity && !stats) return KNERF_ERR_INVALID;
     const int deg = field->sh_degree, L = field->brick_log2;
-    if (flags & ~(KNERF_BAKED_WHITE_BACKGROUND | KNERF_BAKED_SKIP_EMPTY | KNERF_BAKED_LANES_MASK)) return KNERF_ERR_INVALID;
+    if (!baked::check_rays(near, far, near_all, far_all, n_rays, step, termination, flags)) return KNERF_ERR_INVALID;
     if ((flags & KNERF_BAKED_SKIP_EMPTY) && !field->bits) return KNERF_ERR_INVALID;
-    if (!(step > 0.f) || !std::isfinite(step) || !(termination >= 0.f) || !(termination < 1.f)) return KNERF_ERR_INVALID;
-    if ((!near && !std::isfinite(near_all)) || (!far && !std::isfinite(far_all))) return KNERF_ERR_INVALID;
-    int lanes = (flags & KNERF_BAKED_LANES_MASK) >> KNERF_BAKED_LANES_SHIFT;
-    if (lanes == 0) lanes = quant::default_lanes(deg);
-    if (!(lanes == 1 || (lanes == 2 && deg == 2) || (lanes == 4 && deg == 3))) return KNERF_ERR_INVALID;
-    if (n_rays >= (1ull << 36)) return KNERF_ERR_INVALID;
+    const int lanes = baked::pick_lanes(deg, flags, quant::kQuantLaneGroups);
+    if (!lanes) return KNERF_ERR_INVALID;
     if (n_rays == 0) return KNERF_OK;
     for (int c = 0; c < 3; ++c) { a.R[c] = field->resolution[c]; a.lo[c] = field->lo[c]; a.hi[c] = field->hi[c]; }
     a.rec = static_cast<const unsigned char*>(field->records); a.exps = qfield->exponents; a.brick_of = field->brick_of; a.bits = field->bits;

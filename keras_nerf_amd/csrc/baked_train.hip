@@ -1,9 +1,10 @@
 // baked_train.hip -- optimising a baked field against ray batches (gfx950), context-free: the gradient of the march of baked.hip and
-// the Adam step that rewrites the records.  Extension: the reference has nothing of the kind (PlenOctrees and Plenoxels optimise
-// their grids against the photographs after conversion in this way).  include/knerf.h holds the contract; tests/baked_train_reference.py
-// is its fp64 restatement.  baked.hip is not touched: the helpers of its march are restated here (same constants, same operations).
+// the Adam step that rewrites the records, for dense and for brick storage (the dense record table of a brick field is never formed).
+// Extension: the reference has nothing of the kind (PlenOctrees and Plenoxels optimise their grids against the photographs after
+// conversion in this way).  include/knerf.h holds the contract; tests/baked_train_reference.py is its fp64 restatement.  What the file
+// shares with the other baked*.hip files is in baked_common.h.
 //
-//   baked_train_rays_kernel   <DEG, G>, the lane variants of baked_render_kernel: G lanes march one ray, lane `sub` owns chunks
+//   baked_train_rays_kernel   <DEG, G, Args>, the lane variants of baked_render_kernel: G lanes march one ray, lane `sub` owns chunks
 //                             sub, sub + G, ... of every record.  Each ray is marched TWICE in the one launch by the same code
 //                             (march<DEG, G, BWD>): the first march is the render kernel's arithmetic sample for sample and gives C, O
 //                             and with them g = dL/dout; the second recomputes every sample, forms dL/dsigma and dL/dr and adds them
@@ -13,6 +14,14 @@
 //                             P the running sums of the second march.  They are the first march's own arithmetic, so at a ray's last
 //                             sample P equals the total bit for bit and the suffix is exactly 0; in between the difference carries the
 //                             rounding of the totals, about 2^-24 |C|.
+//                             Args = TrainArgs (dense) or BrickTrainArgs: ONE march for both storages (tests/test_gpu_baked_bricks_train.py
+//                             holds the two bit for bit).  Only a corner's address and its row differ (Args::kBrick).  Dense: the row
+//                             of a lattice point is slot_of[point].  Brick: the address is formed through brick_of as in
+//                             baked_render_kernel, with the lane's one-entry cache of the brick it looked up last; an entry < 0 or
+//                             >= n_bricks counts as absent BEFORE any address is formed, an absent corner's record reads as zero and
+//                             NOTHING is added for it, so a damaged table never becomes an out-of-range read or write.  There is no slot
+//                             table: the rows of gradient, master value and moments are per STORED RECORD, and a row's index is the
+//                             record's index.
 //   Gradient rows: fp32 [n_slots][1 + 3 K], sigma first, then [k][c]: the columns of a record.  Every lane of a group holds the whole
 //   basis and the same dL/dr and dL/dsigma, so any lane can form any column: lane `sub` adds the columns sub, sub + G, ... of a
 //   corner's row, so that ONE atomic instruction of the group adds G consecutive floats (the memory side works in 64-byte requests;
@@ -21,27 +30,17 @@
 //                             v += (g g - v)(1 - b2), w -= rate m / (sqrt(v) + eps)), sigma masked by the slot's flag and projected
 //                             to >= 0, the chunk of the record rewritten (fp32 sigma, fp16 coefficients to nearest even, zero padding),
 //                             the gradient columns zeroed.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/knerf.h"
+//   baked_bricks_train_apply_kernel  one lane per (record, chunk): the same arithmetic on the rows of a brick field.  flags[record]
+//                             bit 0: the record is a slot (a corner of a support cell); a record without it is skipped entirely.
+//                             Bit 1: sigma is trainable there.
+#include "baked_common.h"
 
 namespace knerf {
 namespace baked_train {
-
-constexpr int kBlock = 256;
-constexpr int kBatch = 8;                           // as baked.hip: samples whose support bits are looked up together
-constexpr int kMaxSamples = 1 << 23;
-constexpr unsigned long long kMaxBytes = 1ull << 40;
-
-__host__ __device__ constexpr int n_coeff(int deg) { return (deg + 1) * (deg + 1); }
-__host__ __device__ constexpr int rec_bytes(int deg) { return (4 + 6 * n_coeff(deg) + 15) / 16 * 16; }
-
-__device__ __forceinline__ float half_bits_to_float(unsigned h) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(h & 0xffffu)); }
-__device__ __forceinline__ unsigned float_to_half_bits(float f) { return (unsigned)__builtin_bit_cast(unsigned short, (_Float16)f); }   // round to nearest even
+using namespace baked;
 
 struct TrainArgs {
+    static constexpr bool kBrick = false;
     const uint4* rec;
     const unsigned* bits;
     int R[3];
@@ -57,68 +56,23 @@ struct TrainArgs {
     float* sq_err;
 };
 
-// the basis of baked.hip sh_eval
-template <int DEG>
-__device__ __forceinline__ void sh_eval(float x, float y, float z, float (&Y)[n_coeff(DEG)]) {
-    Y[0] = 0.28209479177387814f;
-    if constexpr (DEG >= 1) {
-        Y[1] = 0.4886025119029199f * y;
-        Y[2] = 0.4886025119029199f * z;
-        Y[3] = 0.4886025119029199f * x;
-    }
-    if constexpr (DEG >= 2) {
-        const float xx = x * x, yy = y * y, zz = z * z;
-        Y[4] = 1.0925484305920792f * (x * y);
-        Y[5] = 1.0925484305920792f * (y * z);
-        Y[6] = 0.31539156525252005f * (3.f * zz - 1.f);
-        Y[7] = 1.0925484305920792f * (x * z);
-        Y[8] = 0.5462742152960396f * (xx - yy);
-        if constexpr (DEG >= 3) {
-            Y[9] = 0.5900435899266435f * (y * (3.f * xx - yy));
-            Y[10] = 2.890611442640554f * (x * y * z);
-            Y[11] = 0.4570457994644658f * (y * (5.f * zz - 1.f));
-            Y[12] = 0.3731763325901154f * (z * (5.f * zz - 3.f));
-            Y[13] = 0.4570457994644658f * (x * (5.f * zz - 1.f));
-            Y[14] = 1.445305721320277f * (z * (xx - yy));
-            Y[15] = 0.5900435899266435f * (x * (xx - 3.f * yy));
-        }
-    }
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp(float x) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, false));
-}
-template <int G>
-__device__ __forceinline__ float group_sum(float x) {
-    if constexpr (G >= 2) x = x + dpp<0xB1>(x);        // quad_perm [1,0,3,2]
-    if constexpr (G >= 4) x = x + dpp<0x4E>(x);        // quad_perm [2,3,0,1]
-    return x;
-}
-template <int G>
-__device__ __forceinline__ float group_first(float x) {
-    if constexpr (G == 2) return dpp<0xA0>(x);         // quad_perm [0,0,2,2]
-    if constexpr (G == 4) return dpp<0x00>(x);         // quad_perm [0,0,0,0]
-    return x;
-}
-
-__device__ __forceinline__ bool locate(const TrainArgs& a, float near, const float (&o3)[3], const float (&d3)[3], int i, float& t,
-                                       int (&ci)[3], float (&fr)[3]) {
-    t = __fadd_rn(near, __fmul_rn((float)i + 0.5f, a.step));
-    bool inside = true;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float p = __fadd_rn(o3[c], __fmul_rn(d3[c], t));
-        const float u = __fmul_rn(__fsub_rn(p, a.lo[c]), a.scale[c]);
-        const int cells = a.R[c] - 1;
-        const bool in = u >= 0.f && u <= (float)cells;
-        inside = inside && in;
-        const int f = in ? (int)__builtin_floorf(u) : 0;
-        ci[c] = f < cells ? f : cells - 1;
-        fr[c] = __fsub_rn(u, (float)ci[c]);
-    }
-    return inside;
-}
+struct BrickTrainArgs {
+    static constexpr bool kBrick = true;
+    const uint4* rec;
+    const int* brick_of;
+    const unsigned* bits;
+    int R[3];
+    int L, By, Bz;                                  // log2 of the brick edge; the brick grid's y and z extents
+    long long n_bricks;
+    float lo[3], hi[3], scale[3];
+    const float *o, *d, *near, *far, *target;
+    float near0, far0;
+    long long n;
+    float step, eps, gscale;                        // gscale = 2 / (3 N)
+    int white;
+    float* grad;
+    float* sq_err;
+};
 
 // what the second march needs from the first: g = dL/dout (already gated by the output clamp) and the totals
 struct Totals {
@@ -127,16 +81,19 @@ struct Totals {
 
 // One march of one ray over the samples [i, i1): the loop of baked_render_kernel without depth and statistics.  BWD = false: img / opa
 // end as C / O.  BWD = true: the same arithmetic again (img / opa are then the prefix sums), and per sample the gradient is added.
-template <int DEG, int G, bool BWD>
-__device__ __forceinline__ void march(const TrainArgs& a, const float (&o3)[3], const float (&d3)[3], float near, int i, int i1,
+template <int DEG, int G, bool BWD, class Args>
+__device__ __forceinline__ void march(const Args& a, const float (&o3)[3], const float (&d3)[3], float near, int i, int i1,
                                       float delta, int sub, const float (&Y)[n_coeff(DEG)],
                                       const float (&wr)[(rec_bytes(DEG) / 16 + G - 1) / G][8],
                                       const float (&wg)[(rec_bytes(DEG) / 16 + G - 1) / G][8],
                                       const float (&wb)[(rec_bytes(DEG) / 16 + G - 1) / G][8],
                                       const float (&gy)[(1 + 3 * n_coeff(DEG) + G - 1) / G][3], float (&img)[3], float& opa, const Totals& tt) {
     constexpr int K = n_coeff(DEG), NCH = rec_bytes(DEG) / 16, CPL = (NCH + G - 1) / G, W = 1 + 3 * K, NI = (W + G - 1) / G;
-    const long long sy = a.R[2], sx = (long long)a.R[1] * a.R[2];
+    constexpr bool BRICK = Args::kBrick;
+    [[maybe_unused]] const long long sy = a.R[2], sx = (long long)a.R[1] * a.R[2];     // dense: the lattice's strides
     const int cyc = a.R[1] - 1, czc = a.R[2] - 1;
+    [[maybe_unused]] const int L = brick_log2(a), inm = (1 << L) - 1;
+    [[maybe_unused]] int last_key = -1, last_slot = -1;     // BRICK: the brick this lane looked up last, as baked_render_kernel
     float T = 1.f;
     img[0] = img[1] = img[2] = 0.f;
     opa = 0.f;
@@ -158,7 +115,29 @@ __device__ __forceinline__ void march(const TrainArgs& a, const float (&o3)[3], 
             int ci[3];
             float fr[3], t;
             locate(a, near, o3, d3, i + kk, t, ci, fr);
-            const long long base = (long long)ci[0] * sx + (long long)ci[1] * sy + ci[2];
+            // dense: the address is formed at its load.  BRICK: the 8 corner records through the brick table, in front of the loads:
+            // at[cn] < 0 = a point of an absent brick; the 8 record indices stay live from the loads to the scatter
+            [[maybe_unused]] const long long base = (long long)ci[0] * sx + (long long)ci[1] * sy + ci[2];
+            [[maybe_unused]] int at[8];
+            if constexpr (BRICK) {
+                int key[8], slot[8];
+#pragma unroll
+                for (int cn = 0; cn < 8; ++cn) {
+                    const int x = ci[0] + ((cn >> 2) & 1), y = ci[1] + ((cn >> 1) & 1), z = ci[2] + (cn & 1);
+                    key[cn] = ((x >> L) * a.By + (y >> L)) * a.Bz + (z >> L);
+                }
+#pragma unroll
+                for (int cn = 0; cn < 8; ++cn) slot[cn] = key[cn] == last_key ? last_slot : a.brick_of[key[cn]];
+                last_key = key[0]; last_slot = slot[0];
+                // a record's index fits 32 bits (n_bricks <= Bx By Bz, so at most 1032^3 records); byte offsets are formed in 64
+#pragma unroll
+                for (int cn = 0; cn < 8; ++cn) {
+                    const int x = ci[0] + ((cn >> 2) & 1), y = ci[1] + ((cn >> 1) & 1), z = ci[2] + (cn & 1);
+                    const int in = ((((x & inm) << L) | (y & inm)) << L) | (z & inm);
+                    const bool stored = slot[cn] >= 0 && (long long)slot[cn] < a.n_bricks;
+                    at[cn] = stored ? (int)(((unsigned)slot[cn] << (3 * L)) + (unsigned)in) : -1;
+                }
+            }
             float sig = 0.f, cf[CPL][8];
 #pragma unroll
             for (int j = 0; j < CPL; ++j)
@@ -167,12 +146,14 @@ __device__ __forceinline__ void march(const TrainArgs& a, const float (&o3)[3], 
 #pragma unroll
             for (int cn = 0; cn < 8; ++cn) {
                 const float w = ((cn & 4) ? fr[0] : 1.f - fr[0]) * ((cn & 2) ? fr[1] : 1.f - fr[1]) * ((cn & 1) ? fr[2] : 1.f - fr[2]);
-                const long long pt = base + ((cn & 4) ? sx : 0) + ((cn & 2) ? sy : 0) + (cn & 1);
+                long long pt;
+                if constexpr (BRICK) pt = at[cn];                   // (sign-extended: -1 stays -1)
+                else pt = base + ((cn & 4) ? sx : 0) + ((cn & 2) ? sy : 0) + (cn & 1);
                 uint4 v[CPL];
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) {
                     const int qc = sub + j * G;
-                    v[j] = qc < NCH ? a.rec[pt * NCH + qc] : make_uint4(0u, 0u, 0u, 0u);
+                    v[j] = (qc < NCH && (!BRICK || pt >= 0)) ? a.rec[pt * NCH + qc] : make_uint4(0u, 0u, 0u, 0u);
                 }
 #pragma unroll
                 for (int j = 0; j < CPL; ++j) {
@@ -240,10 +221,15 @@ __device__ __forceinline__ void march(const TrainArgs& a, const float (&o3)[3], 
 #pragma unroll
                     for (int cn = 0; cn < 8; ++cn) {
                         const float tw = ((cn & 4) ? fr[0] : 1.f - fr[0]) * ((cn & 2) ? fr[1] : 1.f - fr[1]) * ((cn & 1) ? fr[2] : 1.f - fr[2]);
-                        const long long pt = base + ((cn & 4) ? sx : 0) + ((cn & 2) ? sy : 0) + (cn & 1);
-                        const long long slot = a.slot_of[pt];
-                        if (slot < 0 || slot >= a.n_slots) continue;     // a corner of a support cell always has a slot; never write past the rows
-                        float* row = a.grad + slot * W;
+                        long long at_row;                                // the corner's row
+                        if constexpr (BRICK) {
+                            at_row = at[cn];
+                            if (at_row < 0) continue;                    // a point of an absent brick has no row: nothing is added
+                        } else {
+                            at_row = a.slot_of[base + ((cn & 4) ? sx : 0) + ((cn & 2) ? sy : 0) + (cn & 1)];
+                            if (at_row < 0 || at_row >= a.n_slots) continue;     // a corner of a support cell always has a slot; never write past the rows
+                        }
+                        float* row = a.grad + at_row * W;
                         // lane `sub` adds the columns sub, sub + G, ...: one instruction of the group adds G consecutive floats of the row
 #pragma unroll
                         for (int s = 0; s < NI; ++s) {
@@ -265,8 +251,8 @@ __device__ __forceinline__ void march(const TrainArgs& a, const float (&o3)[3], 
     }
 }
 
-template <int DEG, int G>
-__global__ __launch_bounds__(kBlock) void baked_train_rays_kernel(TrainArgs a) {
+template <int DEG, int G, class Args>
+__global__ __launch_bounds__(kBlock) void baked_train_rays_kernel(Args a) {
     constexpr int K = n_coeff(DEG), NCH = rec_bytes(DEG) / 16, CPL = (NCH + G - 1) / G;
     static_assert(G == 1 || G == 2 || G == 4, "a group is a lane, a pair or a quad");
     const long long gid = (long long)blockIdx.x * kBlock + threadIdx.x;
@@ -351,11 +337,13 @@ __global__ __launch_bounds__(kBlock) void baked_train_rays_kernel(TrainArgs a) {
     march<DEG, G, true>(a, o3, d3, near, i0, i1, delta, sub, Y, wr, wg, wb, gy, img, opa, tt);
 }
 
-template <int DEG, int G>
-hipError_t launch_rays(const TrainArgs& a, hipStream_t s) {
-    const long long lanes = a.n * G, blocks = (lanes + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL((baked_train_rays_kernel<DEG, G>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
-    return hipGetLastError();
+template <class Args>
+hipError_t launch_rays(int deg, int lanes, const Args& a, hipStream_t s) {
+    return dispatch_deg_lanes(deg, lanes, [&](auto DEG, auto G) {
+        const long long blocks = (a.n * G + kBlock - 1) / kBlock;
+        hipLaunchKernelGGL((baked_train_rays_kernel<DEG, G, Args>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
+        return hipGetLastError();
+    });
 }
 
 struct ApplyArgs {
@@ -367,18 +355,6 @@ struct ApplyArgs {
     int K, nch;
     float rate_sigma, rate_sh, b1, b2, eps;
 };
-
-__device__ __forceinline__ float adam(const ApplyArgs& a, long long at, float rate, bool train) {
-    const float g = a.g[at];
-    a.g[at] = 0.f;
-    float w = a.w[at];
-    if (!train) return w;
-    float m = a.m[at], v = a.v[at];
-    m = m + (g - m) * (1.f - a.b1);
-    v = v + (g * g - v) * (1.f - a.b2);
-    a.m[at] = m; a.v[at] = v;
-    return w - rate * m / (sqrtf(v) + a.eps);
-}
 
 __global__ __launch_bounds__(256) void baked_train_apply_kernel(ApplyArgs a) {
     const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -412,22 +388,91 @@ __global__ __launch_bounds__(256) void baked_train_apply_kernel(ApplyArgs a) {
     a.rec[p * a.nch + q] = out;
 }
 
-// the checks both entry points share; fills the lattice part of TrainArgs-like fields
+struct BrickApplyArgs {
+    uint4* rec;
+    const unsigned char* flags;
+    float *w, *m, *v, *g;
+    long long n_records;
+    int K, nch;
+    float rate_sigma, rate_sh, b1, b2, eps;
+};
+
+__global__ __launch_bounds__(256) void baked_bricks_train_apply_kernel(BrickApplyArgs a) {
+    const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= a.n_records * a.nch) return;
+    const long long record = idx / a.nch;
+    const int q = (int)(idx - record * a.nch);
+    const unsigned flag = a.flags[record];
+    if (!(flag & 1u)) return;                                   // not a slot: record, master, moments and gradient keep their bytes
+    const long long row = record * (1 + 3 * a.K);
+    float sig = 0.f;
+    if (q == 0) {
+        sig = fmaxf(adam(a, row, a.rate_sigma, (flag & 2u) != 0), 0.f);           // the projection; an untrainable sigma is and stays 0
+        a.w[row] = sig;
+    }
+    unsigned h[8];
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+        const int e = 8 * q - 2 + s;
+        h[s] = 0u;
+        if (e >= 0 && e < 3 * a.K) {
+            const float w = adam(a, row + 1 + e, a.rate_sh, true);
+            a.w[row + 1 + e] = w;
+            h[s] = float_to_half_bits(w);
+        }
+    }
+    uint4 out;
+    out.x = q == 0 ? __float_as_uint(sig) : (h[0] | (h[1] << 16));
+    out.y = h[2] | (h[3] << 16);
+    out.z = h[4] | (h[5] << 16);
+    out.w = h[6] | (h[7] << 16);
+    a.rec[record * a.nch + q] = out;
+}
+
+// what every entry point of the dense optimiser checks of its struct; the lattice's points come back
 static bool check_state(const knerf_baked_train* t, unsigned long long& points) {
     if (!t || !t->field.records || !t->field.bits || !t->slot_of || !t->grad) return false;
-    const int deg = t->field.sh_degree;
-    if (deg < 0 || deg > 3) return false;
-    points = 1;
-    for (int c = 0; c < 3; ++c) {
-        const int r = t->field.resolution[c];
-        if (r < 2 || r > 1025) return false;
-        if (!std::isfinite(t->field.lo[c]) || !std::isfinite(t->field.hi[c]) || !(t->field.hi[c] > t->field.lo[c])) return false;
-        points *= (unsigned)r;
-    }
-    if (points >= kMaxBytes / (unsigned)rec_bytes(deg)) return false;
+    if (!check_lattice(t->field.resolution, t->field.lo, t->field.hi, t->field.sh_degree, nullptr, points)) return false;
     // a slot is a lattice point: at least one, at most all of them (the rows then stay below 2^40 bytes with the records)
-    if (t->n_slots < 1 || t->n_slots > points) return false;
+    return t->n_slots >= 1 && t->n_slots <= points;
+}
+
+// the same for the brick optimiser: what knerf_baked_render_bricks refuses of its struct, and the NULLs this one adds
+static bool check_state(const knerf_baked_bricks_train* t, int (&B)[3], float (&scale)[3], unsigned long long& n_records) {
+    if (!t || !t->field.records || !t->field.brick_of || !t->field.bits || !t->grad) return false;
+    const knerf_baked_bricks* f = &t->field;
+    unsigned long long points = 0;
+    if (!check_lattice(f->resolution, f->lo, f->hi, f->sh_degree, scale, points)) return false;
+    if (!check_brick_grid(f->resolution, f->sh_degree, f->brick_log2, f->n_bricks, B)) return false;
+    n_records = f->n_bricks << (3 * f->brick_log2);
     return true;
+}
+
+// the ray arguments of both gradient launches; lanes comes back resolved.  n_rays = 0 is for the caller
+static bool check_train_rays(int deg, const float* origins, const float* directions, const float* near, const float* far, float near_all,
+                             float far_all, const float* target, uint64_t n_rays, uint64_t n_norm, float step, float termination,
+                             int flags, int& lanes) {
+    if (!origins || !directions || !target) return false;
+    if (!check_rays(near, far, near_all, far_all, n_rays, step, termination, flags) || n_norm >= (1ull << 36)) return false;
+    lanes = pick_lanes(deg, flags, kLaneGroups);
+    return lanes != 0;
+}
+
+// the same fields in both argument structs
+template <class Args>
+static void set_rays(Args& a, const float* origins, const float* directions, const float* near, const float* far, float near_all,
+                     float far_all, const float* target, uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags,
+                     float* grad, float* sq_err) {
+    a.o = origins; a.d = directions; a.near = near; a.far = far; a.near0 = near_all; a.far0 = far_all; a.target = target;
+    a.n = (long long)n_rays; a.step = step; a.eps = termination;
+    a.gscale = (float)(2.0 / (3.0 * (double)(n_norm ? n_norm : n_rays)));
+    a.white = (flags & KNERF_BAKED_WHITE_BACKGROUND) ? 1 : 0;
+    a.grad = grad; a.sq_err = sq_err;
+}
+
+static bool check_adam(float rate_sigma, float rate_sh, float beta_1, float beta_2, float epsilon) {
+    return std::isfinite(rate_sigma) && std::isfinite(rate_sh) && (beta_1 >= 0.f && beta_1 < 1.f) && (beta_2 >= 0.f && beta_2 < 1.f) &&
+           (epsilon > 0.f) && std::isfinite(epsilon);
 }
 
 }  // namespace baked_train
@@ -439,43 +484,22 @@ extern "C" int knerf_baked_train_rays(void* stream, const knerf_baked_train* tra
                                       const float* near, const float* far, float near_all, float far_all, const float* target,
                                       uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags, float* sq_err) {
     unsigned long long points = 0;
-    if (!baked_train::check_state(train, points) || !origins || !directions || !target) return KNERF_ERR_INVALID;
-    if (flags & ~(KNERF_BAKED_WHITE_BACKGROUND | KNERF_BAKED_SKIP_EMPTY | KNERF_BAKED_LANES_MASK)) return KNERF_ERR_INVALID;
-    if (!(step > 0.f) || !std::isfinite(step) || !(termination >= 0.f) || !(termination < 1.f)) return KNERF_ERR_INVALID;
-    if ((!near && !std::isfinite(near_all)) || (!far && !std::isfinite(far_all))) return KNERF_ERR_INVALID;
+    int lanes = 0;
+    if (!baked_train::check_state(train, points)) return KNERF_ERR_INVALID;
     const knerf_baked_field* field = &train->field;
     const int deg = field->sh_degree;
+    if (!baked_train::check_train_rays(deg, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination,
+                                       flags, lanes))
+        return KNERF_ERR_INVALID;
     baked_train::TrainArgs a{};
-    for (int c = 0; c < 3; ++c) {
-        const int r = field->resolution[c];
-        a.R[c] = r; a.lo[c] = field->lo[c]; a.hi[c] = field->hi[c];
-        a.scale[c] = (float)((double)(r - 1) / ((double)field->hi[c] - (double)field->lo[c]));
-        if (!std::isfinite(a.scale[c])) return KNERF_ERR_INVALID;
-    }
-    int lanes = (flags & KNERF_BAKED_LANES_MASK) >> KNERF_BAKED_LANES_SHIFT;
-    if (lanes == 0) lanes = deg == 0 ? 1 : (deg == 1 ? 2 : 4);
-    if (!(lanes == 1 || (lanes == 2 && deg == 1) || (lanes == 4 && deg >= 2))) return KNERF_ERR_INVALID;
-    if (n_rays >= (1ull << 36) || n_norm >= (1ull << 36)) return KNERF_ERR_INVALID;
+    if (!baked::check_lattice(field->resolution, field->lo, field->hi, deg, a.scale, points)) return KNERF_ERR_INVALID;
     if (n_rays == 0) return KNERF_OK;
+    for (int c = 0; c < 3; ++c) { a.R[c] = field->resolution[c]; a.lo[c] = field->lo[c]; a.hi[c] = field->hi[c]; }
     a.rec = static_cast<const uint4*>(field->records); a.bits = field->bits;
-    a.o = origins; a.d = directions; a.near = near; a.far = far; a.near0 = near_all; a.far0 = far_all; a.target = target;
-    a.n = (long long)n_rays; a.step = step; a.eps = termination;
-    a.gscale = (float)(2.0 / (3.0 * (double)(n_norm ? n_norm : n_rays)));
-    a.white = (flags & KNERF_BAKED_WHITE_BACKGROUND) ? 1 : 0;
-    a.slot_of = train->slot_of; a.n_slots = (long long)train->n_slots; a.grad = train->grad; a.sq_err = sq_err;
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipErrorInvalidValue;
-    switch (deg * 8 + lanes) {
-        case 0 * 8 + 1: e = baked_train::launch_rays<0, 1>(a, s); break;
-        case 1 * 8 + 1: e = baked_train::launch_rays<1, 1>(a, s); break;
-        case 1 * 8 + 2: e = baked_train::launch_rays<1, 2>(a, s); break;
-        case 2 * 8 + 1: e = baked_train::launch_rays<2, 1>(a, s); break;
-        case 2 * 8 + 4: e = baked_train::launch_rays<2, 4>(a, s); break;
-        case 3 * 8 + 1: e = baked_train::launch_rays<3, 1>(a, s); break;
-        case 3 * 8 + 4: e = baked_train::launch_rays<3, 4>(a, s); break;
-        default: return KNERF_ERR_INVALID;
-    }
-    return e == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
+    a.slot_of = train->slot_of; a.n_slots = (long long)train->n_slots;
+    baked_train::set_rays(a, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination, flags,
+                          train->grad, sq_err);
+    return baked_train::launch_rays(deg, lanes, a, (hipStream_t)stream) == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
 }
 
 extern "C" int knerf_baked_train_apply(void* stream, const knerf_baked_train* train, const int32_t* point_of,
@@ -483,18 +507,60 @@ extern "C" int knerf_baked_train_apply(void* stream, const knerf_baked_train* tr
                                        float beta_1, float beta_2, float epsilon) {
     unsigned long long points = 0;
     if (!baked_train::check_state(train, points) || !point_of || !sigma_trainable || !master || !m || !v) return KNERF_ERR_INVALID;
-    if (!std::isfinite(rate_sigma) || !std::isfinite(rate_sh) || !(beta_1 >= 0.f && beta_1 < 1.f) || !(beta_2 >= 0.f && beta_2 < 1.f) ||
-        !(epsilon > 0.f) || !std::isfinite(epsilon))
-        return KNERF_ERR_INVALID;
+    if (!baked_train::check_adam(rate_sigma, rate_sh, beta_1, beta_2, epsilon)) return KNERF_ERR_INVALID;
     const int deg = train->field.sh_degree;
     baked_train::ApplyArgs a{};
     a.rec = static_cast<uint4*>(const_cast<void*>(train->field.records));
     a.point_of = point_of; a.trainable = sigma_trainable; a.w = master; a.m = m; a.v = v; a.g = train->grad;
     a.n_slots = (long long)train->n_slots; a.n_points = (long long)points;
-    a.K = baked_train::n_coeff(deg); a.nch = baked_train::rec_bytes(deg) / 16;
+    a.K = baked::n_coeff(deg); a.nch = baked::rec_bytes(deg) / 16;
     a.rate_sigma = rate_sigma; a.rate_sh = rate_sh; a.b1 = beta_1; a.b2 = beta_2; a.eps = epsilon;
     const unsigned long long blocks = (train->n_slots * (unsigned)a.nch + 255) / 256;
     if (blocks >= (1ull << 31)) return KNERF_ERR_INVALID;
     hipLaunchKernelGGL(baked_train::baked_train_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
+}
+
+extern "C" int knerf_baked_bricks_train_rays(void* stream, const knerf_baked_bricks_train* train, const float* origins,
+                                             const float* directions, const float* near, const float* far, float near_all, float far_all,
+                                             const float* target, uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags,
+                                             float* sq_err) {
+    int B[3], lanes = 0;
+    unsigned long long n_records = 0;
+    baked_train::BrickTrainArgs a{};
+    if (!baked_train::check_state(train, B, a.scale, n_records)) return KNERF_ERR_INVALID;
+    const knerf_baked_bricks* field = &train->field;
+    const int deg = field->sh_degree;
+    // every lane variant of knerf_baked_train_rays exists here too: each builds without scratch (DESIGN.md 2.23 has hipcc's counts)
+    if (!baked_train::check_train_rays(deg, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination,
+                                       flags, lanes))
+        return KNERF_ERR_INVALID;
+    if (n_rays == 0) return KNERF_OK;
+    for (int c = 0; c < 3; ++c) { a.R[c] = field->resolution[c]; a.lo[c] = field->lo[c]; a.hi[c] = field->hi[c]; }
+    a.rec = static_cast<const uint4*>(field->records); a.brick_of = field->brick_of; a.bits = field->bits;
+    a.L = field->brick_log2; a.By = B[1]; a.Bz = B[2]; a.n_bricks = (long long)field->n_bricks;
+    baked_train::set_rays(a, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination, flags,
+                          train->grad, sq_err);
+    return baked_train::launch_rays(deg, lanes, a, (hipStream_t)stream) == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
+}
+
+extern "C" int knerf_baked_bricks_train_apply(void* stream, const knerf_baked_bricks_train* train, const uint8_t* flags, float* master,
+                                              float* m, float* v, float rate_sigma, float rate_sh, float beta_1, float beta_2,
+                                              float epsilon) {
+    int B[3];
+    float scale[3];
+    unsigned long long n_records = 0;
+    if (!baked_train::check_state(train, B, scale, n_records) || !flags || !master || !m || !v) return KNERF_ERR_INVALID;
+    if (!baked_train::check_adam(rate_sigma, rate_sh, beta_1, beta_2, epsilon)) return KNERF_ERR_INVALID;
+    const int deg = train->field.sh_degree;
+    baked_train::BrickApplyArgs a{};
+    a.rec = static_cast<uint4*>(const_cast<void*>(train->field.records));
+    a.flags = flags; a.w = master; a.m = m; a.v = v; a.g = train->grad;
+    a.n_records = (long long)n_records;
+    a.K = baked::n_coeff(deg); a.nch = baked::rec_bytes(deg) / 16;
+    a.rate_sigma = rate_sigma; a.rate_sh = rate_sh; a.b1 = beta_1; a.b2 = beta_2; a.eps = epsilon;
+    const unsigned long long blocks = (n_records * (unsigned)a.nch + 255) / 256;
+    if (blocks >= (1ull << 31)) return KNERF_ERR_INVALID;
+    hipLaunchKernelGGL(baked_train::baked_bricks_train_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
 }

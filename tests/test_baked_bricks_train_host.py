@@ -1,7 +1,7 @@
 """Optimising a brick baked field, the parts that need no GPU: the package's train-brick set, flags and master rows
 (keras_nerf_amd/baked_bricks_train.py train_state) and the gather behind finish() (kept_bricks) on host tensors against
-tests/baked_bricks_train_reference.py, the argument checks of the Python surface and of both entry points, and the text of the
-helpers csrc/baked_bricks_train.hip restates.  Every condition is stated in tests/README_baked_bricks_train.md."""
+tests/baked_bricks_train_reference.py, the argument checks of the Python surface and of both entry points, and that the helpers of
+the march are defined once (csrc/baked_common.h).  Every condition is stated in tests/README_baked_bricks_train.md."""
 import numpy as np
 import pytest
 
@@ -241,33 +241,13 @@ def test_entry_points_refuse_bad_arguments_before_any_launch():
         assert apply(state(), **bad) == INV, bad
 
 
-def test_the_restated_helpers_are_those_of_the_kernels_they_restate():
-    """csrc/baked_bricks_train.hip restates the march helpers and the Adam column of csrc/baked_train.hip (which is not edited): same
-    text; and the two kernels differ from the dense ones only where the file says"""
+def test_the_march_helpers_and_the_adam_column_are_defined_once_in_the_shared_header():
+    """the dense and the brick optimiser run ONE march (csrc/baked_train.hip), and what they share with the other baked*.hip files --
+    sh_eval, the DPP group sums, locate, the Adam column, the record's sizes and codec -- is defined once, in csrc/baked_common.h"""
     import os
-    import re
     from keras_nerf_amd import baked
-    csrc = os.path.join(os.path.dirname(os.path.abspath(baked.__file__)), "csrc")
-    a, b = (open(os.path.join(csrc, f)).read() for f in ("baked_train.hip", "baked_bricks_train.hip"))
-
-    def body(src, head):
-        i = src.index(head)
-        return re.sub(r"//[^\n]*", "", src[i:src.index("\n}\n", i)]).split()
-    for head in ("__device__ __forceinline__ void sh_eval(", "__device__ __forceinline__ float group_sum(",
-                 "__device__ __forceinline__ float group_first(", "__device__ __forceinline__ bool locate(",
-                 "__device__ __forceinline__ float adam("):
-        assert body(a, head) == body(b, head), head
-    # the ray kernel behind its march: the same text but for the kernel's name
-    ka = body(a, "__global__ __launch_bounds__(kBlock) void baked_train_rays_kernel(")
-    kb = body(b, "__global__ __launch_bounds__(kBlock) void baked_bricks_train_rays_kernel(")
-    assert ka[:3] == kb[:3] and ka[4:] == kb[4:] and ka[3] != kb[3]
-    # the march: every line of the dense march that does not form an address is in the brick march, in order
-    ma, mb = (src[src.index("__device__ __forceinline__ void march("):src.index("template <int DEG, int G>\n__global__")] for src in (a, b))
-    strip = lambda s: [ln.split("//")[0].strip() for ln in s.splitlines() if ln.split("//")[0].strip()]
-    la, lb = strip(ma), strip(mb)
-    address = ("const long long sy =", "const long long base =", "const long long pt =", "v[j] =", "const long long slot =",
-               "if (slot < 0", "float* row =")
-    rest = [ln for ln in la if not ln.startswith(address)]
-    it = iter(lb)
-    missing = [ln for ln in rest if not any(ln == other for other in it)]
-    assert not missing, missing
+    from tests.test_baked_train_host import MARCH_HELPERS, defined_once_in_the_header
+    defined_once_in_the_header(MARCH_HELPERS + ("__device__ __forceinline__ float adam(",))
+    src = open(os.path.join(os.path.dirname(os.path.abspath(baked.__file__)), "csrc", "baked_train.hip")).read()
+    assert src.count("__device__ __forceinline__ void march(") == 1 and src.count("void baked_train_rays_kernel(") == 1
+    assert "knerf_baked_train_rays(" in src and "knerf_baked_bricks_train_rays(" in src

@@ -29,10 +29,11 @@ def test_sh_basis_is_orthonormal_under_an_exact_quadrature():
 
 
 def test_kernel_constants_agree_with_the_reference():
-    """the literals of csrc/baked.hip sh_eval, read from the source, against the closed forms"""
+    """the literals of sh_eval (csrc/baked_common.h: the one definition every baked*.hip uses), read from the source, against the closed
+    forms"""
     import os
     import re
-    src = open(os.path.join(os.path.dirname(os.path.abspath(B.__file__)), "csrc", "baked.hip")).read()
+    src = open(os.path.join(os.path.dirname(os.path.abspath(B.__file__)), "csrc", "baked_common.h")).read()
     body = src[src.index("void sh_eval"):src.index("template <int CTRL>")]
     got = [float(m) for m in re.findall(r"Y\[\d+\] = ([0-9.]+)f", body)]
     pi = np.pi

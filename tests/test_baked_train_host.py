@@ -224,18 +224,34 @@ def test_entry_points_refuse_bad_arguments_before_any_launch():
         assert apply(state(), **bad) == INV, bad
 
 
-def test_the_restated_march_helpers_are_those_of_the_render_kernel():
-    """csrc/baked_train.hip restates sh_eval, the DPP group sums and locate of csrc/baked.hip (which is not edited): same text"""
+def defined_once_in_the_header(heads):
+    """every head of `heads` is defined exactly once across csrc/baked*.hip and csrc/baked_common.h, and that once is in the header; every
+    baked*.hip that calls one of them includes the header"""
+    import glob
     import os
     import re
     from keras_nerf_amd import baked
     csrc = os.path.join(os.path.dirname(os.path.abspath(baked.__file__)), "csrc")
-    a, b = (open(os.path.join(csrc, f)).read() for f in ("baked.hip", "baked_train.hip"))
+    files = sorted(glob.glob(os.path.join(csrc, "baked*.hip")))
+    assert len(files) >= 5, files
+    text = {os.path.basename(f): re.sub(r"//[^\n]*", "", open(f).read()) for f in files + [os.path.join(csrc, "baked_common.h")]}
+    for head in heads:
+        where = [(name, src.count(head)) for name, src in text.items() if head in src]
+        assert where == [("baked_common.h", 1)], (head, where)
+    for name, src in text.items():
+        if name == "baked_common.h":
+            continue
+        calls = [head for head in heads if re.search(r"\b" + re.escape(head.split()[-1].rstrip("(")) + r"\s*[<(]", src)]
+        assert not calls or '#include "baked_common.h"' in src, (name, calls)
 
-    def body(src, head):
-        i = src.index(head)
-        return re.sub(r"//[^\n]*", "", src[i:src.index("\n}\n", i)]).replace("RenderArgs", "Args").replace("TrainArgs", "Args").split()
-    for head in ("__device__ __forceinline__ void sh_eval(", "__device__ __forceinline__ float group_sum(",
-                 "__device__ __forceinline__ float group_first(", "__device__ __forceinline__ bool locate("):
-        assert body(a, head) == body(b, head), head
 
+# the definitions' first lines as they stand in the header (template heads are on the line above)
+MARCH_HELPERS = ("__device__ __forceinline__ void sh_eval(", "__device__ __forceinline__ float group_sum(",
+                 "__device__ __forceinline__ float group_first(", "__device__ __forceinline__ bool locate(",
+                 "__device__ __forceinline__ float dpp(", "__host__ __device__ constexpr int n_coeff(",
+                 "__host__ __device__ constexpr int rec_bytes(", "__device__ __forceinline__ float half_bits_to_float(")
+
+
+def test_the_march_helpers_are_defined_once_in_the_shared_header():
+    """sh_eval, the DPP group sums, locate and the record's sizes and codec: one definition, in csrc/baked_common.h, for every baked*.hip"""
+    defined_once_in_the_header(MARCH_HELPERS)

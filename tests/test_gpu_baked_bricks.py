@@ -1,4 +1,4 @@
-"""The brick storage of a baked field on the GPU (keras_nerf_amd/baked.py BrickBakedField, csrc/baked_bricks.hip): renders that are
+"""The brick storage of a baked field on the GPU (keras_nerf_amd/baked.py BrickBakedField, csrc/baked.hip): renders that are
 bit-identical to the dense field's for every degree, kernel variant, skipping on / off, background and brick size; compact / to_dense
 against tests/baked_bricks_reference.py; persistence; baking straight into bricks.  The conditions are stated in
 tests/README_baked_bricks.md.  No test feeds the kernel a damaged table: its range guard is checked by reading."""

@@ -1,4 +1,4 @@
-"""Optimising a brick baked field on the GPU (keras_nerf_amd/baked_bricks_train.py, csrc/baked_bricks_train.hip): bit identity with the
+"""Optimising a brick baked field on the GPU (keras_nerf_amd/baked_bricks_train.py, csrc/baked_train.hip): bit identity with the
 dense optimiser of the same field, whole batches against the fp64 reference, the support invariant over twenty steps, a short
 optimisation with save / load, the memory condition (no tensor of the dense table's size) and the lane variants.  The conditions are
 stated in tests/README_baked_bricks_train.md.  No test feeds the kernel a damaged table: its range guard is checked by reading.

@@ -5,7 +5,7 @@ views on poses pose_spherical(theta, -30, 4), white background, termination --th
 and its QuantizedBrickField:
   - bytes on the device (records + exponents + brick table + bits) and in the saved file;
   - quantize() and dequantize() seconds (device-synchronised wall clock, the median of five after a warm-up call);
-  - frame time: HIP events around render(), --frames poses per round, the brick kernel (the untouched launch of csrc/baked_bricks.hip at
+  - frame time: HIP events around render(), --frames poses per round, the brick kernel (the untouched launch of csrc/baked.hip at
     its default variant) and every variant of the quantised kernel alternating in rotating order inside every pose, after a warm-up
     render of each; the median per round, --rounds rounds, and the spread of the rounds' medians (max - min): the run-to-run figure a
     difference between two of them has to exceed;
