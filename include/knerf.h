@@ -659,6 +659,48 @@ int knerf_baked_bricks_train_rays(void* stream, const knerf_baked_bricks_train* 
 int knerf_baked_bricks_train_apply(void* stream, const knerf_baked_bricks_train* train, const uint8_t* flags, float* master, float* m,
                                    float* v, float rate_sigma, float rate_sh, float beta_1, float beta_2, float epsilon);
 
+/* ---- Growing a brick field as it is.  Extension, no reference counterpart.  "Growing a baked field" above on the brick layout, so that
+ * a field is resampled, regularised and pruned without a table of the dense lattice's size; csrc/baked_bricks_grow.hip,
+ * tests/baked_bricks_grow_reference.py restates it in NumPy.  The arithmetic of a lattice point is one text for both storages
+ * (csrc/baked_grow_common.h): each launch gives the bits of its dense counterpart on the dense arrays of the field (absent bricks read as
+ * zero records).  Every table lookup is range-checked before an address is formed; every element offset is computed in 64 bits. */
+/* knerf_baked_resample_bricks_sigma -- extension, no reference counterpart.  The first pass of resampling a brick field: dst_sigma, fp32
+ * [R'x][R'y][R'z] (DEVICE), the sigma knerf_baked_resample stores at every point of the lattice dst_resolution (HOST [3]) from the dense
+ * arrays of src: the same placement (u in double, cell, f), the same lerp along z, then y, then x, a result <= sigma_threshold stored as
+ * exactly 0.  One lane per new point; a source corner whose brick_of entry is < 0 or >= n_bricks reads as a zero record.  src->bits is not
+ * read.  From dst_sigma the caller forms the new occupancy bits (knerf_occupancy_from_grid(sigma', 0, 0)) and from them the new brick table.
+ * KNERF_ERR_INVALID, before any launch: NULL src, dst_resolution or dst_sigma; everything knerf_baked_render_bricks refuses of its field;
+ * every argument error of knerf_baked_resample (a new resolution outside 2..1025, a new table of 2^40 bytes or more, sigma_threshold
+ * negative or not finite). */
+int knerf_baked_resample_bricks_sigma(void* stream, const knerf_baked_bricks* src, const int32_t dst_resolution[3], float sigma_threshold,
+                                      float* dst_sigma);
+/* knerf_baked_resample_bricks -- extension, no reference counterpart.  The second pass: the records of the destination's stored bricks.
+ * dst: HOST struct with the destination's lattice, box, degree, brick size, brick table and n_bricks; dst->records and dst->bits are not
+ * read (dst_records is what is written).  dst_keys: int32 [n_bricks'] (DEVICE), the linear index in the destination's brick grid of every
+ * stored destination brick, ascending (the inverse of dst->brick_of).  dst_records: [n_bricks'][b'^3] records, one lane per (record,
+ * 16-byte chunk).  A place past the lattice, and every record of a brick whose key lies outside the brick grid, is written as zeros, so
+ * the caller may pass uninitialised memory.  Every other record is what knerf_baked_resample writes for that lattice point from the dense
+ * arrays of src: fp32 sigma with the threshold, coefficients fp16 -> fp32 -> fp16 to nearest even, zero padding.  The source and
+ * destination brick sizes may differ.
+ * KNERF_ERR_INVALID, before any launch: NULL src, dst, dst_keys or dst_records; everything knerf_baked_render_bricks refuses of either
+ * field (dst->records apart); a degree or a box that differs between the two; sigma_threshold negative or not finite; dst_records
+ * overlapping the source records. */
+int knerf_baked_resample_bricks(void* stream, const knerf_baked_bricks* src, const knerf_baked_bricks* dst, const int32_t* dst_keys,
+                                float sigma_threshold, void* dst_records);
+/* knerf_baked_bricks_train_tv -- extension, no reference counterpart.  knerf_baked_train_tv on the rows of knerf_baked_bricks_train: ADDS
+ * to grad the gradient of the same R with v_q(p) = master[record of p][q].  A point takes part iff it lies in the lattice, its brick is
+ * stored and its flag has bit 0 (flags: as knerf_baked_bricks_train_apply); for a train-brick set that is the dense optimiser's slot set.
+ * keys: int32 [n_bricks] (DEVICE), the linear brick-grid index of every stored brick, ascending (the inverse of brick_of): a record
+ * learns its lattice point from it.  The records of a brick whose key lies outside the brick grid take no part.  A record without bit 0
+ * keeps its gradient row and gets tv_out = (0, 0).  g of a record's column is formed in registers by knerf_baked_train_tv's formula in
+ * its order of operations and added to grad with ONE fp32 add, no atomics: the rows get the bits knerf_baked_train_tv gives the same master
+ * and gradient values, and two calls from the same state give the same bits.  A weight of exactly 0 leaves the columns of its group
+ * untouched.  tv_out: fp32 [n_bricks b^3][2] or NULL, as there.  With both weights 0 and tv_out NULL nothing is launched.
+ * KNERF_ERR_INVALID, before any launch: NULL train, keys, flags or master; epsilon <= 0 or not finite; a weight that is negative or not
+ * finite; every struct error of knerf_baked_bricks_train_apply. */
+int knerf_baked_bricks_train_tv(void* stream, const knerf_baked_bricks_train* train, const int32_t* keys, const uint8_t* flags,
+                                const float* master, float weight_sigma, float weight_sh, float epsilon, float* tv_out);
+
 /* ---- Refining camera poses against a baked field.  Extension, no reference counterpart (BARF, NeRF-- and the current toolkits optimise
  * their cameras with the field).  Three context-free launches; csrc/baked_pose.hip, tests/baked_pose_reference.py restates them in fp64,
  * DESIGN.md 2.24 has the derivation.  The MLP path has no input gradient; NDC rays are not covered (the pose does not enter them as

@@ -161,6 +161,9 @@ SIGNATURES = {
                                                 C.c_uint64, C.c_float, C.c_float, C.c_int, _F]),
     "knerf_baked_bricks_train_apply": (C.c_int, [_P, C.POINTER(KnerfBakedBricksTrain), _P, _F, _F, _F, C.c_float, C.c_float, C.c_float,
                                                  C.c_float, C.c_float]),
+    "knerf_baked_resample_bricks_sigma": (C.c_int, [_P, C.POINTER(KnerfBakedBricks), C.POINTER(C.c_int32), C.c_float, _F]),
+    "knerf_baked_resample_bricks": (C.c_int, [_P, C.POINTER(KnerfBakedBricks), C.POINTER(KnerfBakedBricks), _P, C.c_float, _P]),
+    "knerf_baked_bricks_train_tv": (C.c_int, [_P, C.POINTER(KnerfBakedBricksTrain), _P, _P, _F, C.c_float, C.c_float, C.c_float, _F]),
     "knerf_baked_ray_gradients": (C.c_int, [_P, C.POINTER(KnerfBakedField), _F, _F, _F, _F, C.c_float, C.c_float, _F, C.c_uint64,
                                             C.c_uint64, C.c_float, C.c_float, C.c_int, _F, _F, _F]),
     "knerf_baked_ray_gradients_bricks": (C.c_int, [_P, C.POINTER(KnerfBakedBricks), _F, _F, _F, _F, C.c_float, C.c_float, _F, C.c_uint64,

@@ -648,7 +648,7 @@ class BrickBakedField:
     a corner of an occupied cell stored, behind the int32 table brick_of [Bx,By,Bz] (slot or -1); every other record reads as zero.
     render() marches rays through it on the GPU and gives the bits of the dense field's render().  Built by BakedField.compact,
     NeRF.bake(bricks=...) or BrickBakedField.load; to_dense() leads back.  baked_train.brick_optimizer(field, ...) optimises it as it
-    is; resampling, the total-variation regulariser and fit_coarse_to_fine work on a BakedField."""
+    is; baked_bricks_grow has resampling, the total-variation regulariser, pruning and coarse-to-fine fitting on bricks."""
 
     def __init__(self, records, brick_of, words, resolution, bounds, sh_degree, brick=DEFAULT_BRICK, sigma_threshold=0.0):
         # uint8 [n_bricks, b^3, record bytes], int32 [Bx,By,Bz], int32 [ceil(cells / 32)] on the device
@@ -800,7 +800,8 @@ class BrickBakedField:
 def __getattr__(name):
     """the optimiser's names live in baked_train.py (which imports this module) and are reachable from here as well"""
     if name in ("BakedFieldOptimizer", "check_optimizer_args", "check_target_shape", "bias_corrected_rate", "check_tv_args",
-                "fit_coarse_to_fine", "BrickFieldOptimizer", "brick_optimizer", "BRICK_TRAIN_VARIANTS"):
+                "fit_coarse_to_fine", "BrickFieldOptimizer", "brick_optimizer", "BRICK_TRAIN_VARIANTS", "BrickGridTrainer", "grid_trainer",
+                "resample_bricks", "fit_coarse_to_fine_bricks"):
         from . import baked_train
         return getattr(baked_train, name)
     if name in ("QuantizedBrickField", "quantized_record_bytes", "quantize_bricks", "dequantize_bricks", "read_quantized_brick_file"):

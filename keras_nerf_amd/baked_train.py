@@ -255,7 +255,7 @@ def brick_optimizer(field, learning_rate_sigma, learning_rate_sh, beta_1=0.9, be
     """A BrickFieldOptimizer (baked_bricks_train.py) over a COPY of a BrickBakedField's bricks: BakedField.optimizer for a field
     stored as sparse bricks, with the same arguments and meaning, optimised as it is (no table of the dense lattice's size is formed;
     finish() gives a BrickBakedField).  There is no total-variation regulariser here: tv_sigma, tv_sh and tv_epsilon belong to the
-    dense optimiser (field.to_dense().optimizer(...)), as resampling and fit_coarse_to_fine do."""
+    dense optimiser and, on bricks, to baked_bricks_grow.grid_trainer, beside resample_bricks and fit_coarse_to_fine_bricks."""
     from .baked_bricks_train import BrickFieldOptimizer
     from .baked_quant import QuantizedBrickField
     if isinstance(field, QuantizedBrickField):
@@ -269,6 +269,9 @@ def __getattr__(name):
     if name in ("BrickFieldOptimizer", "BRICK_TRAIN_VARIANTS"):
         from . import baked_bricks_train
         return getattr(baked_bricks_train, name)
+    if name in ("BrickGridTrainer", "grid_trainer", "resample_bricks", "fit_coarse_to_fine_bricks"):
+        from . import baked_bricks_grow       # (it imports this module as well)
+        return getattr(baked_bricks_grow, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -2,7 +2,7 @@
 // regulariser over the slots of an optimiser and the resampling of a field onto another lattice (coarse to fine).  Extension: the
 // reference has nothing of the kind (Plenoxels and its kin regularise and refine their grids in this way).  include/knerf.h holds
 // the contract; tests/baked_grow_reference.py is its NumPy restatement.  The record's sizes and codec and the lattice check are those
-// of baked_common.h.
+// of baked_common.h; the arithmetic of a point is that of baked_grow_common.h, which baked_bricks_grow.hip shares.
 //
 //   baked_tv_kernel <W>       one lane per (slot, column) of the rows [n_slots][W], W = 1 + 3 K = 4 / 13 / 28 / 49.  A block of 256
 //                             lanes holds floor(256 / W) WHOLE rows (256 / 247 / 252 / 245 lanes at work), so that consecutive lanes
@@ -15,10 +15,10 @@
 //                             records, trilinear z, y, x with lerp(a, b, f) = a (1 - f) + b f in separate roundings (f = 0 returns a,
 //                             f = 1 returns b, exactly), the position of the new point on each axis computed in double.
 #include "baked_common.h"
+#include "baked_grow_common.h"
 
 namespace knerf {
 namespace baked_grow {
-using namespace baked;
 
 struct TvArgs {
     const int* slot_of;
@@ -38,15 +38,6 @@ __device__ __forceinline__ long long slot_at(const TvArgs& a, int x, int y, int 
     return s < a.n_slots ? s : -1;
 }
 
-// tv at a point with value v whose successors along x, y, z have the slots s[0..2] (-1: no difference along that axis); the
-// differences come back in d
-template <int W>
-__device__ __forceinline__ float tv_term(const TvArgs& a, int q, float v, const long long (&s)[3], float (&d)[3]) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) d[c] = s[c] >= 0 ? a.master[s[c] * W + q] - v : 0.f;
-    return sqrtf(((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) + a.eps);
-}
-
 template <int W>
 __global__ __launch_bounds__(kBlock) void baked_tv_kernel(TvArgs a) {
     constexpr int S = kBlock / W;                        // whole rows per block
@@ -60,49 +51,14 @@ __global__ __launch_bounds__(kBlock) void baked_tv_kernel(TvArgs a) {
     if (valid && (w != 0.f || a.tv_out)) {
         const long long p = a.point_of[slot];
         if (p >= 0 && p < a.n_points) {
-            const long long at = slot * W + q;
             const int z = (int)(p % a.R[2]);
             const long long xy = p / a.R[2];
             const int y = (int)(xy % a.R[1]), x = (int)(xy / a.R[1]);
-            const float v0 = a.master[at];
-            float d[3];
-            const long long s0[3] = {slot_at(a, x + 1, y, z), slot_at(a, x, y + 1, z), slot_at(a, x, y, z + 1)};
-            tv0 = tv_term<W>(a, q, v0, s0, d);
-            if (w != 0.f) {
-                float acc = 0.f - ((d[0] + d[1]) + d[2]) / tv0;      // (0 - x, not -x: where every difference is 0, g is +0)
-                // the predecessors: along axis c the successor of p - e_c is p itself
-                const long long sx = slot_at(a, x - 1, y, z);
-                if (sx >= 0) {
-                    const long long s[3] = {slot, slot_at(a, x - 1, y + 1, z), slot_at(a, x - 1, y, z + 1)};
-                    const float tv = tv_term<W>(a, q, a.master[sx * W + q], s, d);
-                    acc = acc + d[0] / tv;
-                }
-                const long long sy = slot_at(a, x, y - 1, z);
-                if (sy >= 0) {
-                    const long long s[3] = {slot_at(a, x + 1, y - 1, z), slot, slot_at(a, x, y - 1, z + 1)};
-                    const float tv = tv_term<W>(a, q, a.master[sy * W + q], s, d);
-                    acc = acc + d[1] / tv;
-                }
-                const long long sz = slot_at(a, x, y, z - 1);
-                if (sz >= 0) {
-                    const long long s[3] = {slot_at(a, x + 1, y, z - 1), slot_at(a, x, y + 1, z - 1), slot};
-                    const float tv = tv_term<W>(a, q, a.master[sz * W + q], s, d);
-                    acc = acc + d[2] / tv;
-                }
-                a.grad[at] = a.grad[at] + w * acc;       // the one add
-            }
+            tv0 = tv_column<W>(a.master, a.grad, a.eps, w, slot, q,
+                               [&](int dx, int dy, int dz) { return slot_at(a, x + dx, y + dy, z + dz); });
         }
     }
-    if (a.tv_out) {                                      // the same for every lane of the launch
-        terms[t] = tv0;
-        __syncthreads();
-        if (valid && q == 0) {
-            double sum = 0.0;
-            for (int j = 1; j < W; ++j) sum += (double)terms[t + j];
-            a.tv_out[slot * 2] = tv0;
-            a.tv_out[slot * 2 + 1] = (float)sum;
-        }
-    }
+    if (a.tv_out) tv_store<W>(terms, t, valid && q == 0, tv0, a.tv_out, slot);      // the same for every lane of the launch
 }
 
 template <int W>
@@ -123,17 +79,6 @@ struct ResampleArgs {
     float threshold;
 };
 
-// a (1 - f) + b f, every operation rounded on its own: f = 0 gives a and f = 1 gives b exactly
-__device__ __forceinline__ float lerp(float a, float b, float f) { return __fadd_rn(__fmul_rn(a, __fsub_rn(1.f, f)), __fmul_rn(b, f)); }
-
-// where the new index i of an axis with rn points lies among the r old points: the old cell and the position inside it
-__device__ __forceinline__ void place(int i, int r, int rn, int& cell, float& f) {
-    const double u = (double)i * (double)(r - 1) / (double)(rn - 1);
-    const int fl = (int)floor(u);
-    cell = fl < r - 2 ? fl : r - 2;
-    f = (float)(u - (double)cell);
-}
-
 __global__ __launch_bounds__(kBlock) void baked_resample_kernel(ResampleArgs a) {
     const long long idx = (long long)blockIdx.x * kBlock + threadIdx.x;
     if (idx >= a.n_new * a.nch) return;
@@ -147,38 +92,13 @@ __global__ __launch_bounds__(kBlock) void baked_resample_kernel(ResampleArgs a) 
     place(i, a.R[0], a.Rn[0], cx, fx);
     place(j, a.R[1], a.Rn[1], cy, fy);
     place(k, a.R[2], a.Rn[2], cz, fz);
-    float plane[2][8], sig_plane[2];                     // per x corner: the chunk's 8 values (and sigma) after the z and y steps
+    uint4 old[8];                                        // the chunk of the 8 surrounding old records
 #pragma unroll
-    for (int dx = 0; dx < 2; ++dx) {
-        float line[2][8], sig_line[2];
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy) {
-            const long long pt = ((long long)(cx + dx) * a.R[1] + (cy + dy)) * a.R[2] + cz;
-            const uint4 lo = a.src[pt * a.nch + qc], hi = a.src[(pt + 1) * a.nch + qc];
-            const unsigned wl[4] = {lo.x, lo.y, lo.z, lo.w}, wh[4] = {hi.x, hi.y, hi.z, hi.w};
-            sig_line[dy] = lerp(__uint_as_float(wl[0]), __uint_as_float(wh[0]), fz);
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                line[dy][s] = lerp(half_bits_to_float(wl[s >> 1] >> ((s & 1) * 16)), half_bits_to_float(wh[s >> 1] >> ((s & 1) * 16)), fz);
-            }
-        }
-        sig_plane[dx] = lerp(sig_line[0], sig_line[1], fy);
-#pragma unroll
-        for (int s = 0; s < 8; ++s) plane[dx][s] = lerp(line[0][s], line[1][s], fy);
+    for (int cn = 0; cn < 8; ++cn) {
+        const long long pt = ((long long)(cx + (cn >> 2)) * a.R[1] + (cy + ((cn >> 1) & 1))) * a.R[2] + (cz + (cn & 1));
+        old[cn] = a.src[pt * a.nch + qc];
     }
-    unsigned h[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) {
-        const int e = 8 * qc - 2 + s;
-        h[s] = (e >= 0 && e < 3 * a.K) ? float_to_half_bits(lerp(plane[0][s], plane[1][s], fx)) : 0u;
-    }
-    const float sig = lerp(sig_plane[0], sig_plane[1], fx);
-    uint4 out;
-    out.x = qc == 0 ? __float_as_uint(sig > a.threshold ? sig : 0.f) : (h[0] | (h[1] << 16));
-    out.y = h[2] | (h[3] << 16);
-    out.z = h[4] | (h[5] << 16);
-    out.w = h[6] | (h[7] << 16);
-    a.dst[idx] = out;
+    a.dst[idx] = resample_chunk(old, qc, a.K, fx, fy, fz, a.threshold);
 }
 
 }  // namespace baked_grow
@@ -195,8 +115,7 @@ extern "C" int knerf_baked_train_tv(void* stream, const knerf_baked_train* train
     if (!baked::check_lattice(train->field.resolution, train->field.lo, train->field.hi, train->field.sh_degree, nullptr, points))
         return KNERF_ERR_INVALID;
     if (train->n_slots < 1 || train->n_slots > points) return KNERF_ERR_INVALID;
-    if (!(epsilon > 0.f) || !std::isfinite(epsilon)) return KNERF_ERR_INVALID;
-    if (!(weight_sigma >= 0.f) || !std::isfinite(weight_sigma) || !(weight_sh >= 0.f) || !std::isfinite(weight_sh)) return KNERF_ERR_INVALID;
+    if (!baked_grow::check_tv(weight_sigma, weight_sh, epsilon)) return KNERF_ERR_INVALID;
     if (weight_sigma == 0.f && weight_sh == 0.f && !tv_out) return KNERF_OK;      // nothing to add, nothing to report
     baked_grow::TvArgs a{};
     a.slot_of = train->slot_of; a.point_of = point_of; a.master = master; a.grad = train->grad; a.tv_out = tv_out;
