@@ -543,6 +543,35 @@ typedef struct knerf_baked_train {
 int knerf_baked_train_rays(void* stream, const knerf_baked_train* train, const float* origins, const float* directions, const float* near,
                            const float* far, float near_all, float far_all, const float* target, uint64_t n_rays, uint64_t n_norm,
                            float step, float termination, int flags, float* sq_err);
+/* knerf_baked_train_rays_ext -- extension, no reference counterpart.  knerf_baked_train_rays under the objective record of the train
+ * step (knerf_objective above; its `nets` field is IGNORED here: a grid has no coarse / fine pair): the robust losses and the two
+ * regularisers of a ray's weights, for a grid.  Per ray, over the samples the march fetches, in march order, up to and including the
+ * sample behind which a termination cut falls: w_j, O = sum w_j, C, pre = C + bg (1 - O), out = clip(pre, 0, 1), d_c = out_c - target_c as
+ * above; delta = step |d|, the length of every fetched sample's interval; m_j = (i_j - i_first) delta, i_j the sample's index on the ray
+ * and i_first that of the ray's first fetched sample (D is shift-invariant; samples that are skipped never enter).  With N = n_norm
+ * (0: n_rays) the launch ADDS to grad the gradient of
+ *   L = 1 / (3 N) sum_rays sum_c rho(d_c) + (distortion / N) sum_rays D + (opacity_entropy / N) sum_rays H
+ *   rho: the four kinds of KNERF_LOSS_* as defined above; g_c = rho'(d_c) / (3 N) [0 <= pre_c <= 1]
+ *   D = sum_i sum_j w_i w_j |m_i - m_j| + delta / 3 sum_i w_i^2, evaluated with the exclusive prefixes W_k = sum_{j<k} w_j,
+ *       M_k = sum_{j<k} w_j m_j and MT = sum w m:   D = 2 sum_k w_k (m_k W_k - M_k) + delta / 3 sum_k w_k^2,
+ *       dD/dw_k = 2 (2 m_k W_k - 2 M_k + MT - m_k O) + 2/3 delta w_k,   sum_k w_k dD/dw_k = 2 D
+ *   H = -a ln a - (1 - a) ln(1 - a), a = clamp(O, 1e-4, 1 - 1e-4);  dH/dw_k = ln((1 - a) / a) where 1e-4 <= O <= 1 - 1e-4, else 0
+ *   A_j = sum_c g_c (col_jc - bg) + (distortion / N) dD/dw_j + (opacity_entropy / N) dH/dw_j
+ *   grad[n][sigma] += tau_n delta (T_{j+1} A_j - sum_{i>j} w_i A_i),   the coefficient columns as above with the new g_c.
+ * The regularisers are functions of the weights alone: they pass neither clamp, so a ray whose g is 0 on every channel still adds their
+ * gradient.  The termination cut stays fixed; t, step and the sample positions carry no gradient.  The photometric share of the sum over
+ * later samples is the plain kernel's (exactly 0 at a ray's last sample); the regularisers' share is their total (wd 2 D + we dH O) minus
+ * a running prefix and carries the total's rounding.
+ * objective == NULL, or KNERF_LOSS_MSE with both weights 0: the call IS knerf_baked_train_rays -- the same kernel, the same bits -- and
+ * `terms` is left untouched.  Otherwise the extended kernel runs (one per degree, lane variant and storage; kind and weights are run-time
+ * values) and terms, fp32 [n_rays][4] or NULL, receives per ray (sum_c rho(d_c), sum_c d_c^2, D, H) by plain stores; a ray without a
+ * fetched sample stores D = 0 and H = H(1e-4).  sq_err as above.
+ * KNERF_ERR_INVALID, before any launch: everything knerf_baked_train_rays refuses; an unknown loss_kind; huber_delta <= 0 or not finite
+ * under KNERF_LOSS_HUBER; a weight that is negative or not finite. */
+int knerf_baked_train_rays_ext(void* stream, const knerf_baked_train* train, const float* origins, const float* directions,
+                               const float* near, const float* far, float near_all, float far_all, const float* target, uint64_t n_rays,
+                               uint64_t n_norm, float step, float termination, int flags, float* sq_err,
+                               const knerf_objective* objective, float* terms);
 /* knerf_baked_train_apply -- extension, no reference counterpart.  One Adam step over all slots and the records rewritten.
  * point_of: int32 [n_slots], the lattice point of a slot (the inverse of slot_of); sigma_trainable: uint8 [n_slots]; master, m, v:
  * fp32 [n_slots][1 + 3 K] like grad.  Per column, Keras form: m += (g - m)(1 - beta_1), v += (g g - v)(1 - beta_2),
@@ -651,6 +680,15 @@ typedef struct knerf_baked_bricks_train {
 int knerf_baked_bricks_train_rays(void* stream, const knerf_baked_bricks_train* train, const float* origins, const float* directions,
                                   const float* near, const float* far, float near_all, float far_all, const float* target,
                                   uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags, float* sq_err);
+/* knerf_baked_bricks_train_rays_ext -- extension, no reference counterpart.  knerf_baked_train_rays_ext through the brick table: the same
+ * objective, marches, per-ray terms and refusals (`nets` ignored; objective NULL or plain: the call IS knerf_baked_bricks_train_rays and
+ * `terms` is left untouched), a corner's address formed as in knerf_baked_bricks_train_rays.  For a brick set that holds every corner of
+ * every support cell, gradient addends and terms are those of knerf_baked_train_rays_ext on the dense field, bit for bit.
+ * KNERF_ERR_INVALID, before any launch: everything knerf_baked_bricks_train_rays and knerf_baked_train_rays_ext refuse. */
+int knerf_baked_bricks_train_rays_ext(void* stream, const knerf_baked_bricks_train* train, const float* origins, const float* directions,
+                                      const float* near, const float* far, float near_all, float far_all, const float* target,
+                                      uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags, float* sq_err,
+                                      const knerf_objective* objective, float* terms);
 /* knerf_baked_bricks_train_apply -- extension, no reference counterpart.  knerf_baked_train_apply over the stored records: the same Adam
  * step, projection, record rewrite (fp32 sigma, coefficients to fp16 to nearest even, zero padding) and zeroing of the gradient row.
  * flags: uint8 [n_bricks b^3]; bit 0: the record is a slot (a corner of a support cell), bit 1: its sigma is trainable.  A record without

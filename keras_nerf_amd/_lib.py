@@ -151,6 +151,8 @@ SIGNATURES = {
                                      C.c_float, C.c_int, _F, _F, _F, _P]),
     "knerf_baked_train_rays": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _F, _F, _F, _F, C.c_float, C.c_float, _F, C.c_uint64, C.c_uint64,
                                          C.c_float, C.c_float, C.c_int, _F]),
+    "knerf_baked_train_rays_ext": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _F, _F, _F, _F, C.c_float, C.c_float, _F, C.c_uint64,
+                                             C.c_uint64, C.c_float, C.c_float, C.c_int, _F, C.POINTER(KnerfObjective), _F]),
     "knerf_baked_train_apply": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _P, _P, _F, _F, _F, C.c_float, C.c_float, C.c_float, C.c_float,
                                           C.c_float]),
     "knerf_baked_train_tv": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _P, _F, C.c_float, C.c_float, C.c_float, _F]),
@@ -159,6 +161,9 @@ SIGNATURES = {
                                             C.c_float, C.c_int, _F, _F, _F, _P]),
     "knerf_baked_bricks_train_rays": (C.c_int, [_P, C.POINTER(KnerfBakedBricksTrain), _F, _F, _F, _F, C.c_float, C.c_float, _F, C.c_uint64,
                                                 C.c_uint64, C.c_float, C.c_float, C.c_int, _F]),
+    "knerf_baked_bricks_train_rays_ext": (C.c_int, [_P, C.POINTER(KnerfBakedBricksTrain), _F, _F, _F, _F, C.c_float, C.c_float, _F,
+                                                    C.c_uint64, C.c_uint64, C.c_float, C.c_float, C.c_int, _F,
+                                                    C.POINTER(KnerfObjective), _F]),
     "knerf_baked_bricks_train_apply": (C.c_int, [_P, C.POINTER(KnerfBakedBricksTrain), _P, _F, _F, _F, C.c_float, C.c_float, C.c_float,
                                                  C.c_float, C.c_float]),
     "knerf_baked_resample_bricks_sigma": (C.c_int, [_P, C.POINTER(KnerfBakedBricks), C.POINTER(C.c_int32), C.c_float, _F]),

@@ -498,16 +498,20 @@ class BakedField:
 
     # ---- optimisation against ray batches
     def optimizer(self, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
-                  white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6):
+                  white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6, loss=None,
+                  regularizers=None):
         """A BakedFieldOptimizer (baked_train.py) over a COPY of this field's records: Adam on sigma and the SH coefficients of the
         lattice points around the occupied cells (grown by `dilation` cells) against batches of rays and their colours; this field
         itself is left as it is.  step, white_background, termination, lanes_per_ray: how the optimiser marches, as in render().
         tv_sigma, tv_sh (>= 0, default off): the weights of the total-variation regulariser on density and on the colour coefficients
         (knerf_baked_train_tv; each is the weight of the MEAN term over the slots, resp. over the slots and the 3 K coefficient
-        columns), tv_epsilon (> 0) the constant under its root.  With both weights 0 a step is what it is without them."""
+        columns), tv_epsilon (> 0) the constant under its root.  With both weights 0 a step is what it is without them.
+        loss, regularizers: the objective, as NeRF.compile takes it (a name, a keras_nerf_amd.losses class, a Keras loss object or its
+        serialised dict; losses.RayRegularizers(distortion=, opacity_entropy=) with the default nets): knerf_baked_train_rays_ext.
+        Default, and "mse" without a regulariser: the mean squared error, the launches and bits of an optimiser without them."""
         from .baked_train import BakedFieldOptimizer
         return BakedFieldOptimizer(self, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
-                                   termination, lanes_per_ray, tv_sigma, tv_sh, tv_epsilon)
+                                   termination, lanes_per_ray, tv_sigma, tv_sh, tv_epsilon, loss, regularizers)
 
     # ---- how the objective moves when a ray moves (baked_pose.py: refining camera poses)
     def ray_gradients(self, origins, directions, near, far, target, step=None, white_background=False, termination=0.0, n_total=None,

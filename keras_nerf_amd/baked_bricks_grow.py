@@ -20,7 +20,7 @@ import numpy as np
 from .baked import (BakedField, BrickBakedField, _brick_points_device, _brick_slabs, _brick_table_device, _check, _stream, _unpack_words,
                     check_brick, check_lattice_spec, check_table_size, check_threshold, record_bytes)
 from .baked_bricks_train import FLAG_SIGMA, FLAG_SLOT, BrickFieldOptimizer, brick_sigma, train_state
-from .baked_train import check_optimizer_args, check_stages, check_tv_args
+from .baked_train import check_optimizer_args, check_stages, check_tv_args, fit_terms
 
 CARRY_ROWS = 1 << 22          # rows whose columns move in one piece when a prune carries the optimiser's state
 
@@ -124,11 +124,12 @@ class BrickGridTrainer(BrickFieldOptimizer):
     re-supports the trainer on what the field has become and keeps Adam's state where it can."""
 
     def __init__(self, source, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
-                 white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6):
+                 white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6, loss=None,
+                 regularizers=None):
         self.tv_sigma, self.tv_sh, self.tv_epsilon = check_tv_args(tv_sigma, tv_sh, tv_epsilon)
         self.last_regularizer = None                                        # what the latest train_step's regularize() returned
         super().__init__(source, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
-                         termination, lanes_per_ray)
+                         termination, lanes_per_ray, loss, regularizers)
         self._keys = stored_keys(self.field._brick_of)
 
     # ---- the regulariser
@@ -174,14 +175,17 @@ class BrickGridTrainer(BrickFieldOptimizer):
             return super().fit(batches, near, far, steps)
         if steps is not None and (isinstance(steps, bool) or int(steps) != steps or int(steps) < 0):
             raise ValueError(f"steps must be a non-negative integer or None, got {steps!r}")
-        losses, tvs = [], []
+        losses, tvs, terms = [], [], []
         for k, (target, (o, d, _t)) in enumerate(batches):
             if steps is not None and k >= int(steps):
                 break
             losses.append(self.train_step(o, d, near, far, target))
             tvs.append(torch.stack(self.last_regularizer))
+            if self.objective is not None:
+                terms.append(self.objective_terms())
         both = torch.stack(tvs).cpu() if tvs else torch.zeros((0, 2))
-        return {"loss": torch.stack(losses).cpu().tolist() if losses else [], "tv_sigma": both[:, 0].tolist(), "tv_sh": both[:, 1].tolist()}
+        out = {"loss": torch.stack(losses).cpu().tolist() if losses else [], "tv_sigma": both[:, 0].tolist(), "tv_sh": both[:, 1].tolist()}
+        return out if self.objective is None else fit_terms(out, terms)
 
     # ---- going sparse while training
     def counts(self):
@@ -227,13 +231,15 @@ class BrickGridTrainer(BrickFieldOptimizer):
 
 
 def grid_trainer(field, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
-                 white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6):
+                 white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6, loss=None,
+                 regularizers=None):
     """A BrickGridTrainer over a COPY of a BrickBakedField's bricks: baked_train.brick_optimizer with the dense optimiser's
     total-variation keywords (tv_sigma, tv_sh: the weights of mean tv_sigma and mean tv_q, both >= 0; tv_epsilon > 0 under the root) and
-    prune().  With both weights 0 it trains exactly as brick_optimizer's BrickFieldOptimizer does."""
+    prune().  With both weights 0 it trains exactly as brick_optimizer's BrickFieldOptimizer does.  loss, regularizers: the objective, as
+    BakedField.optimizer takes it."""
     _check_brick_field(field, "grid_trainer")
     return BrickGridTrainer(field, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
-                            termination, lanes_per_ray, tv_sigma, tv_sh, tv_epsilon)
+                            termination, lanes_per_ray, tv_sigma, tv_sh, tv_epsilon, loss, regularizers)
 
 
 def check_prune_every(prune_every):

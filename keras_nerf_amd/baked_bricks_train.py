@@ -22,7 +22,8 @@ import numpy as np
 
 from .baked import (BrickBakedField, _brick_points_device, _brick_slabs, _brick_table_device, _check, _ray_args, _stream, _unpack_words,
                     check_render_args, check_table_size, check_threshold, n_coefficients, record_bytes)
-from .baked_train import bias_corrected_rate, check_optimizer_args, check_target_shape
+from .baked_train import (bias_corrected_rate, check_objective, check_optimizer_args, check_target_shape, fit_terms,
+                          objective_value)
 
 # lanes per ray knerf_baked_bricks_train_rays is built for, per degree: every variant of the dense gradient kernel builds without
 # scratch with brick addressing as well (DESIGN.md 2.23 has hipcc's register counts)
@@ -130,10 +131,12 @@ class BrickFieldOptimizer:
     train bricks, its bits are the support, and it can be rendered at any time.  The source field is left as it is."""
 
     def __init__(self, source, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
-                 white_background=False, termination=0.0, lanes_per_ray=0):
+                 white_background=False, termination=0.0, lanes_per_ray=0, loss=None, regularizers=None):
         import torch
         from . import _lib
         from .runtime import occupancy_words_from_grid
+        self.objective = check_objective(loss, regularizers)               # None: the plain objective, the plain entry point
+        self._terms = None                                                  # the last accumulate's means (objective_terms)
         if not isinstance(source, BrickBakedField):
             raise ValueError(f"a brick optimiser is built on a BrickBakedField, got {type(source).__name__} (a BakedField has "
                              f"optimizer(), the dense BakedFieldOptimizer)")
@@ -158,7 +161,8 @@ class BrickFieldOptimizer:
     # ---- the two launches
     def accumulate(self, origins, directions, near, far, target, n_total=None):
         """knerf_baked_bricks_train_rays: adds the gradient of the batch's mean squared error to the gradient rows and returns the
-        loss, a float64 device scalar; n_total as BakedFieldOptimizer.accumulate"""
+        loss, a float64 device scalar; n_total as BakedFieldOptimizer.accumulate.  Under an objective that is not the plain one:
+        knerf_baked_bricks_train_rays_ext and the objective's value, as there"""
         import torch
         from . import _lib
         from .runtime import _f32, _ptr
@@ -172,11 +176,24 @@ class BrickFieldOptimizer:
         sq = torch.empty((n,), device=f.device, dtype=torch.float32)
         flags = (_lib.BAKED_WHITE_BACKGROUND if self.white_background else 0) | _lib.BAKED_SKIP_EMPTY | \
             (self.lanes_per_ray << _lib.BAKED_LANES_SHIFT)
+        if self.objective is not None:
+            terms = torch.zeros((n, 4), device=f.device, dtype=torch.float32)
+            if n:
+                _check(_lib.load().knerf_baked_bricks_train_rays_ext(_stream(f.device), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t),
+                                                                     _ptr(far_t), near0, far0, _ptr(tg), n, norm, h, self.termination,
+                                                                     flags, _ptr(sq), C.byref(self.objective), _ptr(terms)),
+                       "knerf_baked_bricks_train_rays_ext")
+            loss, self._terms = objective_value(self.objective, terms, norm)
+            return loss
         if n:
             _check(_lib.load().knerf_baked_bricks_train_rays(_stream(f.device), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t),
                                                              _ptr(far_t), near0, far0, _ptr(tg), n, norm, h, self.termination, flags,
                                                              _ptr(sq)), "knerf_baked_bricks_train_rays")
         return sq.to(torch.float64).sum() / (3.0 * max(norm, 1))
+
+    def objective_terms(self):
+        """BakedFieldOptimizer.objective_terms: the four means of the last accumulate(), None under the plain objective"""
+        return None if self._terms is None else dict(self._terms)
 
     def apply(self):
         """knerf_baked_bricks_train_apply: one Adam step from the accumulated gradient, the slots' records rewritten, their gradient
@@ -199,16 +216,20 @@ class BrickFieldOptimizer:
 
     def fit(self, batches, near, far, steps=None):
         """train_step on every batch of `batches` (each (target [n,3], (origins, directions, t)) as RayBatchDataset yields them), at
-        most `steps` of them.  {"loss": [...]}: read from the device once, after the last step."""
+        most `steps` of them.  {"loss": [...]}: read from the device once, after the last step; under an objective that is not the
+        plain one also the four lists of objective_terms()."""
         import torch
         if steps is not None and (isinstance(steps, bool) or int(steps) != steps or int(steps) < 0):
             raise ValueError(f"steps must be a non-negative integer or None, got {steps!r}")
-        losses = []
+        losses, terms = [], []
         for k, (target, (o, d, _t)) in enumerate(batches):
             if steps is not None and k >= int(steps):
                 break
             losses.append(self.train_step(o, d, near, far, target))
-        return {"loss": torch.stack(losses).cpu().tolist() if losses else []}
+            if self.objective is not None:
+                terms.append(self.objective_terms())
+        out = {"loss": torch.stack(losses).cpu().tolist() if losses else []}
+        return out if self.objective is None else fit_terms(out, terms)
 
     # ---- views for tests and tools
     def _dense(self, per_record, dtype):

@@ -262,6 +262,8 @@ def fit_with_poses(opt, pose_opt, batches, near, far, steps=None, field_steps_fi
     against `field` (a BakedField or BrickBakedField, frozen) marched with **march (step, white_background, termination,
     lanes_per_ray as field.ray_gradients takes them).  field_steps_first: that many first steps move the field alone, so that it
     settles before the cameras do.  steps: at most that many batches (None: all of them).
+    An optimiser built with loss= / regularizers= uses that objective for the FIELD step only: the pose gradient (ray_gradients) stays
+    that of the mean squared error.
     Returns {"loss": [...]} (the data term before each step), read from the device once, after the last step.  NDC rays (batches
     whose ray_model() says so) raise ValueError before the first launch.  The dataset keeps the provider afterwards: its next batches
     are drawn with the refined poses (set_cameras(None) gives the stored ones back)."""

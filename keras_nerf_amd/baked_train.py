@@ -5,6 +5,8 @@ The arithmetic is HIP (csrc/baked_train.hip: knerf_baked_train_rays marches a ba
 gradient into the lattice; knerf_baked_train_apply is Adam and rewrites the records; csrc/baked_grow.hip: knerf_baked_train_tv, the
 optional total-variation regulariser between the two, and the resampling behind fit_coarse_to_fine; include/knerf.h holds the contract).  torch is
 used for device memory, streams and the index plumbing of the construction only.  No step waits for the GPU.
+With loss= / regularizers= (the objective of NeRF.compile: keras_nerf_amd/losses.py) the gradient launch is knerf_baked_train_rays_ext,
+the same march under a robust loss and the distortion / opacity-entropy regularisers of a ray's weights.
 
 What keeps skipping empty cells exact while the numbers move:
   support    the field's occupancy bits at the start, grown by `dilation` cells, fixed for the optimiser's lifetime: the bits of every
@@ -64,6 +66,44 @@ def check_target_shape(shape, n_rays) -> None:
         raise ValueError(f"target must be [{n_rays}, 3], one colour per ray; got {tuple(shape)}")
 
 
+def check_objective(loss, regularizers):
+    """The knerf_objective record of a grid optimiser's `loss=` / `regularizers=` keywords (losses.objective_from: every spelling
+    NeRF.compile takes), or None for the plain objective (mean squared error, both weights 0): the optimiser then calls the plain entry
+    point.  ValueError, before any device work, for what losses refuses and for a RayRegularizers whose nets is not the default: a grid
+    has no coarse / fine pair."""
+    from . import losses
+    r = losses.regularizers_from(regularizers)
+    if r.nets != "both":
+        raise ValueError(f"RayRegularizers nets={r.nets!r}: a baked field has no coarse / fine pair, leave nets at its default")
+    obj = losses.objective_from(loss, r)
+    return None if losses.is_plain(obj) else obj
+
+
+TERM_NAMES = ("photometric", "mse", "distortion", "opacity_entropy")
+
+
+def objective_value(obj, terms, norm):
+    """(loss, {name: mean}) from the per-ray terms [n, 4] of an extended launch, float64 device scalars: the terms are summed in float64
+    on the device; photometric and mse are means over rays and channels, distortion and opacity_entropy over rays (N = norm); loss =
+    photometric + distortion weight x mean D + opacity_entropy weight x mean H, the function whose gradient the launch added."""
+    import torch
+    total = terms.to(torch.float64).sum(dim=0)
+    n = float(max(norm, 1))
+    means = {"photometric": total[0] / (3.0 * n), "mse": total[1] / (3.0 * n), "distortion": total[2] / n,
+             "opacity_entropy": total[3] / n}
+    loss = means["photometric"] + float(obj.distortion) * means["distortion"] + float(obj.opacity_entropy) * means["opacity_entropy"]
+    return loss, means
+
+
+def fit_terms(out, rows):
+    """adds the four lists of TERM_NAMES to a fit() dict from the per-step objective_terms() (one device read)"""
+    import torch
+    both = torch.stack([torch.stack([r[k] for k in TERM_NAMES]) for r in rows]).cpu() if rows else torch.zeros((0, 4))
+    for i, k in enumerate(TERM_NAMES):
+        out[k] = both[:, i].tolist()
+    return out
+
+
 def bias_corrected_rate(learning_rate: float, beta_1: float, beta_2: float, t: int) -> float:
     """Keras-form Adam: learning_rate sqrt(1 - beta_2^t) / (1 - beta_1^t) in double, t the step being applied (from 1)"""
     return float(learning_rate) * float(np.sqrt(1.0 - float(beta_2) ** t)) / (1.0 - float(beta_1) ** t)
@@ -74,13 +114,16 @@ class BakedFieldOptimizer:
     optimiser rewrites, its bits are the support, and it can be rendered at any time."""
 
     def __init__(self, source, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
-                 white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6):
+                 white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6, loss=None,
+                 regularizers=None):
         import torch
         from . import _lib
         from .runtime import occupancy_words_from_grid
         self.learning_rate_sigma, self.learning_rate_sh, self.beta_1, self.beta_2, self.epsilon, self.dilation = \
             check_optimizer_args(learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation)
         self.tv_sigma, self.tv_sh, self.tv_epsilon = check_tv_args(tv_sigma, tv_sh, tv_epsilon)
+        self.objective = check_objective(loss, regularizers)               # None: the plain objective, the plain entry point
+        self._terms = None                                                  # the last accumulate's means (objective_terms)
         self.last_regularizer = None                                        # what the latest train_step's regularize() returned
         check_render_args(step, termination, ("image",), source.sh_degree, lanes_per_ray)
         self.step, self.white_background, self.termination, self.lanes_per_ray = step, bool(white_background), float(termination), \
@@ -124,7 +167,10 @@ class BakedFieldOptimizer:
     def accumulate(self, origins, directions, near, far, target, n_total=None):
         """knerf_baked_train_rays: adds the gradient of the batch's mean squared error to the gradient rows and returns the loss, a
         float64 device scalar (the per-ray errors are summed in float64 on the device; nothing waits).  n_total: the N of the loss
-        1 / (3 N) sum (out - target)^2 when the batch is one part of several accumulated before apply() (default: this batch's rays)."""
+        1 / (3 N) sum (out - target)^2 when the batch is one part of several accumulated before apply() (default: this batch's rays).
+        With a loss= / regularizers= objective that is not the plain one: knerf_baked_train_rays_ext, and the value returned is that
+        of the function whose gradient was added, the mean of rho plus distortion x mean D plus opacity_entropy x mean H (the per-ray
+        terms summed in float64 on the device); objective_terms() then gives the four means."""
         import torch
         from . import _lib
         from .runtime import _f32, _ptr
@@ -138,11 +184,26 @@ class BakedFieldOptimizer:
         sq = torch.empty((n,), device=f.device, dtype=torch.float32)
         flags = (_lib.BAKED_WHITE_BACKGROUND if self.white_background else 0) | _lib.BAKED_SKIP_EMPTY | \
             (self.lanes_per_ray << _lib.BAKED_LANES_SHIFT)
+        if self.objective is not None:
+            terms = torch.zeros((n, 4), device=f.device, dtype=torch.float32)
+            if n:
+                _check(_lib.load().knerf_baked_train_rays_ext(_stream(f.device), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t),
+                                                              _ptr(far_t), near0, far0, _ptr(tg), n, norm, h, self.termination, flags,
+                                                              _ptr(sq), C.byref(self.objective), _ptr(terms)),
+                       "knerf_baked_train_rays_ext")
+            loss, self._terms = objective_value(self.objective, terms, norm)
+            return loss
         if n:
             _check(_lib.load().knerf_baked_train_rays(_stream(f.device), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t), _ptr(far_t),
                                                       near0, far0, _ptr(tg), n, norm, h, self.termination, flags, _ptr(sq)),
                    "knerf_baked_train_rays")
         return sq.to(torch.float64).sum() / (3.0 * max(norm, 1))
+
+    def objective_terms(self):
+        """{"photometric", "mse", "distortion", "opacity_entropy"}: the four means of the last accumulate() as float64 device scalars
+        (photometric: the mean of rho over rays and channels; mse: of the squared difference; the other two: mean D and mean H over
+        the rays, unweighted).  None before any accumulate(), and always under the plain objective."""
+        return None if self._terms is None else dict(self._terms)
 
     def apply(self):
         """knerf_baked_train_apply: one Adam step from the accumulated gradient, the records rewritten, the gradient zeroed"""
@@ -193,21 +254,26 @@ class BakedFieldOptimizer:
         """train_step on every batch of `batches` (each (target [n,3], (origins, directions, t)) as RayBatchDataset yields them; t is
         not used: the baked march places its own samples), at most `steps` of them.  {"loss": [...]}: read from the device once, after
         the last step.  With a total-variation weight > 0 the dict also holds "tv_sigma" and "tv_sh": regularize()'s two means per
-        step."""
+        step; with an objective that is not the plain one also "photometric", "mse", "distortion" and "opacity_entropy":
+        objective_terms() per step."""
         import torch
         if steps is not None and (isinstance(steps, bool) or int(steps) != steps or int(steps) < 0):
             raise ValueError(f"steps must be a non-negative integer or None, got {steps!r}")
-        losses, tvs = [], []
+        losses, tvs, terms = [], [], []
         for k, (target, (o, d, _t)) in enumerate(batches):
             if steps is not None and k >= int(steps):
                 break
             losses.append(self.train_step(o, d, near, far, target))
             if self.regularized:
                 tvs.append(torch.stack(self.last_regularizer))
+            if self.objective is not None:
+                terms.append(self.objective_terms())
         out = {"loss": torch.stack(losses).cpu().tolist() if losses else []}
         if self.regularized:
             both = torch.stack(tvs).cpu() if tvs else torch.zeros((0, 2))
             out["tv_sigma"], out["tv_sh"] = both[:, 0].tolist(), both[:, 1].tolist()
+        if self.objective is not None:
+            fit_terms(out, terms)
         return out
 
     # ---- views for tests and tools
@@ -251,17 +317,18 @@ class BakedFieldOptimizer:
 
 
 def brick_optimizer(field, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
-                    white_background=False, termination=0.0, lanes_per_ray=0):
+                    white_background=False, termination=0.0, lanes_per_ray=0, loss=None, regularizers=None):
     """A BrickFieldOptimizer (baked_bricks_train.py) over a COPY of a BrickBakedField's bricks: BakedField.optimizer for a field
     stored as sparse bricks, with the same arguments and meaning, optimised as it is (no table of the dense lattice's size is formed;
     finish() gives a BrickBakedField).  There is no total-variation regulariser here: tv_sigma, tv_sh and tv_epsilon belong to the
-    dense optimiser and, on bricks, to baked_bricks_grow.grid_trainer, beside resample_bricks and fit_coarse_to_fine_bricks."""
+    dense optimiser and, on bricks, to baked_bricks_grow.grid_trainer, beside resample_bricks and fit_coarse_to_fine_bricks.
+    loss, regularizers: the objective, as BakedField.optimizer takes it (knerf_baked_bricks_train_rays_ext)."""
     from .baked_bricks_train import BrickFieldOptimizer
     from .baked_quant import QuantizedBrickField
     if isinstance(field, QuantizedBrickField):
         raise ValueError("a brick optimiser is built on a BrickBakedField, got a QuantizedBrickField: dequantize() gives one")
     return BrickFieldOptimizer(field, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
-                               termination, lanes_per_ray)
+                               termination, lanes_per_ray, loss, regularizers)
 
 
 def __getattr__(name):
@@ -293,14 +360,14 @@ def check_stages(stages):
 def fit_coarse_to_fine(field, batches, near, far, stages, **optimizer_kwargs):
     """Coarse-to-fine optimisation of a baked field: for every stage (resolution | None, steps) in turn the field is resampled onto
     `resolution` (BakedField.resample; None keeps the lattice), an optimiser is built on it (field.optimizer(**optimizer_kwargs):
-    learning rates, dilation, march and total-variation keywords), fit for `steps` batches and finished (finish()).  `batches` is
+    learning rates, dilation, march, total-variation and objective (loss=, regularizers=) keywords), fit for `steps` batches and finished (finish()).  `batches` is
     consumed continuously: a stage goes on where the one before stopped, and no batch is dropped in between.
 
     Adam's moments are NOT carried across stages.  A resample changes the lattice, the support and with them the set of slots, so
     every stage gets a new slot set and a fresh optimiser whose moments start at zero and whose bias correction starts at t = 1.
 
-    Returns (the finished field of the last stage, history): history["loss"] (and "tv_sigma", "tv_sh" when a weight is > 0) run over
-    all stages, history["stages"] holds one {"resolution", "steps", "n_slots"} per stage (steps: those actually run)."""
+    Returns (the finished field of the last stage, history): history["loss"] (and "tv_sigma", "tv_sh" when a weight is > 0, and the four
+    lists of objective_terms() under an objective that is not the plain one) run over all stages, history["stages"] holds one {"resolution", "steps", "n_slots"} per stage (steps: those actually run)."""
     import itertools
     todo = check_stages(stages)
     it = iter(batches)

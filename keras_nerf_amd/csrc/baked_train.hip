@@ -22,6 +22,13 @@
 //                             NOTHING is added for it, so a damaged table never becomes an out-of-range read or write.  There is no slot
 //                             table: the rows of gradient, master value and moments are per STORED RECORD, and a row's index is the
 //                             record's index.
+//                             Args::kExt (Ext<TrainArgs>, Ext<BrickTrainArgs>): the same march and kernel under the objective record of
+//                             knerf_baked_train_rays_ext -- the robust losses and the distortion / opacity-entropy regularisers of a
+//                             ray's weights.  The first march also keeps the prefix sums D needs, the second forms
+//                             r_j = wd dD/dw_j + we dH/dw, adds it to A_j and takes the later samples' share as total minus a running
+//                             prefix; the early exit of a ray with g = 0 holds only where no regulariser has a gradient.  Every line
+//                             of it stands under `if constexpr`: the plain instantiations are instruction for instruction what they
+//                             were.  tests/baked_objective_reference.py restates it in fp64.
 //   Gradient rows: fp32 [n_slots][1 + 3 K], sigma first, then [k][c]: the columns of a record.  Every lane of a group holds the whole
 //   basis and the same dL/dr and dL/dsigma, so any lane can form any column: lane `sub` adds the columns sub, sub + G, ... of a
 //   corner's row, so that ONE atomic instruction of the group adds G consecutive floats (the memory side works in 64-byte requests;
@@ -40,7 +47,7 @@ namespace baked_train {
 using namespace baked;
 
 struct TrainArgs {
-    static constexpr bool kBrick = false;
+    static constexpr bool kBrick = false, kExt = false;
     const uint4* rec;
     const unsigned* bits;
     int R[3];
@@ -57,7 +64,7 @@ struct TrainArgs {
 };
 
 struct BrickTrainArgs {
-    static constexpr bool kBrick = true;
+    static constexpr bool kBrick = true, kExt = false;
     const uint4* rec;
     const int* brick_of;
     const unsigned* bits;
@@ -74,6 +81,32 @@ struct BrickTrainArgs {
     float* sq_err;
 };
 
+// The extended objective (knerf_baked_train_rays_ext): the argument struct of a storage with the objective behind it.
+// Args::kExt is the ONE compile-time switch of march and kernel; every line it adds stands under `if constexpr (Args::kExt)`, so the
+// plain instantiations are the text they were.  Kind and weights are run-time values: one extended instantiation per <DEG, G, storage>.
+struct Objective {
+    int kind;                                       // KNERF_LOSS_*
+    float huber_delta;
+    float hscale;                                   // 1 / (3 N): g_c = rho'(d_c) hscale (for mse the bits of diff * gscale)
+    float wd, we;                                   // lambda_d / N, lambda_e / N
+    float* terms;                                   // [n][4] or NULL
+};
+template <class Base>
+struct Ext : Base {
+    static constexpr bool kExt = true;
+    Objective obj;
+};
+
+// kExt: what the regularisers keep per ray, with m_j = (i_j - first) delta and the exclusive prefixes W_k = sum_{j<k} w_j (the march's own
+// opa) and M_k = sum_{j<k} w_j m_j.  First march: M ends as MT, S1 = sum w_k (m_k W_k - M_k), S2 = sum w_k^2, so D = 2 S1 + delta S2 / 3.
+// Second march: M runs again as the prefix, run = sum_{i<=j} w_i r_i, r_j = wd dD/dw_j + re the regularisers' share of A_j; the later
+// samples' share is total - run, total = wd 2 D + re O (D is homogeneous of degree 2 in w, H depends on O alone).
+struct RegState {
+    float M, S1, S2, run;
+    int first;                                      // index of the ray's first fetched sample, -1: none yet
+    float mt, wd, re, total;                        // MT, lambda_d / N, (lambda_e / N) dH/dw, sum_i w_i r_i
+};
+
 // what the second march needs from the first: g = dL/dout (already gated by the output clamp) and the totals
 struct Totals {
     float g[3], img[3], opa, bg;
@@ -87,9 +120,10 @@ __device__ __forceinline__ void march(const Args& a, const float (&o3)[3], const
                                       const float (&wr)[(rec_bytes(DEG) / 16 + G - 1) / G][8],
                                       const float (&wg)[(rec_bytes(DEG) / 16 + G - 1) / G][8],
                                       const float (&wb)[(rec_bytes(DEG) / 16 + G - 1) / G][8],
-                                      const float (&gy)[(1 + 3 * n_coeff(DEG) + G - 1) / G][3], float (&img)[3], float& opa, const Totals& tt) {
+                                      const float (&gy)[(1 + 3 * n_coeff(DEG) + G - 1) / G][3], float (&img)[3], float& opa, const Totals& tt,
+                                      [[maybe_unused]] RegState& rs) {
     constexpr int K = n_coeff(DEG), NCH = rec_bytes(DEG) / 16, CPL = (NCH + G - 1) / G, W = 1 + 3 * K, NI = (W + G - 1) / G;
-    constexpr bool BRICK = Args::kBrick;
+    constexpr bool BRICK = Args::kBrick, EXT = Args::kExt;
     [[maybe_unused]] const long long sy = a.R[2], sx = (long long)a.R[1] * a.R[2];     // dense: the lattice's strides
     const int cyc = a.R[1] - 1, czc = a.R[2] - 1;
     [[maybe_unused]] const int L = brick_log2(a), inm = (1 << L) - 1;
@@ -203,6 +237,17 @@ __device__ __forceinline__ void march(const Args& a, const float (&o3)[3], const
             for (int c = 0; c < 3; ++c) col[c] = fminf(fmaxf(raw[c], 0.f), 1.f);
             const float alpha = 1.f - expf(-(sig * delta));
             const float w = T * alpha;
+            [[maybe_unused]] float mk = 0.f, Wk = 0.f, Mk = 0.f;    // EXT: m_k and the exclusive prefixes W_k, M_k
+            if constexpr (EXT) {
+                if (rs.first < 0) rs.first = i + kk;
+                mk = (float)(i + kk - rs.first) * delta;
+                Wk = opa; Mk = rs.M;
+                if constexpr (!BWD) {
+                    rs.S1 = rs.S1 + w * (mk * Wk - Mk);
+                    rs.S2 = rs.S2 + w * w;
+                }
+                rs.M = Mk + w * mk;
+            }
             img[0] = img[0] + w * col[0]; img[1] = img[1] + w * col[1]; img[2] = img[2] + w * col[2];
             opa = opa + w;
             T = T * (1.f - alpha);
@@ -215,6 +260,14 @@ __device__ __forceinline__ void march(const Args& a, const float (&o3)[3], const
                     A = __builtin_fmaf(tt.g[c], col[c] - tt.bg, A);
                     later = __builtin_fmaf(tt.g[c], (tt.img[c] - img[c]) - tt.bg * rest_o, later);
                     dr[c] = (raw[c] >= 0.f && raw[c] <= 1.f) ? tt.g[c] * w : 0.f;
+                }
+                if constexpr (EXT) {
+                    // the regularisers are functions of the weights alone: they pass neither clamp.  The photometric share of
+                    // `later` above stays what it is (exactly 0 at the last sample); this share carries the rounding of `total`
+                    const float r = rs.wd * (2.f * (2.f * mk * Wk - 2.f * Mk + rs.mt - mk * tt.opa) + (2.f / 3.f) * delta * w) + rs.re;
+                    rs.run = rs.run + w * r;
+                    A = A + r;
+                    later = later + (rs.total - rs.run);
                 }
                 const float dsig = delta * (T * A - later);           // T is T_{j+1} here
                 if (dsig != 0.f || dr[0] != 0.f || dr[1] != 0.f || dr[2] != 0.f) {     // the same on every lane of the group
@@ -254,6 +307,7 @@ __device__ __forceinline__ void march(const Args& a, const float (&o3)[3], const
 template <int DEG, int G, class Args>
 __global__ __launch_bounds__(kBlock) void baked_train_rays_kernel(Args a) {
     constexpr int K = n_coeff(DEG), NCH = rec_bytes(DEG) / 16, CPL = (NCH + G - 1) / G;
+    constexpr bool EXT = Args::kExt;
     static_assert(G == 1 || G == 2 || G == 4, "a group is a lane, a pair or a quad");
     const long long gid = (long long)blockIdx.x * kBlock + threadIdx.x;
     const long long ray = gid / G;
@@ -318,23 +372,89 @@ __global__ __launch_bounds__(kBlock) void baked_train_rays_kernel(Args a) {
     }
     const float delta = a.step * nrm;
     Totals tt{};
-    march<DEG, G, false>(a, o3, d3, near, i0, i1, delta, sub, Y, wr, wg, wb, gy, tt.img, tt.opa, tt);
+    RegState rs{};
+    rs.first = -1;
+    march<DEG, G, false>(a, o3, d3, near, i0, i1, delta, sub, Y, wr, wg, wb, gy, tt.img, tt.opa, tt, rs);
     tt.bg = a.white ? 1.f : 0.f;
     const float bg = a.white ? 1.f - tt.opa : 0.f;          // the render kernel's expression
     float sq = 0.f;
     bool any = false;
+    if constexpr (!EXT) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float pre = tt.img[c] + bg, out = fminf(fmaxf(pre, 0.f), 1.f);
-        const float diff = out - a.target[ray * 3 + c];
-        sq = sq + diff * diff;
-        tt.g[c] = (pre >= 0.f && pre <= 1.f) ? diff * a.gscale : 0.f;
-        any = any || tt.g[c] != 0.f;
+        for (int c = 0; c < 3; ++c) {
+            const float pre = tt.img[c] + bg, out = fminf(fmaxf(pre, 0.f), 1.f);
+            const float diff = out - a.target[ray * 3 + c];
+            sq = sq + diff * diff;
+            tt.g[c] = (pre >= 0.f && pre <= 1.f) ? diff * a.gscale : 0.f;
+            any = any || tt.g[c] != 0.f;
+        }
+        if (sub == 0 && a.sq_err) a.sq_err[ray] = sq;
+    } else {
+        const Objective& ob = a.obj;
+        float diff[3], dv[3], rv[3];
+        bool gate[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float pre = tt.img[c] + bg, out = fminf(fmaxf(pre, 0.f), 1.f);
+            diff[c] = out - a.target[ray * 3 + c];
+            gate[c] = pre >= 0.f && pre <= 1.f;
+            sq = sq + diff[c] * diff[c];
+        }
+        // rho and rho' of the ray's three differences: the kind is the same for every ray of the launch, one uniform branch
+        if (ob.kind == KNERF_LOSS_MAE) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                rv[c] = fabsf(diff[c]);
+                dv[c] = diff[c] > 0.f ? 1.f : (diff[c] < 0.f ? -1.f : 0.f);
+            }
+        } else if (ob.kind == KNERF_LOSS_HUBER) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float ad = fabsf(diff[c]);
+                const bool in = ad <= ob.huber_delta;
+                rv[c] = in ? 0.5f * (diff[c] * diff[c]) : ob.huber_delta * (ad - 0.5f * ob.huber_delta);
+                dv[c] = in ? diff[c] : (diff[c] > 0.f ? ob.huber_delta : -ob.huber_delta);
+            }
+        } else if (ob.kind == KNERF_LOSS_LOG_COSH) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float ad = fabsf(diff[c]);
+                rv[c] = ad + log1pf(expf(-2.f * ad)) - 0.69314718055994531f;
+                dv[c] = tanhf(diff[c]);
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                rv[c] = diff[c] * diff[c];
+                dv[c] = 2.f * diff[c];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            tt.g[c] = gate[c] ? dv[c] * ob.hscale : 0.f;
+            any = any || tt.g[c] != 0.f;
+        }
+        // D, H and what the second march needs of them.  A ray without a fetched sample: D = 0, O = 0, H = H(1e-4)
+        const float D = 2.f * rs.S1 + (delta * (1.f / 3.f)) * rs.S2;
+        const float O = tt.opa, ac = fminf(fmaxf(O, 1e-4f), 1.f - 1e-4f);
+        const float H = -ac * logf(ac) - (1.f - ac) * logf(1.f - ac);
+        const float dH = (O >= 1e-4f && O <= 1.f - 1e-4f) ? logf((1.f - ac) / ac) : 0.f;
+        if (sub == 0) {
+            if (a.sq_err) a.sq_err[ray] = sq;
+            if (ob.terms) {
+                float* tr = ob.terms + ray * 4;
+                tr[0] = (rv[0] + rv[1]) + rv[2]; tr[1] = sq; tr[2] = D; tr[3] = H;
+            }
+        }
+        rs.mt = rs.M; rs.wd = ob.wd; rs.re = ob.we * dH;
+        rs.total = ob.wd * (2.f * D) + rs.re * O;
+        rs.M = 0.f; rs.run = 0.f;
+        // a ray whose g is 0 on every channel still has the regularisers' gradient once it fetched a sample
+        any = any || ((ob.wd > 0.f || ob.we > 0.f) && rs.first >= 0);
     }
-    if (sub == 0 && a.sq_err) a.sq_err[ray] = sq;
     if (!any) return;                                       // the same on every lane of the group
     float img[3], opa;
-    march<DEG, G, true>(a, o3, d3, near, i0, i1, delta, sub, Y, wr, wg, wb, gy, img, opa, tt);
+    march<DEG, G, true>(a, o3, d3, near, i0, i1, delta, sub, Y, wr, wg, wb, gy, img, opa, tt, rs);
 }
 
 template <class Args>
@@ -344,6 +464,36 @@ hipError_t launch_rays(int deg, int lanes, const Args& a, hipStream_t s) {
         hipLaunchKernelGGL((baked_train_rays_kernel<DEG, G, Args>), dim3((unsigned)blocks), dim3(kBlock), 0, s, a);
         return hipGetLastError();
     });
+}
+
+// the gradient launch of either storage: the plain kernel, or with an objective record the extended one
+template <class Args>
+hipError_t launch_rays(int deg, int lanes, const Args& a, const Objective* obj, hipStream_t s) {
+    if (!obj) return launch_rays(deg, lanes, a, s);
+    Ext<Args> e{};
+    static_cast<Args&>(e) = a;
+    e.obj = *obj;
+    return launch_rays(deg, lanes, e, s);
+}
+
+// the objective record of the _ext entry points.  false: KNERF_ERR_INVALID.  plain: NULL, or mse with both weights 0 (the call is then
+// the plain launch).  Otherwise `out` is what the extended kernel takes, with the weights and 1 / (3 N) formed in double
+static bool check_objective(const knerf_objective* o, uint64_t n_rays, uint64_t n_norm, float* terms, bool& plain, Objective& out) {
+    plain = true;
+    if (!o) return true;
+    if (o->loss_kind < KNERF_LOSS_MSE || o->loss_kind > KNERF_LOSS_LOG_COSH) return false;
+    if (o->loss_kind == KNERF_LOSS_HUBER && (!(o->huber_delta > 0.f) || !std::isfinite(o->huber_delta))) return false;
+    if (!(o->distortion >= 0.f) || !std::isfinite(o->distortion)) return false;
+    if (!(o->opacity_entropy >= 0.f) || !std::isfinite(o->opacity_entropy)) return false;
+    plain = o->loss_kind == KNERF_LOSS_MSE && o->distortion == 0.f && o->opacity_entropy == 0.f;
+    const double N = (double)(n_norm ? n_norm : (n_rays ? n_rays : 1));
+    out.kind = o->loss_kind;
+    out.huber_delta = o->loss_kind == KNERF_LOSS_HUBER ? o->huber_delta : 0.f;
+    out.hscale = (float)(1.0 / (3.0 * N));
+    out.wd = (float)((double)o->distortion / N);
+    out.we = (float)((double)o->opacity_entropy / N);
+    out.terms = terms;
+    return true;
 }
 
 struct ApplyArgs {
@@ -480,12 +630,16 @@ static bool check_adam(float rate_sigma, float rate_sh, float beta_1, float beta
 
 using namespace knerf;
 
-extern "C" int knerf_baked_train_rays(void* stream, const knerf_baked_train* train, const float* origins, const float* directions,
-                                      const float* near, const float* far, float near_all, float far_all, const float* target,
-                                      uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags, float* sq_err) {
+// knerf_baked_train_rays (objective = NULL) and knerf_baked_train_rays_ext
+static int train_rays(void* stream, const knerf_baked_train* train, const float* origins, const float* directions, const float* near,
+                      const float* far, float near_all, float far_all, const float* target, uint64_t n_rays, uint64_t n_norm, float step,
+                      float termination, int flags, float* sq_err, const knerf_objective* objective, float* terms) {
     unsigned long long points = 0;
     int lanes = 0;
+    bool plain = true;
+    baked_train::Objective obj{};
     if (!baked_train::check_state(train, points)) return KNERF_ERR_INVALID;
+    if (!baked_train::check_objective(objective, n_rays, n_norm, terms, plain, obj)) return KNERF_ERR_INVALID;
     const knerf_baked_field* field = &train->field;
     const int deg = field->sh_degree;
     if (!baked_train::check_train_rays(deg, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination,
@@ -499,7 +653,22 @@ extern "C" int knerf_baked_train_rays(void* stream, const knerf_baked_train* tra
     a.slot_of = train->slot_of; a.n_slots = (long long)train->n_slots;
     baked_train::set_rays(a, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination, flags,
                           train->grad, sq_err);
-    return baked_train::launch_rays(deg, lanes, a, (hipStream_t)stream) == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
+    return baked_train::launch_rays(deg, lanes, a, plain ? nullptr : &obj, (hipStream_t)stream) == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
+}
+
+extern "C" int knerf_baked_train_rays(void* stream, const knerf_baked_train* train, const float* origins, const float* directions,
+                                      const float* near, const float* far, float near_all, float far_all, const float* target,
+                                      uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags, float* sq_err) {
+    return train_rays(stream, train, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination, flags,
+                      sq_err, nullptr, nullptr);
+}
+
+extern "C" int knerf_baked_train_rays_ext(void* stream, const knerf_baked_train* train, const float* origins, const float* directions,
+                                          const float* near, const float* far, float near_all, float far_all, const float* target,
+                                          uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags, float* sq_err,
+                                          const knerf_objective* objective, float* terms) {
+    return train_rays(stream, train, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination, flags,
+                      sq_err, objective, terms);
 }
 
 extern "C" int knerf_baked_train_apply(void* stream, const knerf_baked_train* train, const int32_t* point_of,
@@ -521,14 +690,18 @@ extern "C" int knerf_baked_train_apply(void* stream, const knerf_baked_train* tr
     return hipGetLastError() == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
 }
 
-extern "C" int knerf_baked_bricks_train_rays(void* stream, const knerf_baked_bricks_train* train, const float* origins,
-                                             const float* directions, const float* near, const float* far, float near_all, float far_all,
-                                             const float* target, uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags,
-                                             float* sq_err) {
+// knerf_baked_bricks_train_rays (objective = NULL) and knerf_baked_bricks_train_rays_ext
+static int bricks_train_rays(void* stream, const knerf_baked_bricks_train* train, const float* origins, const float* directions,
+                             const float* near, const float* far, float near_all, float far_all, const float* target, uint64_t n_rays,
+                             uint64_t n_norm, float step, float termination, int flags, float* sq_err, const knerf_objective* objective,
+                             float* terms) {
     int B[3], lanes = 0;
     unsigned long long n_records = 0;
+    bool plain = true;
+    baked_train::Objective obj{};
     baked_train::BrickTrainArgs a{};
     if (!baked_train::check_state(train, B, a.scale, n_records)) return KNERF_ERR_INVALID;
+    if (!baked_train::check_objective(objective, n_rays, n_norm, terms, plain, obj)) return KNERF_ERR_INVALID;
     const knerf_baked_bricks* field = &train->field;
     const int deg = field->sh_degree;
     // every lane variant of knerf_baked_train_rays exists here too: each builds without scratch (DESIGN.md 2.23 has hipcc's counts)
@@ -541,7 +714,24 @@ extern "C" int knerf_baked_bricks_train_rays(void* stream, const knerf_baked_bri
     a.L = field->brick_log2; a.By = B[1]; a.Bz = B[2]; a.n_bricks = (long long)field->n_bricks;
     baked_train::set_rays(a, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination, flags,
                           train->grad, sq_err);
-    return baked_train::launch_rays(deg, lanes, a, (hipStream_t)stream) == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
+    return baked_train::launch_rays(deg, lanes, a, plain ? nullptr : &obj, (hipStream_t)stream) == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
+}
+
+extern "C" int knerf_baked_bricks_train_rays(void* stream, const knerf_baked_bricks_train* train, const float* origins,
+                                             const float* directions, const float* near, const float* far, float near_all, float far_all,
+                                             const float* target, uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags,
+                                             float* sq_err) {
+    return bricks_train_rays(stream, train, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination,
+                             flags, sq_err, nullptr, nullptr);
+}
+
+extern "C" int knerf_baked_bricks_train_rays_ext(void* stream, const knerf_baked_bricks_train* train, const float* origins,
+                                                 const float* directions, const float* near, const float* far, float near_all,
+                                                 float far_all, const float* target, uint64_t n_rays, uint64_t n_norm, float step,
+                                                 float termination, int flags, float* sq_err, const knerf_objective* objective,
+                                                 float* terms) {
+    return bricks_train_rays(stream, train, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination,
+                             flags, sq_err, objective, terms);
 }
 
 extern "C" int knerf_baked_bricks_train_apply(void* stream, const knerf_baked_bricks_train* train, const uint8_t* flags, float* master,
