@@ -328,7 +328,7 @@ int knerf_draw_ray_batch_ext(knerf_ctx* ctx, void* stream, const float* images, 
  * composite = render_image_depth_chunk (utils.py:16-58): raw [R,S,4] = (r,g,b,sigma), t [R,S] -> image [R,3], depth [R]
  *   or NULL, weights [R,S] or NULL.
  * inverse_cdf = fine_hierarchical_sampling_chunk (utils.py:60-97) with u injected: mid_points [R,n_mid],
- *   weights [R,n_weights], u [R,n_samples] -> out [R,n_samples] (unsorted). */
+ *   weights [R,n_weights], u [R,n_samples] -> out [R,n_samples] (unsorted); 1 <= n_weights <= 4096, n_mid >= 1 and unrelated to it. */
 int knerf_positional_encoding(void* stream, const float* x, long long n_rows, int L, float* out);
 /* ray(t) = o + t d (utils.py:193-194): o, d [R,3], t [R,S] -> out [R,S,3] */
 int knerf_ray_points(void* stream, const float* o, const float* d, const float* t, int n_rays, int n_samples, float* out);
@@ -376,7 +376,10 @@ int knerf_query_grid(knerf_ctx* ctx, void* stream, int net, const int32_t* resol
  * normalised.  Three calls on one caller workspace:
  *   1. workspace NULL: *workspace_bytes = the size needed (rx ry rz <= 2^28);
  *   2. vertices, faces, normals all NULL: classification and scans; counts[0] = V, counts[1] = F (host; synchronises `stream`);
- *   3. the same workspace, grid and threshold: writes vertices [V,3], faces [F,3] (int32), normals [V,3] (each may be NULL). */
+ *   3. the same workspace, grid and threshold: writes vertices [V,3], faces [F,3] (int32), normals [V,3] (each may be NULL).
+ * Non-finite samples stay local: NaN is never > threshold (outside), +inf always is (inside), and the faces follow from that alone.
+ * What the vertices on such a sample's six grid edges hold, and the normals whose gradient stencil (the six neighbours of an edge's
+ * two ends) contains it, is unspecified; every other vertex and normal has the bits it has on the grid without that sample. */
 int knerf_marching_cubes(void* stream, const float* grid, int rx, int ry, int rz, const float* lo, const float* hi, float threshold,
                          void* workspace, size_t* workspace_bytes, int64_t* counts, float* vertices, int32_t* faces, float* normals);
 

@@ -22,7 +22,8 @@ __global__ void posenc_kernel(const float* x, float* out, long long n, int L) {
 }
 
 // NeRFUtils.fine_hierarchical_sampling_chunk (utils.py:60-97) on caller-provided mid-points: unsorted samples.
-// One thread per ray builds the cdf (left to right, like sampler.hip); Nw <= 256 weights, M mid-points.
+// One wave per ray builds the cdf (left to right, like sampler.hip); Nw <= 4096 weights (4 (Nw + 1) floats of dynamic LDS per
+// workgroup: 65,552 bytes at the limit, which gfx950 launches), M mid-points, M unrelated to Nw.
 __global__ void inverse_cdf_kernel(const float* mids, const float* w, const float* u, float* out, int R, int M, int Nw, int Nf,
                                    int oob_clamp) {
     extern __shared__ float sm[];
@@ -83,16 +84,20 @@ __global__ __launch_bounds__(256) void image_metrics_kernel(MetricArgs m) {
         const int wi = idx / ww, wj = idx % ww;
         const float c1 = 0.01f * 0.01f, c2 = 0.03f * 0.03f;
         for (int c = 0; c < m.C; ++c) {
+            // the five window moments of x - pv and y - pv, pv = the window's centre pixel of A: variances and covariance are the same
+            // quantities, but on a flat bright region xx - mx mx no longer cancels four digits of float32 beside c2 = 9e-4
+            const float pv = A[((size_t)(wi + 5) * m.W + (wj + 5)) * m.C + c];
             float mx = 0.f, my = 0.f, xx = 0.f, yy = 0.f, xy = 0.f;
             for (int di = 0; di < 11; ++di)
                 for (int dj = 0; dj < 11; ++dj) {
                     const float w = m.g[di] * m.g[dj];
                     const size_t p = ((size_t)(wi + di) * m.W + (wj + dj)) * m.C + c;
-                    const float x = A[p], y = B[p];
+                    const float x = A[p] - pv, y = B[p] - pv;
                     mx += w * x; my += w * y; xx += w * x * x; yy += w * y * y; xy += w * x * y;
                 }
             const float sxx = xx - mx * mx, syy = yy - my * my, sxy = xy - mx * my;
-            ssum += (2.f * mx * my + c1) / (mx * mx + my * my + c1) * ((2.f * sxy + c2) / (sxx + syy + c2));
+            const float ux = mx + pv, uy = my + pv;                                       // the means themselves, for the luminance term
+            ssum += (2.f * ux * uy + c1) / (ux * ux + uy * uy + c1) * ((2.f * sxy + c2) / (sxx + syy + c2));
         }
     }
     for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < (size_t)m.H * m.W * m.C; p += (size_t)gridDim.x * 256) {

@@ -17,9 +17,10 @@ def _gpu_mc(grid, tau, lo=LO, hi=HI):
     return v.cpu().numpy(), f.cpu().numpy(), n.cpu().numpy()
 
 
-def _same_as_reference(grid, tau, lo=LO, hi=HI):
+def _same_as_reference(grid, tau, lo=LO, hi=HI, ref=None):
+    """ref: M.marching_cubes(grid, tau, lo, hi) where the caller has it already"""
     v, f, n = _gpu_mc(grid, tau, lo, hi)
-    rv, rf, rn = M.marching_cubes(grid, tau, lo, hi)
+    rv, rf, rn = ref if ref is not None else M.marching_cubes(grid, tau, lo, hi)
     assert np.array_equal(f, rf), (f.shape, rf.shape)
     assert v.shape == rv.shape and np.abs(v - rv).max(initial=0) <= 1e-6 * EXT
     assert np.abs(n - rn).max(initial=0) <= 1e-6 * EXT
