@@ -841,6 +841,65 @@ int knerf_baked_render_qbricks(void* stream, const knerf_baked_qbricks* field, c
                                const float* near, const float* far, float near_all, float far_all, uint64_t n_rays, float step,
                                float termination, int flags, float* image, float* depth, float* opacity, int64_t* stats);
 
+/* ---- What a baked field holds at a point.  Extension, no reference counterpart (Plenoxels and PlenOctrees answer point queries on
+ * their grids and export meshes from them).  csrc/baked_query.hip; tests/baked_query_reference.py restates the arithmetic in fp64.
+ * knerf_baked_query / knerf_baked_query_bricks / knerf_baked_query_qbricks -- density, colour along a direction and the density's
+ * gradient of a dense, a brick and an 8-bit brick field at n points.  The evaluation is knerf_baked_render's evaluation of one sample.
+ * query: HOST struct.  The points are EITHER a list, points [n,3] (DEVICE), OR a grid (grid_resolution[3], grid_lo[3], grid_hi[3]: HOST,
+ * all three given, points NULL and n ignored): then n = Rx Ry Rz and point idx = (i Ry + j) Rz + k (C order, z fastest) lies, per axis, at
+ *   __fadd_rn(lo, __fmul_rn((float)idx_axis, step)), step = (hi - lo) / (R - 1) in fp32
+ * as knerf_query_grid places it; no coordinate tensor exists.  The grid's box is independent of the field's box.
+ * Per point p, in fp32:
+ *   CELL.  Per axis u = __fmul_rn(__fsub_rn(p, lo), scale), scale = fp32(cells / (hi - lo)) computed in double, cells = R - 1 (the
+ *   lookup of knerf_baked_render).  The point is inside iff 0 <= u <= cells on every axis; a NaN coordinate is outside.  Outside: sigma,
+ *   rgb and gradient are exactly 0.  Inside: cell = min(floor(u), cells - 1) (a point on the upper face belongs to the last cell),
+ *   f = u - cell.
+ *   DENSITY.  Corners cn = 0..7 with x = bit 2, y = bit 1, z = bit 0; weight w_cn = ((cn&4 ? fx : 1-fx) * (cn&2 ? fy : 1-fy)) *
+ *   (cn&1 ? fz : 1-fz); sigma = the sum in ascending cn of fma(w_cn, sigma_cn, sum).  This is the sample of knerf_baked_render: a
+ *   queried sigma is the sigma the march composites at that position.
+ *   COLOUR (only where rgb is asked for).  Every coefficient is interpolated with the same weights in the same fma order; slots of a
+ *   record that hold no coefficient count as 0 whatever their bits are.  colour_c = sum over k of fma(coeff[k][c], Y_k(d / |d|), sum),
+ *   with one point per lane in ascending e = 3 k + c, clamped to [0, 1].  d is normalised as the render normalises it:
+ *   |d| = sqrt(dx dx + dy dy + dz dz), d / |d| per component.  directions: NULL, one shared [3] (per_point = 0) or [n,3] (per_point =
+ *   1), DEVICE.  A NULL direction, or one whose length is 0 or not finite (a NaN component included), gives the DC term alone:
+ *   colour_c = clamp(Y_0 coeff[0][c]); the bands above 0 do not enter.
+ *   GRADIENT (optional).  The exact gradient of the trilinear sigma inside the located cell, d sigma / d p: per axis a, with b < c the
+ *   other two axes, scale_a * S_a, S_a = the sum over the four corner pairs (lower corner cn with the axis' bit clear, in ascending cn)
+ *   of fma(w_b w_c, sigma_(cn | bit) - sigma_cn, sum), w_b and w_c the one-axis weights above (f or 1 - f), one final multiply by
+ *   scale_a.  The trilinear sigma is not differentiable across cell faces: a point on a face gets the gradient of the cell picked above
+ *   (the cell on its upper side; on the box's upper face the last cell).
+ * Storage.  Bricks: a corner's record is found through brick_of as in knerf_baked_render_bricks (a value < 0 or >= n_bricks reads as a
+ * zero record); dense and bricks of the same field give identical bits.  8-bit bricks: every corner's coefficients are decoded to fp32
+ * before they enter the fma (an exponent byte outside [-24, 9] is clamped into it); with one point per lane the result has the bits of
+ * knerf_baked_query_bricks with one point per lane on the dequantised records.
+ * Lanes per point (bits 8..11 of flags, KNERF_BAKED_LANES_*): 0 = the library's choice, 1 = one point per lane, or the group of the
+ * storage's renderer (dense, bricks: 2 at degree 1, 4 at degrees 2 and 3; 8-bit: 2 at degree 2, 4 at degree 3): a group reads each
+ * corner record as one contiguous fetch of 16-byte chunks and adds its channel sums across lanes; the choices differ in the colour's
+ * summation order only.  No other flag bit exists.
+ * sigma [n], rgb [n,3], gradient [n,3] (DEVICE; in grid mode [Rx,Ry,Rz], [Rx,Ry,Rz,3]): each may be NULL, not all.  Without rgb only the
+ * first word of each corner record is loaded (4 bytes, not the record), directions are not read and the lane choice has no effect;
+ * the sigma and gradient bits are those of a call with rgb.
+ * KNERF_ERR_INVALID, before any launch: a NULL field, records (brick_of, exponents) or query; everything knerf_baked_render (_bricks)
+ * refuses of its field; no output; neither points nor a grid, or both; a grid given in part; a grid resolution < 2 or a grid of more
+ * than 2^31 points; a grid box that is not finite, has hi <= lo or a step that is not finite; per_point outside {0, 1}; unknown flag
+ * bits; a lane count the degree does not have; n >= 2^36.  n = 0 succeeds without a launch. */
+typedef struct knerf_baked_query_spec {
+    const float* points;             /* DEVICE [n,3], or NULL with a grid */
+    uint64_t n;                      /* points in the list (ignored with a grid) */
+    const int32_t* grid_resolution;  /* HOST [3], or NULL with a list */
+    const float* grid_lo;            /* HOST [3] */
+    const float* grid_hi;            /* HOST [3] */
+    const float* directions;         /* DEVICE: NULL, [3] or [n,3] */
+    int32_t per_point;               /* directions: 0 = one shared [3], 1 = [n,3] */
+    int32_t flags;                   /* lanes per point in KNERF_BAKED_LANES_MASK */
+    float* sigma;                    /* DEVICE [n] or NULL */
+    float* rgb;                      /* DEVICE [n,3] or NULL */
+    float* gradient;                 /* DEVICE [n,3] or NULL */
+} knerf_baked_query_spec;
+int knerf_baked_query(void* stream, const knerf_baked_field* field, const knerf_baked_query_spec* query);
+int knerf_baked_query_bricks(void* stream, const knerf_baked_bricks* field, const knerf_baked_query_spec* query);
+int knerf_baked_query_qbricks(void* stream, const knerf_baked_qbricks* field, const knerf_baked_query_spec* query);
+
 /* Diagnostics (layout tables, workspace views, hardware-fact and bandwidth probes) are NOT part of this library: they are
  * declared in include/knerf_debug.h and built into libknerf_probe.so for tests/ and tools/ only. */
 

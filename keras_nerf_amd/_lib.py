@@ -62,6 +62,14 @@ class KnerfBakedQBricks(C.Structure):
     _fields_ = [("bricks", KnerfBakedBricks), ("exponents", C.c_void_p)]
 
 
+class KnerfBakedQuerySpec(C.Structure):
+    """struct knerf_baked_query_spec (include/knerf.h): the points (a device list, or a grid given on the host), the directions, the lane
+    choice and the three outputs"""
+    _fields_ = [("points", C.c_void_p), ("n", C.c_uint64), ("grid_resolution", C.POINTER(C.c_int32)), ("grid_lo", C.POINTER(C.c_float)),
+                ("grid_hi", C.POINTER(C.c_float)), ("directions", C.c_void_p), ("per_point", C.c_int32), ("flags", C.c_int32),
+                ("sigma", C.c_void_p), ("rgb", C.c_void_p), ("gradient", C.c_void_p)]
+
+
 class KnerfBakedBricksTrain(C.Structure):
     """struct knerf_baked_bricks_train (include/knerf.h): the optimiser's brick field (bits = the support) and the gradient rows, one
     per stored record"""
@@ -178,6 +186,9 @@ SIGNATURES = {
     "knerf_baked_dequantize_bricks": (C.c_int, [_P, C.POINTER(KnerfBakedQBricks), _P]),
     "knerf_baked_render_qbricks": (C.c_int, [_P, C.POINTER(KnerfBakedQBricks), _F, _F, _F, _F, C.c_float, C.c_float, C.c_uint64, C.c_float,
                                              C.c_float, C.c_int, _F, _F, _F, _P]),
+    "knerf_baked_query": (C.c_int, [_P, C.POINTER(KnerfBakedField), C.POINTER(KnerfBakedQuerySpec)]),
+    "knerf_baked_query_bricks": (C.c_int, [_P, C.POINTER(KnerfBakedBricks), C.POINTER(KnerfBakedQuerySpec)]),
+    "knerf_baked_query_qbricks": (C.c_int, [_P, C.POINTER(KnerfBakedQBricks), C.POINTER(KnerfBakedQuerySpec)]),
 }
 
 _lib = None

@@ -5,7 +5,8 @@ The arithmetic is HIP (csrc/baked.hip: knerf_baked_project, knerf_baked_pack, kn
 BakedField.optimizer and baked_train.py: optimising the records against ray batches, csrc/baked_train.hip;
 BakedField.resample and the optimiser's TV regulariser: csrc/baked_grow.hip;
 BrickBakedField, the same field stored as sparse bricks behind an index table, and its renderer: csrc/baked.hip;
-baked_quant.py QuantizedBrickField, the brick field with 8-bit SH coefficients, its codec and renderer: csrc/baked_quant.hip);
+baked_quant.py QuantizedBrickField, the brick field with 8-bit SH coefficients, its codec and renderer: csrc/baked_quant.hip;
+query, density_grid and extract_mesh of all three storages, baked_query.py: csrc/baked_query.hip);
 torch is used for device memory, streams and the index plumbing of the bake only.  Host-side pieces (basis, fit matrix, record
 layout) are NumPy and need no device.
 """
@@ -520,6 +521,30 @@ class BakedField:
         from .baked_pose import ray_gradients
         return ray_gradients(self, origins, directions, near, far, target, step, white_background, termination, n_total, lanes_per_ray)
 
+    # ---- the field at points, on grids and as a mesh (baked_query.py)
+    def query(self, points, directions=None, gradient=False, lanes_per_point=0):
+        """What the field holds at points [..., 3] (any leading shape), seen along directions None, [3] or [..., 3] (shapes and
+        broadcasting as NeRF.query): (rgb [..., 3], sigma [..., 1]) and with gradient=True also grad [..., 3], the exact gradient of
+        the trilinear sigma inside the point's cell; torch tensors on the field's device.  It is the renderer's evaluation of one
+        sample (include/knerf.h knerf_baked_query): outside the box everything is 0; no direction, or one of length 0, gives the DC
+        colour.  lanes_per_point picks the kernel variant as render's lanes_per_ray does."""
+        from .baked_query import query
+        return query(self, points, directions, gradient, lanes_per_point)
+
+    def density_grid(self, resolution=None, bounds=None, direction=None):
+        """NeRF.density_grid on this field: sigma [Rx,Ry,Rz] on the grid lo + idx (hi - lo) / (R - 1), or (sigma, rgb [Rx,Ry,Rz,3]) with a
+        direction [3].  bounds=None: the field's own box; resolution=None: the field's own resolution.  With neither, the grid is the
+        lattice itself and sigma is the stored sigma column, bit for bit (no coordinate arithmetic)."""
+        from .baked_query import density_grid
+        return density_grid(self, resolution, bounds, direction)
+
+    def extract_mesh(self, threshold, resolution=None, bounds=None, vertex_colors=False):
+        """runtime.marching_cubes(self.density_grid(resolution, bounds), threshold, lo, hi): (vertices [V,3], faces [F,3] int32, normals
+        [V,3]); vertex_colors: also self.query(vertices, -normals)[0], the convention of NeRF.extract_mesh.  An empty surface gives
+        empty arrays.  keras_nerf_amd.io.ply.save_ply writes the result."""
+        from .baked_query import extract_mesh
+        return extract_mesh(self, threshold, resolution, bounds, vertex_colors)
+
     # ---- sparse storage
     def compact(self, brick=DEFAULT_BRICK):
         """This field as a BrickBakedField: only the bricks of brick^3 lattice points (4 or 8) that hold a corner of an occupied cell
@@ -790,6 +815,22 @@ class BrickBakedField:
         """baked_pose.ray_gradients(self, ...): (grad_origin [N,3], grad_direction [N,3], loss) of the squared error against `target`"""
         from .baked_pose import ray_gradients
         return ray_gradients(self, origins, directions, near, far, target, step, white_background, termination, n_total, lanes_per_ray)
+
+    # ---- the field at points, on grids and as a mesh (baked_query.py): BakedField.query / density_grid / extract_mesh on this storage
+    def query(self, points, directions=None, gradient=False, lanes_per_point=0):
+        """BakedField.query through the brick table (knerf_baked_query_bricks): the same bits"""
+        from .baked_query import query
+        return query(self, points, directions, gradient, lanes_per_point)
+
+    def density_grid(self, resolution=None, bounds=None, direction=None):
+        """BakedField.density_grid; the lattice itself is scattered out of the stored bricks, the dense record table is never formed"""
+        from .baked_query import density_grid
+        return density_grid(self, resolution, bounds, direction)
+
+    def extract_mesh(self, threshold, resolution=None, bounds=None, vertex_colors=False):
+        """BakedField.extract_mesh"""
+        from .baked_query import extract_mesh
+        return extract_mesh(self, threshold, resolution, bounds, vertex_colors)
 
     # ---- 8-bit SH coefficients
     def quantize(self, bits=8):

@@ -294,6 +294,23 @@ class QuantizedBrickField:
             out["stats"] = counter
         return out
 
+    # ---- the field at points, on grids and as a mesh (baked_query.py): BakedField.query / density_grid / extract_mesh on the quantised records
+    def query(self, points, directions=None, gradient=False, lanes_per_point=0):
+        """BakedField.query on the quantised records (knerf_baked_query_qbricks); with lanes_per_point=1 the bits of
+        dequantize().query(lanes_per_point=1)"""
+        from .baked_query import query
+        return query(self, points, directions, gradient, lanes_per_point)
+
+    def density_grid(self, resolution=None, bounds=None, direction=None):
+        """BakedField.density_grid; the lattice itself is scattered out of the stored bricks, the dense record table is never formed"""
+        from .baked_query import density_grid
+        return density_grid(self, resolution, bounds, direction)
+
+    def extract_mesh(self, threshold, resolution=None, bounds=None, vertex_colors=False):
+        """BakedField.extract_mesh"""
+        from .baked_query import extract_mesh
+        return extract_mesh(self, threshold, resolution, bounds, vertex_colors)
+
     # ---- what a quantised field does not do
     def ray_gradients(self, *args, **kwargs):
         _refuse("ray_gradients")

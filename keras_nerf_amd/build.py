@@ -23,7 +23,7 @@ PROBE_LIB = os.path.join(HERE, "libknerf_probe.so")
 SOURCES = ["knerf_api.hip", "mlp_fwd.hip", "mlp_bwd.hip", "wgrad.hip", "generic.hip", "composite.hip", "sampler.hip", "optim.hip",
            "raygen.hip", "utils_ops.hip", "query.hip", "mesh.hip", "occupancy.hip", "train_list.hip",
            "termination.hip", "raybatch.hip", "optim_ext.hip", "composite_ext.hip", "rays_ext.hip", "baked.hip", "baked_train.hip", "baked_grow.hip",
-           "baked_pose.hip", "baked_quant.hip", "baked_bricks_grow.hip"]
+           "baked_pose.hip", "baked_quant.hip", "baked_bricks_grow.hip", "baked_query.hip"]
 # The three big kernels are templates on the trunk shape (csrc/layout.h KNERF_FUSED_SHAPES): each of these sources is compiled once
 # per shape with -DKNERF_SHAPE_SLICE=<index> (that translation unit then defines the kernels of its shape only; slice 0 also holds
 # the run-time dispatchers), so the shapes build in parallel and the default shape's object is what it was before the others existed.
@@ -38,8 +38,9 @@ MAX_EXTRA_SHAPES = 36   # a build-time budget, not a limit of csrc/layout.h (one
 # baked_grow.hip: the TV gather holds 13 rows' values and the resampler 8 corners' chunks in registers;
 # baked_pose.hip: the same two marches, dense and through the brick table, with the ray's own sums kept in registers to its end;
 # baked_quant.hip: baked.hip's brick march on 8-bit records, with 8 corners' exponent words and the decoded coefficients in registers;
-# baked_bricks_grow.hip: baked_grow.hip's two gathers with every row and record found through the brick table)
-NO_SPILL = {"baked.hip", "baked_train.hip", "baked_grow.hip", "baked_pose.hip", "baked_quant.hip", "baked_bricks_grow.hip"}
+# baked_bricks_grow.hip: baked_grow.hip's two gathers with every row and record found through the brick table;
+# baked_query.hip: the renderer's evaluation of one sample with the 8 corner sigmas kept for the gradient)
+NO_SPILL = {"baked.hip", "baked_train.hip", "baked_grow.hip", "baked_pose.hip", "baked_quant.hip", "baked_bricks_grow.hip", "baked_query.hip"}
 PROBE_SOURCES = ["debug_api.hip", "probe.hip"]
 # the extra trunk shapes of the `xshape` build variant (tests/test_gpu_variants.py builds and checks it; __graft_entry__.build() keeps an
 # existing one up to date): round 4 added width 64 (8/4 and 4/2 are built in) and pos_emb_dir 5..8 (four head k-steps)
