@@ -323,6 +323,57 @@ int knerf_draw_ray_batch_ext(knerf_ctx* ctx, void* stream, const float* images, 
                              uint64_t epoch, uint64_t first, int n_rays, const float* noise, uint64_t noise_stream, float* o, float* d,
                              float* t, float* target, int64_t* index, const knerf_ray_model* model);
 
+/* ---- Camera models: full intrinsics, lens distortion, fisheye.  Extension, no reference counterpart (the conventions of OpenCV's
+ * calib3d documentation, which COLMAP and nerfstudio / instant-ngp transforms.json files follow).  The two ray entry points below are
+ * knerf_generate_rays_ext and knerf_draw_ray_batch_ext with a camera: the same arguments in the same order, the same pixel order,
+ * the same Philox counters, `focal` replaced by (intrinsics, n_cameras, camera); every other entry point and kernel is untouched.
+ *   intrinsics: DEVICE float [n_cameras, 12] = fx, fy, cx, cy, c0..c5, 0, 0
+ *     OPENCV:  c = k1, k2, p1, p2, k3, 0        FISHEYE (equidistant): c = k1, k2, k3, k4, 0, 0
+ *   n_cameras: 1 (one camera shared by every view) or the number of views of the call (row v for view v).
+ * The ray of pixel (x, y) under a row: distorted normalised coordinates, image y pointing down,
+ *     xn = ((float)x + pixel_offset - cx) / fx,  yn = ((float)y + pixel_offset - cy) / fy
+ *   PINHOLE: (xu, yu) = (xn, yn).
+ *   OPENCV: (xu, yu) solves distort(xu, yu) = (xn, yn), where with r^2 = x^2 + y^2 and rad = 1 + k1 r^2 + k2 r^4 + k3 r^6
+ *     distort(x, y) = (x rad + 2 p1 x y + p2 (r^2 + 2 x^2),  y rad + p1 (r^2 + 2 y^2) + 2 p2 x y)
+ *     by 2-D Newton with the analytic Jacobian from (xn, yn): exactly 8 iterations, no data-dependent exit.
+ *   FISHEYE: theta solves theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8) = theta_d = hypot(xn, yn) by 1-D Newton from
+ *     theta_d, 8 iterations; camera vector (sin theta xn/theta_d, -sin theta yn/theta_d, -cos theta), (0, 0, -1) at theta_d = 0:
+ *     valid past 90 degrees.
+ *   PINHOLE and OPENCV: camera vector (xu, -yu, -1).  Every model: rotated by c2w, normalised, origin = the translation column, with
+ *   the operations of the plain kernels: PINHOLE with fx = fy = focal, cx = W * 0.5f, cy = H * 0.5f, pixel_offset = 0 writes the
+ *   bits of knerf_generate_rays / knerf_draw_ray_batch (of the _ext entry points under a ray model).
+ * The ray model is accepted as before (NULL: plain).  Sample positions do not depend on the camera, so disparity spacing works with
+ * every camera; ndc = 1 applies the NDC map to the camera's ray with the scales -2 fx / W, -2 fy / H of row 0 and needs n_cameras = 1
+ * and a model other than FISHEYE.
+ * KNERF_ERR_INVALID, before any launch, on: what the _ext entry points refuse; a NULL camera or intrinsics pointer; model outside
+ * KNERF_CAMERA_*; n_cameras outside {1, views}; pixel_offset not finite; ndc with FISHEYE or with n_cameras > 1.
+ * NOT checked: the values of the table, which live on the device (no entry point here waits for it).  fx, fy > 0, finite values and a
+ * lens that does not fold inside the image are the caller's to establish before the upload (keras_nerf_amd/data/cameras.py
+ * CameraModel.check_invertible does): Newton on a folding lens converges to whatever root is near, or not at all. */
+enum { KNERF_CAMERA_PINHOLE = 0, KNERF_CAMERA_OPENCV = 1, KNERF_CAMERA_FISHEYE = 2 };
+typedef struct knerf_camera_model {
+    int32_t model;               /* KNERF_CAMERA_*: one model per launch */
+    float pixel_offset;          /* added to the integer pixel coordinates: 0 = pixel corners (the plain camera), 0.5 = centres */
+} knerf_camera_model;
+int knerf_generate_rays_cam(knerf_ctx* ctx, void* stream, const float* c2w, const float* noise, uint64_t seed,
+                            uint64_t stream_id, int batch, int height, int width, int n_samples, const float* intrinsics,
+                            int n_cameras, const knerf_camera_model* camera, float near_plane, float far_plane, float* o, float* d,
+                            float* t, const knerf_ray_model* model);
+int knerf_draw_ray_batch_cam(knerf_ctx* ctx, void* stream, const float* images, const float* c2w, int n_views, int height, int width,
+                             int channels, const float* intrinsics, int n_cameras, const knerf_camera_model* camera,
+                             float near_plane, float far_plane, int n_samples, uint64_t seed, uint64_t epoch, uint64_t first,
+                             int n_rays, const float* noise, uint64_t noise_stream, float* o, float* d, float* t, float* target,
+                             int64_t* index, const knerf_ray_model* model);
+/* The forward map of the same cameras, one lane per point, no iteration, no context: points [n,3] (device) seen from view[i] (int32
+ * [n]; NULL: view 0) with poses c2w [V,4,4] and the intrinsics row of that view (n_cameras = 1: row 0; else n_cameras = V).  With
+ * p = R^T (x - t) the point in the camera's frame: depth [n] = -p_z; pixels [n,2] in the coordinates the ray kernels take -- the ray
+ * of pixel (x, y) projects to (x, y); valid [n] (uint8) = depth > 0 for PINHOLE / OPENCV, and for FISHEYE: the point is not the camera
+ * centre and theta < pi.  Values of view outside [0, V) are the caller's to exclude (V is not passed).  KNERF_ERR_INVALID on a NULL
+ * pointer other than view, n = 0, n_cameras < 1, model out of range, pixel_offset not finite.  The error text is read with
+ * knerf_last_error(NULL). */
+int knerf_project_points(void* stream, const float* points, const int32_t* view, const float* c2w, const float* intrinsics,
+                         int n_cameras, const knerf_camera_model* camera, uint64_t n, float* pixels, float* depth, uint8_t* valid);
+
 /* ---- NeRFUtils as stand-alone ops (no context needed; the train/render path fuses the same arithmetic) ----
  * positional_encoding (utils.py:176-186): x [n_rows,3] -> out [n_rows, 3+6L].
  * composite = render_image_depth_chunk (utils.py:16-58): raw [R,S,4] = (r,g,b,sigma), t [R,S] -> image [R,3], depth [R]

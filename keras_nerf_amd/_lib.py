@@ -38,6 +38,11 @@ class KnerfRayModel(C.Structure):
     _fields_ = [("ndc", C.c_int32), ("spacing", C.c_int32), ("ndc_near", C.c_float)]
 
 
+class KnerfCameraModel(C.Structure):
+    """struct knerf_camera_model (include/knerf.h): the camera model of a launch and the offset added to integer pixel coordinates"""
+    _fields_ = [("model", C.c_int32), ("pixel_offset", C.c_float)]
+
+
 class KnerfBakedField(C.Structure):
     """struct knerf_baked_field (include/knerf.h): device records and occupancy bits, lattice resolution, SH degree, the box"""
     _fields_ = [("records", C.c_void_p), ("bits", C.c_void_p), ("resolution", C.c_int32 * 3), ("sh_degree", C.c_int32),
@@ -79,6 +84,9 @@ class KnerfBakedBricksTrain(C.Structure):
 BAKED_WHITE_BACKGROUND, BAKED_SKIP_EMPTY, BAKED_LANES_SHIFT = 1, 2, 8
 SPACING_LINEAR, SPACING_DISPARITY = 0, 1
 SPACINGS = {"linear": SPACING_LINEAR, "disparity": SPACING_DISPARITY}
+CAMERA_PINHOLE, CAMERA_OPENCV, CAMERA_FISHEYE = 0, 1, 2
+CAMERA_MODELS = {"pinhole": CAMERA_PINHOLE, "opencv": CAMERA_OPENCV, "fisheye": CAMERA_FISHEYE}
+CAMERA_ROW = 12             # floats per intrinsics row: fx, fy, cx, cy, six coefficients, two zeros
 LOSS_MSE, LOSS_MAE, LOSS_HUBER, LOSS_LOG_COSH = 0, 1, 2, 3
 SCHEDULE_CONSTANT, SCHEDULE_EXPONENTIAL, SCHEDULE_COSINE, SCHEDULE_PIECEWISE = 0, 1, 2, 3
 CLIP_NONE, CLIP_VALUE, CLIP_NORM, CLIP_GLOBAL_NORM = 0, 1, 2, 4
@@ -138,6 +146,14 @@ SIGNATURES = {
     "knerf_draw_ray_batch_ext": (C.c_int, [_P, _P, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int,
                                            C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _F, C.c_uint64, _F, _F, _F, _F, _P,
                                            C.POINTER(KnerfRayModel)]),
+    "knerf_generate_rays_cam": (C.c_int, [_P, _P, _F, _F, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          _F, C.c_int, C.POINTER(KnerfCameraModel), C.c_float, C.c_float, _F, _F, _F,
+                                          C.POINTER(KnerfRayModel)]),
+    "knerf_draw_ray_batch_cam": (C.c_int, [_P, _P, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, _F, C.c_int,
+                                           C.POINTER(KnerfCameraModel), C.c_float, C.c_float, C.c_int,
+                                           C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _F, C.c_uint64, _F, _F, _F, _F, _P,
+                                           C.POINTER(KnerfRayModel)]),
+    "knerf_project_points": (C.c_int, [_P, _F, _P, _F, _F, C.c_int, C.POINTER(KnerfCameraModel), C.c_uint64, _F, _F, _P]),
     "knerf_positional_encoding": (C.c_int, [_P, _F, C.c_longlong, C.c_int, _F]),
     "knerf_composite": (C.c_int, [_P, _F, _F, C.c_int, C.c_int, C.c_int, _F, _F, _F]),
     "knerf_inverse_cdf": (C.c_int, [_P, _F, _F, _F, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F]),

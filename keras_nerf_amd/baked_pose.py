@@ -8,7 +8,8 @@ include/knerf.h holds the contract, DESIGN.md 2.24 the derivation).  The pose st
 Rodrigues update are plain torch on the device.  No step waits for the GPU.
 
 Not covered: the MLP path has no input gradient; NDC rays are refused (the pose does not enter them as o = t, d = R cam);
-intrinsics and lens distortion are not refined; there is no pose regulariser.
+there is no pose regulariser.  Intrinsics and lens distortion can be stated (data/cameras.py: every camera there is central, o = t,
+d = R cam, so its rays refine like the plain camera's) but are not refined.
 """
 from __future__ import annotations
 

@@ -23,7 +23,7 @@ PROBE_LIB = os.path.join(HERE, "libknerf_probe.so")
 SOURCES = ["knerf_api.hip", "mlp_fwd.hip", "mlp_bwd.hip", "wgrad.hip", "generic.hip", "composite.hip", "sampler.hip", "optim.hip",
            "raygen.hip", "utils_ops.hip", "query.hip", "mesh.hip", "occupancy.hip", "train_list.hip",
            "termination.hip", "raybatch.hip", "optim_ext.hip", "composite_ext.hip", "rays_ext.hip", "baked.hip", "baked_train.hip", "baked_grow.hip",
-           "baked_pose.hip", "baked_quant.hip", "baked_bricks_grow.hip", "baked_query.hip"]
+           "baked_pose.hip", "baked_quant.hip", "baked_bricks_grow.hip", "baked_query.hip", "rays_cam.hip"]
 # The three big kernels are templates on the trunk shape (csrc/layout.h KNERF_FUSED_SHAPES): each of these sources is compiled once
 # per shape with -DKNERF_SHAPE_SLICE=<index> (that translation unit then defines the kernels of its shape only; slice 0 also holds
 # the run-time dispatchers), so the shapes build in parallel and the default shape's object is what it was before the others existed.
@@ -39,15 +39,17 @@ MAX_EXTRA_SHAPES = 36   # a build-time budget, not a limit of csrc/layout.h (one
 # baked_pose.hip: the same two marches, dense and through the brick table, with the ray's own sums kept in registers to its end;
 # baked_quant.hip: baked.hip's brick march on 8-bit records, with 8 corners' exponent words and the decoded coefficients in registers;
 # baked_bricks_grow.hip: baked_grow.hip's two gathers with every row and record found through the brick table;
-# baked_query.hip: the renderer's evaluation of one sample with the 8 corner sigmas kept for the gradient)
-NO_SPILL = {"baked.hip", "baked_train.hip", "baked_grow.hip", "baked_pose.hip", "baked_quant.hip", "baked_bricks_grow.hip", "baked_query.hip"}
+# baked_query.hip: the renderer's evaluation of one sample with the 8 corner sigmas kept for the gradient;
+# rays_cam.hip: eight unrolled Newton steps per ray with the lens coefficients, the Jacobian and the iterate in registers)
+NO_SPILL = {"baked.hip", "baked_train.hip", "baked_grow.hip", "baked_pose.hip", "baked_quant.hip", "baked_bricks_grow.hip", "baked_query.hip",
+            "rays_cam.hip"}
 PROBE_SOURCES = ["debug_api.hip", "probe.hip"]
 # the extra trunk shapes of the `xshape` build variant (tests/test_gpu_variants.py builds and checks it; __graft_entry__.build() keeps an
 # existing one up to date): round 4 added width 64 (8/4 and 4/2 are built in) and pos_emb_dir 5..8 (four head k-steps)
 # round 6: a concat behind the LAST trunk layer ((n_layers - 1) % skip_layer == 0): the head takes [h ; xyz_enc ; dir_enc]
 XSHAPES = ["6,3,128", "8,2,128", "8,4,256,6,2", "8,4,256,12,4", "8,4,128,5,1", "4,2,256,16,3",
            "6,3,64", "8,4,64,6,2", "8,4,256,10,8", "8,4,128,10,6", "9,4,256", "5,2,128", "5,4,64,6,2"]
-HEADERS = ["chain.h", "ctx.h", "kernels.h", "layout.h", "bwd_body.h", "wgrad_body.h", "generic.h", "query.h", "mesh_table.h", "occupancy.h", "train_list.h", "termination.h", "rays.h", "rays_ext.h", "optim_ext.h", "composite_ext.h", "baked_common.h", "baked_grow_common.h", os.path.join("..", "..", "include", "knerf.h"),
+HEADERS = ["chain.h", "ctx.h", "kernels.h", "layout.h", "bwd_body.h", "wgrad_body.h", "generic.h", "query.h", "mesh_table.h", "occupancy.h", "train_list.h", "termination.h", "rays.h", "rays_ext.h", "rays_cam.h", "optim_ext.h", "composite_ext.h", "baked_common.h", "baked_grow_common.h", os.path.join("..", "..", "include", "knerf.h"),
            os.path.join("..", "..", "include", "knerf_debug.h")]
 # -ffp-contract=off: the parity-critical fp32 arithmetic (ray points, sampler, compositing) must round like the
 # reference's separate mul/add ops; fused multiply-adds are written explicitly (__builtin_fmaf) where wanted.

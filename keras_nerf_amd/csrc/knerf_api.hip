@@ -22,6 +22,7 @@
 #include "query.h"
 #include "rays.h"
 #include "rays_ext.h"
+#include "rays_cam.h"
 #include "termination.h"
 #include "train_list.h"
 
@@ -1587,6 +1588,69 @@ int knerf_draw_ray_batch_ext(knerf_ctx* ctx, void* stream, const float* images, 
     RayModel m{};
     if (int r = check_ray_model(ctx, "draw_ray_batch_ext", model, near_plane, far_plane, &m)) return r;
     if (launch_raybatch_ext(a, m, (hipStream_t)stream) != hipSuccess) return fail(ctx, KNERF_ERR_HIP, "draw_ray_batch_ext: launch failed");
+    return KNERF_OK;
+}
+
+// ---- camera models (include/knerf.h knerf_generate_rays_cam; rays_cam.h) -----------------------------------------------------------
+// the checks of a camera against the views of the call and the ray model it is used with; the table's values stay unread (device)
+static int check_camera(knerf_ctx* ctx, const char* who, const float* intrinsics, int n_cameras, const knerf_camera_model* camera,
+                        int views, const RayModel* m, CamArgs* out) {
+    const std::string w = std::string(who) + ": ";
+    if (!camera || !intrinsics) return fail(ctx, KNERF_ERR_INVALID, w + "null camera or intrinsics");
+    if (camera->model != KNERF_CAMERA_PINHOLE && camera->model != KNERF_CAMERA_OPENCV && camera->model != KNERF_CAMERA_FISHEYE)
+        return fail(ctx, KNERF_ERR_INVALID, w + "unknown camera model " + std::to_string(camera->model));
+    if (!std::isfinite(camera->pixel_offset)) return fail(ctx, KNERF_ERR_INVALID, w + "pixel_offset must be finite");
+    if (n_cameras != 1 && (views <= 0 || n_cameras != views))
+        return fail(ctx, KNERF_ERR_INVALID, w + "n_cameras must be 1 or the number of views (" + std::to_string(views) + "), got " + std::to_string(n_cameras));
+    if (m && m->ndc && camera->model == KNERF_CAMERA_FISHEYE)
+        return fail(ctx, KNERF_ERR_INVALID, w + "NDC rays need a camera that looks along -z: not the fisheye model");
+    if (m && m->ndc && n_cameras > 1)
+        return fail(ctx, KNERF_ERR_INVALID, w + "NDC rays take their scales from one camera: n_cameras must be 1");
+    *out = CamArgs{intrinsics, n_cameras > 1 ? 1 : 0, camera->pixel_offset};
+    return KNERF_OK;
+}
+
+int knerf_generate_rays_cam(knerf_ctx* ctx, void* stream, const float* c2w, const float* noise, uint64_t seed, uint64_t stream_id,
+                            int batch, int height, int width, int n_samples, const float* intrinsics, int n_cameras,
+                            const knerf_camera_model* camera, float near_plane, float far_plane, float* o, float* d, float* t,
+                            const knerf_ray_model* model) {
+    RayGenArgs a{};
+    if (int r = raygen_args(ctx, "generate_rays_cam", c2w, noise, seed, stream_id, batch, height, width, n_samples, 0.f, near_plane, far_plane, o, d, t, &a)) return r;
+    if ((unsigned long long)batch * (unsigned long long)height * (unsigned long long)width >= (1ull << 39) / (unsigned long long)n_samples)
+        return fail(ctx, KNERF_ERR_INVALID, "generate_rays_cam: batch x height x width x n_samples is too large for one launch");
+    RayModel m{};
+    if (int r = check_ray_model(ctx, "generate_rays_cam", model, near_plane, far_plane, &m)) return r;
+    CamArgs c{};
+    if (int r = check_camera(ctx, "generate_rays_cam", intrinsics, n_cameras, camera, batch, &m, &c)) return r;
+    if (launch_raygen_cam(a, m, c, camera->model, (hipStream_t)stream) != hipSuccess) return fail(ctx, KNERF_ERR_HIP, "generate_rays_cam: launch failed");
+    return KNERF_OK;
+}
+
+int knerf_draw_ray_batch_cam(knerf_ctx* ctx, void* stream, const float* images, const float* c2w, int n_views, int height, int width,
+                             int channels, const float* intrinsics, int n_cameras, const knerf_camera_model* camera, float near_plane,
+                             float far_plane, int n_samples, uint64_t seed, uint64_t epoch, uint64_t first, int n_rays,
+                             const float* noise, uint64_t noise_stream, float* o, float* d, float* t, float* target, int64_t* index,
+                             const knerf_ray_model* model) {
+    RayBatchArgs a{};
+    if (int r = raybatch_args(ctx, "draw_ray_batch_cam", images, c2w, n_views, height, width, channels, 0.f, near_plane, far_plane, n_samples, seed, epoch,
+                              first, n_rays, noise, noise_stream, o, d, t, target, index, &a)) return r;
+    RayModel m{};
+    if (int r = check_ray_model(ctx, "draw_ray_batch_cam", model, near_plane, far_plane, &m)) return r;
+    CamArgs c{};
+    if (int r = check_camera(ctx, "draw_ray_batch_cam", intrinsics, n_cameras, camera, n_views, &m, &c)) return r;
+    if (launch_raybatch_cam(a, m, c, camera->model, (hipStream_t)stream) != hipSuccess) return fail(ctx, KNERF_ERR_HIP, "draw_ray_batch_cam: launch failed");
+    return KNERF_OK;
+}
+
+int knerf_project_points(void* stream, const float* points, const int32_t* view, const float* c2w, const float* intrinsics, int n_cameras,
+                         const knerf_camera_model* camera, uint64_t n, float* pixels, float* depth, uint8_t* valid) {
+    if (!points || !c2w || !pixels || !depth || !valid || n == 0) return fail(nullptr, KNERF_ERR_INVALID, "project_points: null/empty argument");
+    if (n >= (1ull << 39)) return fail(nullptr, KNERF_ERR_INVALID, "project_points: too many points for one launch");
+    if (n_cameras < 1) return fail(nullptr, KNERF_ERR_INVALID, "project_points: n_cameras must be at least 1");
+    CamArgs c{};
+    if (int r = check_camera(nullptr, "project_points", intrinsics, n_cameras, camera, n_cameras, nullptr, &c)) return r;
+    ProjectArgs a{points, (const int*)view, c2w, c, (unsigned long long)n, pixels, depth, (unsigned char*)valid};
+    if (launch_project_points(a, camera->model, (hipStream_t)stream) != hipSuccess) return fail(nullptr, KNERF_ERR_HIP, "project_points: launch failed");
     return KNERF_OK;
 }
 

@@ -38,12 +38,9 @@ __device__ __forceinline__ float stratified_sample(int n, int N, float near_, fl
     return fminf(fmaxf(tv, near_), far_);
 }
 
-// the ray through the corner of pixel (xpix, ypix) of a W x H pinhole camera with pose M (c2w, 4x4 row-major): camera vector
-// ((x - W/2) / f, -(y - H/2) / f, -1) rotated and normalised, origin = the translation column
-__device__ __forceinline__ void pixel_ray(const float* M, int xpix, int ypix, int W, int H, float focal, float* o, float* d) {
-    const float xc = __fdiv_rn((float)xpix - (float)W * 0.5f, focal);
-    const float yc = __fdiv_rn((float)ypix - (float)H * 0.5f, focal);
-    const float cam[3] = {xc, -yc, -1.f};
+// the ray of a camera-space vector under pose M (c2w, 4x4 row-major): the vector rotated and normalised, origin = the translation
+// column.  Every camera of the project ends here (pixel_ray below, rays_cam.h), so that they share these roundings.
+__device__ __forceinline__ void camera_ray(const float* M, const float (&cam)[3], float* o, float* d) {
     float dv[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r)
@@ -51,6 +48,15 @@ __device__ __forceinline__ void pixel_ray(const float* M, int xpix, int ypix, in
     const float nrm = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dv[0], dv[0]), __fmul_rn(dv[1], dv[1])), __fmul_rn(dv[2], dv[2])));
 #pragma unroll
     for (int r = 0; r < 3; ++r) { d[r] = __fdiv_rn(dv[r], nrm); o[r] = M[r * 4 + 3]; }
+}
+
+// the ray through the corner of pixel (xpix, ypix) of a W x H pinhole camera with pose M (c2w, 4x4 row-major): camera vector
+// ((x - W/2) / f, -(y - H/2) / f, -1) rotated and normalised, origin = the translation column
+__device__ __forceinline__ void pixel_ray(const float* M, int xpix, int ypix, int W, int H, float focal, float* o, float* d) {
+    const float xc = __fdiv_rn((float)xpix - (float)W * 0.5f, focal);
+    const float yc = __fdiv_rn((float)ypix - (float)H * 0.5f, focal);
+    const float cam[3] = {xc, -yc, -1.f};
+    camera_ray(M, cam, o, d);
 }
 
 // ---- the pixel permutation of a ray batch: a keyed bijection of [0, P), evaluated per position, no table.

@@ -23,7 +23,11 @@ travel through pinned memory with a non-blocking copy.  A dataset larger than `d
 two pinned buffers on a side stream instead, one batch ahead of the step that consumes it.
 
 `RayImageDataset.ray_batches(rays_per_step)` gives the same data as batches of rays drawn at random over all pixels of all images
-(raybatch.py): the usual way to train a NeRF, which the reference does not have."""
+(raybatch.py): the usual way to train a NeRF, which the reference does not have.
+
+A `transforms_*.json` that carries the nerfstudio / instant-ngp intrinsics (fl_x, fl_y, cx, cy, w, h, distortion coefficients,
+camera_model; at top level or per frame) is loaded with a calibrated camera (`camera_from_transforms`, data/cameras.py); a file
+without them loads exactly as the reference loads it."""
 from __future__ import annotations
 
 import json
@@ -165,6 +169,10 @@ class RayImageDataset:
         # the same order on every rank (the rngs are seeded alike and advance alike), each rank keeps its slice
         order = shuffled_order(len(self.image_paths), self.batch_size, self._rng)
         batches = replica_batches(order, self._local_batch(world), rank, world, self._limit)
+        camera = getattr(self._rg, "camera", None)            # a per-view camera table: the generator is told each batch's views
+        per_view = camera is not None and camera.n_cameras > 1
+        if per_view and camera.n_cameras != len(self.image_paths):
+            raise ValueError(f"the ray generator's camera has {camera.n_cameras} rows for {len(self.image_paths)} views")
 
         def gen_resident(res):
             dev, have, cams = res
@@ -177,7 +185,7 @@ class RayImageDataset:
                     for i in missing:
                         self._cache.pop(i, None)              # the device copy is the cache now
                 sel = self._to_device_async(np.asarray(idx, np.int64))
-                o, d, t = self._rg(cams.index_select(0, sel))
+                o, d, t = self._rg(cams.index_select(0, sel), **({"view_index": sel} if per_view else {}))
                 yield dev.index_select(0, sel), (o, d, t)
 
         def gen_staged():
@@ -204,13 +212,58 @@ class RayImageDataset:
                 dev, ev = cur
                 main.wait_event(ev)
                 dev.record_stream(main)
-                o, d, t = self._rg(self._to_device_async(np.stack([self.camera_params[i] for i in idx])))
+                o, d, t = self._rg(self._to_device_async(np.stack([self.camera_params[i] for i in idx])),
+                                   **({"view_index": self._to_device_async(np.asarray(idx, np.int64))} if per_view else {}))
                 yield dev, (o, d, t)
 
         if not batches:
             return _Iterator(iter(()))
         res = self._resident(self._image(batches[0][0]).shape)
         return _Iterator(gen_resident(res) if res is not None else gen_staged())
+
+
+INTRINSIC_KEYS = ("fl_x", "fl_y", "cx", "cy", "w", "h", "k1", "k2", "k3", "k4", "p1", "p2", "camera_model")
+IMAGE_SUFFIXES = (".png", ".jpg", ".jpeg")
+
+
+def camera_from_transforms(cfg: dict, image_width: int, image_height: int):
+    """The CameraModel (data/cameras.py) of a transforms file that carries the nerfstudio / instant-ngp intrinsics -- fl_x, fl_y, cx,
+    cy, w, h, optionally k1, k2, k3, k4, p1, p2 and camera_model "OPENCV" | "OPENCV_FISHEYE", at top level (one camera) or per frame
+    (a frame's keys override the top level; one camera per view) -- scaled from w x h to the requested size, rays through the pixel
+    centres (pixel_offset 0.5).  None for a file without fl_x anywhere: the plain camera of camera_angle_x."""
+    from .cameras import CameraModel
+    frames = cfg.get("frames", [])
+    if "fl_x" not in cfg and not any("fl_x" in fr for fr in frames):
+        return None
+    per_frame = any(key in fr for fr in frames for key in INTRINSIC_KEYS)
+    rows = []
+    for n, fr in enumerate(frames if per_frame else [{}]):
+        g = {key: fr.get(key, cfg.get(key)) for key in INTRINSIC_KEYS}
+        where = f"frame {n}" if per_frame else "the file"
+        if g["fl_x"] is None or g["w"] is None or g["h"] is None:
+            raise ValueError(f"{where}: fl_x, w and h are needed to state a camera")
+        name = g["camera_model"]
+        if name not in (None, "OPENCV", "OPENCV_FISHEYE", "PINHOLE", "SIMPLE_PINHOLE"):
+            raise ValueError(f"{where}: camera_model {name!r} is not supported (OPENCV, OPENCV_FISHEYE)")
+        k = {key: float(g[key] or 0.0) for key in ("k1", "k2", "k3", "k4", "p1", "p2")}
+        if name == "OPENCV_FISHEYE":
+            model, dist = "fisheye", (k["k1"], k["k2"], k["k3"], k["k4"])
+        elif any(k[key] != 0.0 for key in ("k1", "k2", "k3", "p1", "p2")):
+            model, dist = "opencv", (k["k1"], k["k2"], k["p1"], k["p2"], k["k3"])
+        else:
+            model, dist = "pinhole", ()
+        w, h = float(g["w"]), float(g["h"])
+        fl_x = float(g["fl_x"])
+        rows.append((model, fl_x, float(g["fl_y"] if g["fl_y"] is not None else fl_x), float(g["cx"] if g["cx"] is not None else w / 2),
+                     float(g["cy"] if g["cy"] is not None else h / 2), dist, image_width / w, image_height / h))
+    models = {r[0] for r in rows} - {"pinhole"}
+    if len(models) > 1:
+        raise ValueError("a file that mixes OPENCV and OPENCV_FISHEYE cameras: one launch draws rays of one model")
+    model = models.pop() if models else "pinhole"
+    n_coeff = {"pinhole": 0, "opencv": 5, "fisheye": 4}[model]
+    dist = np.array([list(r[5]) + [0.0] * (n_coeff - len(r[5])) for r in rows], np.float64).reshape(len(rows), n_coeff)
+    col = lambda i, j: np.array([r[i] * r[j] for r in rows])
+    return CameraModel(model, col(1, 6), col(2, 7), col(3, 6), col(4, 7), dist, pixel_offset=0.5)
 
 
 class DatasetLoader:
@@ -225,13 +278,34 @@ class DatasetLoader:
         paths = [os.path.join(self.data_dir, f"{fr['file_path']}.png") for fr in json_config["frames"]]
         return paths, [fr["transform_matrix"] for fr in json_config["frames"]]
 
+    def _calibrated_dataset(self, cfg, camera, k, batch_size, image_width, image_height, near, far, n_sample):
+        """the dataset of a file with intrinsics (camera_from_transforms): images resized to image_height rows x image_width columns
+        (calibrated photographs are rarely square), file paths taken with their suffix when they have one"""
+        loader = ImageLoader(image_width, image_height, self.white_background, height_first=True)
+
+        def factory(rank=0):
+            from .rays import RaysGenerator
+            return RaysGenerator(focal_length=None, image_width=image_width, image_height=image_height, near=near, far=far,
+                                 n_sample=n_sample, seed=1000 + k + 4096 * rank, camera=camera)
+        paths = [os.path.join(self.data_dir, fr["file_path"] if fr["file_path"].lower().endswith(IMAGE_SUFFIXES) else f"{fr['file_path']}.png")
+                 for fr in cfg["frames"]]
+        return RayImageDataset(paths, [fr["transform_matrix"] for fr in cfg["frames"]], loader, factory, batch_size, seed=k)
+
     def load_dataset(self, batch_size: int, image_width: int, image_height: int, near: float, far: float, n_sample: int) -> List[RayImageDataset]:
         """loader.py:55-113.  batch_size: the GLOBAL batch (train.py:84-93 passes batch_size x replicas; train_single.py:60-67 the
         only batch there is); a rank of a data-parallel job yields its 1/world slice of every batch"""
         image_loader = ImageLoader(image_width, image_height, self.white_background)
         out = []
+        self.cameras = []                                     # per subset: the CameraModel of a calibrated file, else None
         for k, subset in enumerate(["train", "val", "test"]):
             cfg = self._load_json(os.path.join(self.data_dir, f"transforms_{subset}.json"))
+            camera = camera_from_transforms(cfg, image_width, image_height)
+            self.cameras.append(camera)
+            if camera is not None:
+                camera.check_invertible(image_width, image_height)          # on the host, before anything is uploaded
+                out.append(self._calibrated_dataset(cfg, camera, k, batch_size, image_width, image_height, near, far, n_sample))
+                logging.info(f"Loaded {subset} dataset. {len(cfg['frames'])} images, {camera.model} camera.")
+                continue
             focal = get_focal_from_fov(cfg["camera_angle_x"], image_width)
 
             def factory(rank=0, focal=focal, k=k):

@@ -183,6 +183,8 @@ class RayBatchDataset:
                              f"{dev.shape[1]} x {dev.shape[2]}")
         model = getattr(rg, "ray_model", None)                 # None: the plain rays through the plain entry point
         extra = {} if model is None else {"ray_model": model}
+        if getattr(rg, "camera", None) is not None:            # a calibrated camera: knerf_draw_ray_batch_cam, row v for view v
+            extra["camera"] = rg.camera
 
         def gen():
             for perm, step in steps:

@@ -638,11 +638,25 @@ class KnerfContext:
                                                      _ptr(t), None if ray_model is None else C.byref(ray_model)))
         return o, d, t
 
+    def generate_rays_cam(self, c2w, camera, height, width, near, far, n_samples, ray_model=None, noise=None, seed=0, stream_id=0):
+        """generate_rays_ext with a camera (data.cameras.CameraModel: one camera, or one per matrix of c2w) in place of the focal
+        length: knerf_generate_rays_cam.  The camera's table is the caller's to have checked (CameraModel.check_invertible)."""
+        c2w = self.f32(c2w).reshape(-1, 4, 4)
+        B = c2w.shape[0]
+        noise = None if noise is None else self.f32(noise)
+        o = torch.empty((B, height, width, 3), device=self.device); d = torch.empty_like(o)
+        t = torch.empty((B, height, width, n_samples), device=self.device)
+        table, cs = camera.device_table(self.device), camera.c_struct()
+        self._check(self.lib.knerf_generate_rays_cam(self._ctx, self._stream(), _ptr(c2w), _ptr(noise), seed, stream_id, B, height,
+                                                     width, n_samples, _ptr(table), table.shape[0], C.byref(cs), float(near), float(far),
+                                                     _ptr(o), _ptr(d), _ptr(t), None if ray_model is None else C.byref(ray_model)))
+        return o, d, t
+
     def draw_ray_batch(self, images, c2w, focal, near, far, n_samples, seed, epoch, first, n_rays, noise=None, noise_stream=0,
-                       want_index=False, ray_model=None):
+                       want_index=False, ray_model=None, camera=None):
         """one batch of rays drawn over all pixels of `images` [V,H,W,3|4] (module-level draw_ray_batch, on this context)"""
         return draw_ray_batch(images, c2w, focal, near, far, n_samples, seed, epoch, first, n_rays, noise, noise_stream, want_index,
-                              ctx=self, ray_model=ray_model)
+                              ctx=self, ray_model=ray_model, camera=camera)
 
     PROFILE_CLASSES = ("mlp_fwd_coarse", "mlp_fwd_fine", "composite", "sample_fine", "mlp_bwd_coarse", "mlp_bwd_fine",
                        "wgrad_coarse", "wgrad_fine", "adam_repack")
@@ -659,12 +673,14 @@ class KnerfContext:
 
 
 def draw_ray_batch(images, c2w, focal, near, far, n_samples, seed, epoch, first, n_rays, noise=None, noise_stream=0,
-                   want_index=False, ctx=None, ray_model=None):
+                   want_index=False, ctx=None, ray_model=None, camera=None):
     """knerf_draw_ray_batch: slot i = pixel perm(seed, epoch)(first + i) of images [V,H,W,3|4] (float32, on the device) with camera
     matrices c2w [V,4,4].  Returns (o [n,3], d [n,3], t [n,n_samples], target [n,3]) and, with want_index, the flat pixel indices
     [n] (int64).  One launch on the current stream, nothing waits.  ctx: a KnerfContext, or None (the op needs none).
     ray_model: None -- the plain rays through knerf_draw_ray_batch -- or a _lib.KnerfRayModel (NDC rays, disparity spacing; a pinhole
-    model with linear spacing gives the plain rays bit for bit) through knerf_draw_ray_batch_ext."""
+    model with linear spacing gives the plain rays bit for bit) through knerf_draw_ray_batch_ext.
+    camera: None, or a data.cameras.CameraModel (one camera, or one per view) that takes the place of `focal` (then unused, may be None):
+    knerf_draw_ray_batch_cam, under the same ray_model.  Its table is the caller's to have checked (CameraModel.check_invertible)."""
     if not (isinstance(images, torch.Tensor) and images.is_cuda and images.dtype == torch.float32 and images.dim() == 4):
         raise KnerfError("draw_ray_batch wants the images as one float32 [V,H,W,C] tensor on the device; there is no CPU path")
     dev = images.device
@@ -684,10 +700,15 @@ def draw_ray_batch(images, c2w, focal, near, far, n_samples, seed, epoch, first,
     t = torch.empty((n, n_samples), device=dev)
     index = torch.empty((n,), device=dev, dtype=torch.int64) if want_index else None
     lib = ctx.lib if ctx is not None else _lib.load()
-    args = (None if ctx is None else ctx._ctx, torch.cuda.current_stream(dev).cuda_stream, _ptr(images),
-            _ptr(c2w), V, H, W, C, float(focal), float(near), float(far), int(n_samples), int(seed), int(epoch),
+    head = (None if ctx is None else ctx._ctx, torch.cuda.current_stream(dev).cuda_stream, _ptr(images), _ptr(c2w), V, H, W, C)
+    tail = (float(near), float(far), int(n_samples), int(seed), int(epoch),
             int(first), n, _ptr(noise), int(noise_stream), _ptr(o), _ptr(d), _ptr(t), _ptr(target), _ptr(index))
-    rc = lib.knerf_draw_ray_batch(*args) if ray_model is None else lib.knerf_draw_ray_batch_ext(*args, _byref(ray_model))
+    if camera is not None:
+        table, cs = camera.device_table(dev), camera.c_struct()
+        rc = lib.knerf_draw_ray_batch_cam(*head, _ptr(table), table.shape[0], _byref(cs), *tail, None if ray_model is None else _byref(ray_model))
+    else:
+        args = (*head, float(focal), *tail)
+        rc = lib.knerf_draw_ray_batch(*args) if ray_model is None else lib.knerf_draw_ray_batch_ext(*args, _byref(ray_model))
     if ctx is not None:
         ctx._check(rc)
     elif rc != 0:
