@@ -626,6 +626,37 @@ int knerf_baked_train_rays_ext(void* stream, const knerf_baked_train* train, con
                                const float* near, const float* far, float near_all, float far_all, const float* target, uint64_t n_rays,
                                uint64_t n_norm, float step, float termination, int flags, float* sq_err,
                                const knerf_objective* objective, float* terms);
+/* knerf_baked_train_rays_rgba -- extension, no reference counterpart.  knerf_baked_train_rays_ext against RGBA photographs: a background
+ * per ray, the target recomposited over it with the photograph's alpha, and a loss between the ray's opacity and that alpha (what grid
+ * methods do against cut-out images: a floater in front of an empty pixel then differs from the background and has a gradient). */
+typedef struct knerf_baked_rgba {
+    const float* background;    /* DEVICE [n_rays,3], or NULL: 1 with KNERF_BAKED_WHITE_BACKGROUND, else 0, on every channel */
+    const float* alpha;         /* DEVICE [n_rays], or NULL: the target is used as it is (every alpha then reads as 1) */
+    float stored_background;    /* 0 or 1: what the target's rgb is already composited over */
+    float opacity;              /* lambda_o >= 0; > 0 needs alpha */
+} knerf_baked_rgba;
+/* C, O, w_j, delta, N, rho, D, H as in knerf_baked_train_rays_ext; all fp32 without contraction, in the order written.  Per ray:
+ *   b_c = background[ray][c], or the flag's value;   pre_c = C_c + b_c (1 - O),   out_c = clip(pre_c, 0, 1)
+ *   tgt_c = target_c + (1 - alpha) (b_c - stored_background) with alpha, else target_c: a target stored as alpha rgb + (1 - alpha) B0
+ *       becomes the photograph over b; it is not clipped
+ *   d_c = out_c - tgt_c,   g_c = rho'(d_c) / (3 N) [0 <= pre_c <= 1]
+ *   L = 1 / (3 N) sum rho(d_c) + (distortion / N) sum D + (opacity_entropy / N) sum H + (opacity / N) sum (O - alpha)^2
+ *   A_j = sum_c g_c (col_jc - b_c) + r_j,   r_j = (distortion / N) dD/dw_j + (opacity_entropy / N) dH/dw + (opacity / N) 2 (O - alpha)
+ *   later samples: sum_c g_c ((C_c - P_c) - b_c (O - P_O)) + (total - running prefix),
+ *       total = (distortion / N) 2 D + ((opacity_entropy / N) dH/dw + (opacity / N) 2 (O - alpha)) O
+ * The opacity term passes neither clamp: a ray whose g is 0 on every channel still adds its gradient once it fetched a sample; a ray
+ * without a fetched sample adds none.  With b = 1 the expression 1 (1 - O) has the bits of the white flag's 1 - O, with b = 0 the sum
+ * C + 0 has the bits of C: a background array of ones (zeros) without alpha and weight gives the bits of the flag's _ext call.
+ * terms, fp32 [n_rays][5] or NULL: the four of _ext, then (O - alpha)^2 (alpha = 1 without an alpha array).
+ * rgba == NULL, or background == NULL && alpha == NULL && opacity == 0: the call IS knerf_baked_train_rays_ext (the same launch, the same
+ * bits; terms is then [n_rays][4], and under a plain objective untouched).  Otherwise the rgba kernel runs, also under a plain objective.
+ * KNERF_ERR_INVALID, before any launch: everything knerf_baked_train_rays_ext refuses; stored_background other than 0 or 1; opacity
+ * negative or not finite; opacity > 0 without alpha.  Every lane variant of _ext exists for the rgba kernel too.  The device values of
+ * background and alpha are not read back. */
+int knerf_baked_train_rays_rgba(void* stream, const knerf_baked_train* train, const float* origins, const float* directions,
+                                const float* near, const float* far, float near_all, float far_all, const float* target, uint64_t n_rays,
+                                uint64_t n_norm, float step, float termination, int flags, float* sq_err,
+                                const knerf_objective* objective, float* terms, const knerf_baked_rgba* rgba);
 /* knerf_baked_train_apply -- extension, no reference counterpart.  One Adam step over all slots and the records rewritten.
  * point_of: int32 [n_slots], the lattice point of a slot (the inverse of slot_of); sigma_trainable: uint8 [n_slots]; master, m, v:
  * fp32 [n_slots][1 + 3 K] like grad.  Per column, Keras form: m += (g - m)(1 - beta_1), v += (g g - v)(1 - beta_2),
@@ -743,6 +774,13 @@ int knerf_baked_bricks_train_rays_ext(void* stream, const knerf_baked_bricks_tra
                                       const float* near, const float* far, float near_all, float far_all, const float* target,
                                       uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags, float* sq_err,
                                       const knerf_objective* objective, float* terms);
+/* knerf_baked_bricks_train_rays_rgba -- extension, no reference counterpart.  knerf_baked_train_rays_rgba through the brick table: the
+ * same record, arithmetic, terms [n_rays][5] and refusals (rgba NULL or empty: the call IS knerf_baked_bricks_train_rays_ext); for a
+ * brick set that holds every corner of every support cell the addends are those of the dense call, bit for bit. */
+int knerf_baked_bricks_train_rays_rgba(void* stream, const knerf_baked_bricks_train* train, const float* origins, const float* directions,
+                                       const float* near, const float* far, float near_all, float far_all, const float* target,
+                                       uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags, float* sq_err,
+                                       const knerf_objective* objective, float* terms, const knerf_baked_rgba* rgba);
 /* knerf_baked_bricks_train_apply -- extension, no reference counterpart.  knerf_baked_train_apply over the stored records: the same Adam
  * step, projection, record rewrite (fp32 sigma, coefficients to fp16 to nearest even, zero padding) and zeroing of the gradient row.
  * flags: uint8 [n_bricks b^3]; bit 0: the record is a slot (a corner of a support cell), bit 1: its sigma is trainable.  A record without

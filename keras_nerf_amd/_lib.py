@@ -81,6 +81,12 @@ class KnerfBakedBricksTrain(C.Structure):
     _fields_ = [("field", KnerfBakedBricks), ("grad", C.c_void_p)]
 
 
+class KnerfBakedRgba(C.Structure):
+    """struct knerf_baked_rgba (include/knerf.h): device backgrounds [n,3] and alphas [n] (either may be NULL), what the target's rgb is
+    stored over (0 or 1), the opacity loss's weight"""
+    _fields_ = [("background", C.c_void_p), ("alpha", C.c_void_p), ("stored_background", C.c_float), ("opacity", C.c_float)]
+
+
 BAKED_WHITE_BACKGROUND, BAKED_SKIP_EMPTY, BAKED_LANES_SHIFT = 1, 2, 8
 SPACING_LINEAR, SPACING_DISPARITY = 0, 1
 SPACINGS = {"linear": SPACING_LINEAR, "disparity": SPACING_DISPARITY}
@@ -177,6 +183,9 @@ SIGNATURES = {
                                          C.c_float, C.c_float, C.c_int, _F]),
     "knerf_baked_train_rays_ext": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _F, _F, _F, _F, C.c_float, C.c_float, _F, C.c_uint64,
                                              C.c_uint64, C.c_float, C.c_float, C.c_int, _F, C.POINTER(KnerfObjective), _F]),
+    "knerf_baked_train_rays_rgba": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _F, _F, _F, _F, C.c_float, C.c_float, _F, C.c_uint64,
+                                              C.c_uint64, C.c_float, C.c_float, C.c_int, _F, C.POINTER(KnerfObjective), _F,
+                                              C.POINTER(KnerfBakedRgba)]),
     "knerf_baked_train_apply": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _P, _P, _F, _F, _F, C.c_float, C.c_float, C.c_float, C.c_float,
                                           C.c_float]),
     "knerf_baked_train_tv": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _P, _F, C.c_float, C.c_float, C.c_float, _F]),
@@ -188,6 +197,9 @@ SIGNATURES = {
     "knerf_baked_bricks_train_rays_ext": (C.c_int, [_P, C.POINTER(KnerfBakedBricksTrain), _F, _F, _F, _F, C.c_float, C.c_float, _F,
                                                     C.c_uint64, C.c_uint64, C.c_float, C.c_float, C.c_int, _F,
                                                     C.POINTER(KnerfObjective), _F]),
+    "knerf_baked_bricks_train_rays_rgba": (C.c_int, [_P, C.POINTER(KnerfBakedBricksTrain), _F, _F, _F, _F, C.c_float, C.c_float, _F,
+                                                     C.c_uint64, C.c_uint64, C.c_float, C.c_float, C.c_int, _F,
+                                                     C.POINTER(KnerfObjective), _F, C.POINTER(KnerfBakedRgba)]),
     "knerf_baked_bricks_train_apply": (C.c_int, [_P, C.POINTER(KnerfBakedBricksTrain), _P, _F, _F, _F, C.c_float, C.c_float, C.c_float,
                                                  C.c_float, C.c_float]),
     "knerf_baked_resample_bricks_sigma": (C.c_int, [_P, C.POINTER(KnerfBakedBricks), C.POINTER(C.c_int32), C.c_float, _F]),

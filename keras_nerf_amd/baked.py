@@ -257,6 +257,47 @@ def check_render_args(step, termination, outputs, sh_degree=None, lanes_per_ray=
     return outs
 
 
+def check_colour(colour, what="background"):
+    """ValueError unless `colour` is three finite numbers in [0, 1]; returns them as a tuple of floats"""
+    try:
+        out = tuple(float(v) for v in colour)
+    except (TypeError, ValueError):
+        out = ()
+    if isinstance(colour, str) or len(out) != 3 or not all(np.isfinite(v) and 0.0 <= v <= 1.0 for v in out):
+        raise ValueError(f"{what} must be three finite numbers in [0, 1] (r, g, b), got {colour!r}")
+    return out
+
+
+def compose_background(image, opacity, background):
+    """clip(image + (1 - opacity) background, 0, 1): a render over the black background put over `background` ([3] or [n,3]) on the
+    host side, in the arrays' own type (torch tensors or NumPy arrays).  C <= O <= 1 up to rounding, so no kernel is needed."""
+    out = image + (1.0 - opacity)[..., None] * background
+    return out.clamp(0.0, 1.0) if hasattr(out, "clamp") else np.clip(out, 0.0, 1.0)
+
+
+def render_over(field, background, white_background, outputs, args, kwargs):
+    """field.render(*args, **kwargs) over `background`, a colour (r, g, b) or an [n,3] array of them with finite values in [0, 1]:
+    the black-background launch with image and opacity, then compose_background in torch.  ValueError together with
+    white_background=True (the flag is the launch's own white background) and for a background of another shape or range."""
+    import torch
+    if white_background:
+        raise ValueError("render takes background= or white_background=True, not both")
+    outs = check_render_args(None, 0.0, outputs)
+    want = tuple(dict.fromkeys(outs + ("image", "opacity"))) if "image" in outs else outs
+    res = field.render(*args, white_background=False, outputs=want, **kwargs)
+    if "image" in outs:
+        n = int(res["image"].shape[0])
+        if isinstance(background, torch.Tensor) or (isinstance(background, np.ndarray) and background.ndim == 2):
+            bg = background.to(device=field.device, dtype=torch.float32) if isinstance(background, torch.Tensor) else \
+                torch.as_tensor(np.asarray(background, dtype=np.float32)).to(field.device)
+            if tuple(bg.shape) != (n, 3) or not bool(((bg >= 0) & (bg <= 1)).all()):
+                raise ValueError(f"background must be [{n}, 3] with finite values in [0, 1], got shape {tuple(bg.shape)}")
+        else:
+            bg = torch.tensor(check_colour(background), device=field.device, dtype=torch.float32)
+        res["image"] = compose_background(res["image"], res["opacity"], bg)
+    return {k: v for k, v in res.items() if k in outs or k == "stats"}
+
+
 def _stream(device):
     import torch
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
@@ -468,14 +509,19 @@ class BakedField:
 
     # ---- rendering
     def render(self, origins, directions, near, far, step=None, white_background=False, termination=0.0,
-               outputs=("image", "depth", "opacity"), skip_empty=True, stats=False, lanes_per_ray=0):
+               outputs=("image", "depth", "opacity"), skip_empty=True, stats=False, lanes_per_ray=0, background=None):
         """Volume rendering of rays (origins, directions [N,3]; directions need not be unit vectors, t is in units of |d|) between
         near and far (scalars or [N]) with samples every `step` (None: half the smallest cell edge): {"image": [N,3], "depth": [N],
         "opacity": [N]} restricted to `outputs`, and with stats=True also "stats": int64 [2] device tensor (samples fetched, samples
         inside [near, far] of all rays).  The march is specified in include/knerf.h (knerf_baked_render).  skip_empty only saves
         work: the outputs are bit-identical without it.  lanes_per_ray is a tuning / diagnostic knob for tests and tools/baked_bench.py,
         not a promised part of the interface: it picks the kernel variant (0, the default: the library's choice; the variants differ
-        in summation order only)."""
+        in summation order only).  background: a colour (r, g, b) or an [N,3] tensor of them, values in [0, 1]: the image is
+        clip(image + (1 - opacity) background, 0, 1), composed in torch from the black-background launch (render_over; every other
+        output is that launch's); not together with white_background=True."""
+        if background is not None:
+            return render_over(self, background, white_background, outputs, (origins, directions, near, far),
+                               dict(step=step, termination=termination, skip_empty=skip_empty, stats=stats, lanes_per_ray=lanes_per_ray))
         import torch
         from . import _lib
         from .runtime import _ptr
@@ -500,7 +546,7 @@ class BakedField:
     # ---- optimisation against ray batches
     def optimizer(self, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
                   white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6, loss=None,
-                  regularizers=None):
+                  regularizers=None, background=None, opacity_loss=0.0, target_background=None, background_seed=0):
         """A BakedFieldOptimizer (baked_train.py) over a COPY of this field's records: Adam on sigma and the SH coefficients of the
         lattice points around the occupied cells (grown by `dilation` cells) against batches of rays and their colours; this field
         itself is left as it is.  step, white_background, termination, lanes_per_ray: how the optimiser marches, as in render().
@@ -509,10 +555,16 @@ class BakedField:
         columns), tv_epsilon (> 0) the constant under its root.  With both weights 0 a step is what it is without them.
         loss, regularizers: the objective, as NeRF.compile takes it (a name, a keras_nerf_amd.losses class, a Keras loss object or its
         serialised dict; losses.RayRegularizers(distortion=, opacity_entropy=) with the default nets): knerf_baked_train_rays_ext.
-        Default, and "mse" without a regulariser: the mean squared error, the launches and bits of an optimiser without them."""
+        Default, and "mse" without a regulariser: the mean squared error, the launches and bits of an optimiser without them.
+        background (None | "black" | "white" | "random" | (r, g, b)), opacity_loss (>= 0), target_background (None | "black" | "white":
+        what the targets' rgb is composited over; default: the white flag), background_seed: training on RGBA targets [n,4]
+        (knerf_baked_train_rays_rgba).  "white" equals white_background=True; "random" draws torch.rand((n, 3)) per
+        launch from a generator seeded once; opacity_loss weighs the mean of (O - alpha)^2.  "random" and opacity_loss > 0 need
+        [n,4] targets.  Without these keywords the optimiser makes exactly the calls it made before them."""
         from .baked_train import BakedFieldOptimizer
         return BakedFieldOptimizer(self, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
-                                   termination, lanes_per_ray, tv_sigma, tv_sh, tv_epsilon, loss, regularizers)
+                                   termination, lanes_per_ray, tv_sigma, tv_sh, tv_epsilon, loss, regularizers, background, opacity_loss,
+                                   target_background, background_seed)
 
     # ---- how the objective moves when a ray moves (baked_pose.py: refining camera poses)
     def ray_gradients(self, origins, directions, near, far, target, step=None, white_background=False, termination=0.0, n_total=None,
@@ -785,9 +837,12 @@ class BrickBakedField:
 
     # ---- rendering
     def render(self, origins, directions, near, far, step=None, white_background=False, termination=0.0,
-               outputs=("image", "depth", "opacity"), skip_empty=True, stats=False, lanes_per_ray=0):
+               outputs=("image", "depth", "opacity"), skip_empty=True, stats=False, lanes_per_ray=0, background=None):
         """BakedField.render through the brick table (knerf_baked_render_bricks): the same arguments, checks and result dict, and for
         a field that came from compact() the same bits."""
+        if background is not None:      # a colour or [n,3]: the black-background launch composed on the host (render_over)
+            return render_over(self, background, white_background, outputs, (origins, directions, near, far),
+                               dict(step=step, termination=termination, skip_empty=skip_empty, stats=stats, lanes_per_ray=lanes_per_ray))
         import torch
         from . import _lib
         from .runtime import _ptr

@@ -125,11 +125,11 @@ class BrickGridTrainer(BrickFieldOptimizer):
 
     def __init__(self, source, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
                  white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6, loss=None,
-                 regularizers=None):
+                 regularizers=None, background=None, opacity_loss=0.0, target_background=None, background_seed=0):
         self.tv_sigma, self.tv_sh, self.tv_epsilon = check_tv_args(tv_sigma, tv_sh, tv_epsilon)
         self.last_regularizer = None                                        # what the latest train_step's regularize() returned
         super().__init__(source, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
-                         termination, lanes_per_ray, loss, regularizers)
+                         termination, lanes_per_ray, loss, regularizers, background, opacity_loss, target_background, background_seed)
         self._keys = stored_keys(self.field._brick_of)
 
     # ---- the regulariser
@@ -181,11 +181,11 @@ class BrickGridTrainer(BrickFieldOptimizer):
                 break
             losses.append(self.train_step(o, d, near, far, target))
             tvs.append(torch.stack(self.last_regularizer))
-            if self.objective is not None:
+            if self._terms is not None:
                 terms.append(self.objective_terms())
         both = torch.stack(tvs).cpu() if tvs else torch.zeros((0, 2))
         out = {"loss": torch.stack(losses).cpu().tolist() if losses else [], "tv_sigma": both[:, 0].tolist(), "tv_sh": both[:, 1].tolist()}
-        return out if self.objective is None else fit_terms(out, terms)
+        return out if self.objective is None and not terms else fit_terms(out, terms)
 
     # ---- going sparse while training
     def counts(self):
@@ -232,14 +232,15 @@ class BrickGridTrainer(BrickFieldOptimizer):
 
 def grid_trainer(field, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
                  white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6, loss=None,
-                 regularizers=None):
+                 regularizers=None, background=None, opacity_loss=0.0, target_background=None, background_seed=0):
     """A BrickGridTrainer over a COPY of a BrickBakedField's bricks: baked_train.brick_optimizer with the dense optimiser's
     total-variation keywords (tv_sigma, tv_sh: the weights of mean tv_sigma and mean tv_q, both >= 0; tv_epsilon > 0 under the root) and
     prune().  With both weights 0 it trains exactly as brick_optimizer's BrickFieldOptimizer does.  loss, regularizers: the objective, as
-    BakedField.optimizer takes it."""
+    BakedField.optimizer takes it; background, opacity_loss, target_background, background_seed: the rgba keywords, as there."""
     _check_brick_field(field, "grid_trainer")
     return BrickGridTrainer(field, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
-                            termination, lanes_per_ray, tv_sigma, tv_sh, tv_epsilon, loss, regularizers)
+                            termination, lanes_per_ray, tv_sigma, tv_sh, tv_epsilon, loss, regularizers, background, opacity_loss,
+                            target_background, background_seed)
 
 
 def check_prune_every(prune_every):

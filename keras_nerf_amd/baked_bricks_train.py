@@ -22,8 +22,8 @@ import numpy as np
 
 from .baked import (BrickBakedField, _brick_points_device, _brick_slabs, _brick_table_device, _check, _ray_args, _stream, _unpack_words,
                     check_render_args, check_table_size, check_threshold, n_coefficients, record_bytes)
-from .baked_train import (bias_corrected_rate, check_objective, check_optimizer_args, check_target_shape, fit_terms,
-                          objective_value)
+from .baked_train import (RgbaTargets, bias_corrected_rate, check_objective, check_optimizer_args, fit_terms, objective_value,
+                          rgba_value)
 
 # lanes per ray knerf_baked_bricks_train_rays is built for, per degree: every variant of the dense gradient kernel builds without
 # scratch with brick addressing as well (DESIGN.md 2.23 has hipcc's register counts)
@@ -130,11 +130,15 @@ class BrickFieldOptimizer:
     total-variation regulariser.  `field` is the live BrickBakedField: it owns the records the optimiser rewrites, its bricks are the
     train bricks, its bits are the support, and it can be rendered at any time.  The source field is left as it is."""
 
+    _rgba = RgbaTargets()               # the rgba keywords at their defaults: every launch is what it was without them
+
     def __init__(self, source, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
-                 white_background=False, termination=0.0, lanes_per_ray=0, loss=None, regularizers=None):
+                 white_background=False, termination=0.0, lanes_per_ray=0, loss=None, regularizers=None, background=None,
+                 opacity_loss=0.0, target_background=None, background_seed=0):
         import torch
         from . import _lib
         from .runtime import occupancy_words_from_grid
+        self._rgba = RgbaTargets(white_background, background, opacity_loss, target_background, background_seed)
         self.objective = check_objective(loss, regularizers)               # None: the plain objective, the plain entry point
         self._terms = None                                                  # the last accumulate's means (objective_terms)
         if not isinstance(source, BrickBakedField):
@@ -144,7 +148,7 @@ class BrickFieldOptimizer:
             check_optimizer_args(learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation)
         check_render_args(step, termination, ("image",))
         self.lanes_per_ray = check_brick_lanes(source.sh_degree, lanes_per_ray)
-        self.step, self.white_background, self.termination = step, bool(white_background), float(termination)
+        self.step, self.white_background, self.termination = step, self._rgba.white, float(termination)
         self._width = 1 + 3 * n_coefficients(source.sh_degree)
         sigma = brick_sigma(source)[1]
         support = occupancy_words_from_grid(sigma, 0.0, self.dilation, what="brick_optimizer")
@@ -159,23 +163,34 @@ class BrickFieldOptimizer:
         self._c = _lib.KnerfBakedBricksTrain(self.field._c, C.c_void_p(self._grad.data_ptr()))
 
     # ---- the two launches
-    def accumulate(self, origins, directions, near, far, target, n_total=None):
+    def accumulate(self, origins, directions, near, far, target, n_total=None, background=None):
         """knerf_baked_bricks_train_rays: adds the gradient of the batch's mean squared error to the gradient rows and returns the
         loss, a float64 device scalar; n_total as BakedFieldOptimizer.accumulate.  Under an objective that is not the plain one:
-        knerf_baked_bricks_train_rays_ext and the objective's value, as there"""
+        knerf_baked_bricks_train_rays_ext and the objective's value, as there; with the rgba keywords, an [n,4] target or a per-call
+        background: knerf_baked_bricks_train_rays_rgba, as there"""
         import torch
         from . import _lib
         from .runtime import _f32, _ptr
         f = self.field
         o, d, n, h, (near_t, near0), (far_t, far0) = _ray_args(f, origins, directions, near, far, self.step)
-        tg = _f32(target, f.device)
-        check_target_shape(tuple(tg.shape), n)
+        tg, alpha = self._rgba.split_target(_f32(target, f.device), n)
+        rgba = self._rgba.record(alpha, n, f.device, background)
         norm = n if n_total is None else int(n_total)
         if norm < 1 and n:
             raise ValueError(f"n_total must be a positive ray count, got {n_total!r}")
         sq = torch.empty((n,), device=f.device, dtype=torch.float32)
         flags = (_lib.BAKED_WHITE_BACKGROUND if self.white_background else 0) | _lib.BAKED_SKIP_EMPTY | \
             (self.lanes_per_ray << _lib.BAKED_LANES_SHIFT)
+        if rgba is not None:
+            terms = torch.zeros((n, 5), device=f.device, dtype=torch.float32)
+            if n:
+                _check(_lib.load().knerf_baked_bricks_train_rays_rgba(_stream(f.device), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t),
+                                                                      _ptr(far_t), near0, far0, _ptr(tg), n, norm, h, self.termination,
+                                                                      flags, _ptr(sq),
+                                                                      C.byref(self.objective) if self.objective is not None else None,
+                                                                      _ptr(terms), C.byref(rgba)), "knerf_baked_bricks_train_rays_rgba")
+            loss, self._terms = rgba_value(self.objective, rgba, terms, norm)
+            return loss
         if self.objective is not None:
             terms = torch.zeros((n, 4), device=f.device, dtype=torch.float32)
             if n:
@@ -192,8 +207,14 @@ class BrickFieldOptimizer:
         return sq.to(torch.float64).sum() / (3.0 * max(norm, 1))
 
     def objective_terms(self):
-        """BakedFieldOptimizer.objective_terms: the four means of the last accumulate(), None under the plain objective"""
+        """BakedFieldOptimizer.objective_terms: the four means of the last accumulate() (five after an rgba launch), None under the
+        plain objective"""
         return None if self._terms is None else dict(self._terms)
+
+    @property
+    def last_background(self):
+        """the background tensor [n,3] of the last accumulate() (None: the launch used the flag's colour)"""
+        return self._rgba.last_background
 
     def apply(self):
         """knerf_baked_bricks_train_apply: one Adam step from the accumulated gradient, the slots' records rewritten, their gradient
@@ -226,10 +247,10 @@ class BrickFieldOptimizer:
             if steps is not None and k >= int(steps):
                 break
             losses.append(self.train_step(o, d, near, far, target))
-            if self.objective is not None:
+            if self._terms is not None:
                 terms.append(self.objective_terms())
         out = {"loss": torch.stack(losses).cpu().tolist() if losses else []}
-        return out if self.objective is None else fit_terms(out, terms)
+        return out if self.objective is None and not terms else fit_terms(out, terms)
 
     # ---- views for tests and tools
     def _dense(self, per_record, dtype):

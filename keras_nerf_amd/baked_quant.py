@@ -266,10 +266,14 @@ class QuantizedBrickField:
 
     # ---- rendering
     def render(self, origins, directions, near, far, step=None, white_background=False, termination=0.0,
-               outputs=("image", "depth", "opacity"), skip_empty=True, stats=False, lanes_per_ray=0):
+               outputs=("image", "depth", "opacity"), skip_empty=True, stats=False, lanes_per_ray=0, background=None):
         """BrickBakedField.render on the quantised records (knerf_baked_render_qbricks): the same arguments, checks and result dict.
         lanes_per_ray: 0 = the library's choice, 1 = one ray per lane (any degree; the bits of dequantize().render(lanes_per_ray=1)),
         2 (degree 2) / 4 (degree 3) = a group of lanes per ray; the variants differ in summation order only."""
+        if background is not None:      # a colour or [n,3]: the black-background launch composed on the host (render_over)
+            from .baked import render_over
+            return render_over(self, background, white_background, outputs, (origins, directions, near, far),
+                               dict(step=step, termination=termination, skip_empty=skip_empty, stats=stats, lanes_per_ray=lanes_per_ray))
         import torch
         from . import _lib
         from .runtime import _ptr

@@ -7,6 +7,8 @@ optional total-variation regulariser between the two, and the resampling behind 
 used for device memory, streams and the index plumbing of the construction only.  No step waits for the GPU.
 With loss= / regularizers= (the objective of NeRF.compile: keras_nerf_amd/losses.py) the gradient launch is knerf_baked_train_rays_ext,
 the same march under a robust loss and the distortion / opacity-entropy regularisers of a ray's weights.
+With background= / opacity_loss= and [n,4] targets (rgb and the photograph's alpha) it is knerf_baked_train_rays_rgba: prediction and
+photograph composited over a background per ray, and a loss between the ray's opacity and the alpha.
 
 What keeps skipping empty cells exact while the numbers move:
   support    the field's occupancy bits at the start, grown by `dilation` cells, fixed for the optimiser's lifetime: the bits of every
@@ -96,12 +98,112 @@ def objective_value(obj, terms, norm):
 
 
 def fit_terms(out, rows):
-    """adds the four lists of TERM_NAMES to a fit() dict from the per-step objective_terms() (one device read)"""
+    """adds the four lists of TERM_NAMES (with "opacity" behind them where the steps were rgba launches) to a fit() dict from the
+    per-step objective_terms() (one device read)"""
     import torch
-    both = torch.stack([torch.stack([r[k] for k in TERM_NAMES]) for r in rows]).cpu() if rows else torch.zeros((0, 4))
-    for i, k in enumerate(TERM_NAMES):
+    names = TERM_NAMES + (("opacity",) if rows and all("opacity" in r for r in rows) else ())
+    both = torch.stack([torch.stack([r[k] for k in names]) for r in rows]).cpu() if rows else torch.zeros((0, 4))
+    for i, k in enumerate(names):
         out[k] = both[:, i].tolist()
     return out
+
+
+BACKGROUNDS = ("black", "white", "random")
+
+
+class RgbaTargets:
+    """The keywords background=, opacity_loss=, target_background= and background_seed= of a grid optimiser, checked
+    on the host, and what an accumulate() makes of them: the knerf_baked_rgba record of a launch, or None where the launch is the one
+    the optimiser made before these keywords existed.
+      white          the launch's white-background flag: white_background=True or background="white"
+      mode           None (the flag's colour), "random" (torch.rand per launch) or "colour" (`colour` on every ray)
+      opacity        lambda_o, the weight of mean (O - alpha)^2
+      stored         0.0 or 1.0: what the targets' rgb is composited over (target_background; default: the flag)"""
+
+    def __init__(self, white_background=False, background=None, opacity_loss=0.0, target_background=None, background_seed=0):
+        from .baked import check_colour
+        white = bool(white_background)
+        self.mode, self.colour = None, None
+        if background is None or (isinstance(background, str) and background == "white"):
+            white = white or background == "white"
+        elif isinstance(background, str):
+            if background not in BACKGROUNDS:
+                raise ValueError(f"background must be None, one of {BACKGROUNDS} or a colour (r, g, b), got {background!r}")
+            if white:
+                raise ValueError(f"white_background=True contradicts background={background!r}")
+            self.mode = "random" if background == "random" else None
+        else:
+            self.colour = check_colour(background)
+            if white:
+                raise ValueError(f"white_background=True contradicts background={background!r}")
+            self.mode = "colour"
+        self.white = white
+        if isinstance(opacity_loss, bool) or not isinstance(opacity_loss, (int, float, np.floating, np.integer)) or \
+                not np.isfinite(np.float32(opacity_loss)) or float(opacity_loss) < 0.0:
+            raise ValueError(f"opacity_loss must be a finite number >= 0, got {opacity_loss!r}")
+        self.opacity = float(opacity_loss)
+        if target_background not in (None, "black", "white"):
+            raise ValueError(f'target_background must be None, "black" or "white", got {target_background!r}')
+        self.stored = float(white) if target_background is None else float(target_background == "white")
+        if isinstance(background_seed, bool) or not isinstance(background_seed, (int, np.integer)):
+            raise ValueError(f"background_seed must be an integer, got {background_seed!r}")
+        self.seed = int(background_seed)
+        self._generator = None
+        self.last_background = None
+
+    def split_target(self, tg, n):
+        """(rgb [n,3], alpha [n] | None) of a float32 target [n,3] or [n,4]; ValueError for another shape"""
+        if tg.dim() == 2 and tg.shape[1] == 4 and tg.shape[0] == n:
+            return tg[:, :3].contiguous(), tg[:, 3].contiguous()
+        if tg.dim() != 2 or tg.shape[1] != 3 or tg.shape[0] != n:
+            raise ValueError(f"target must be [{n}, 3] or [{n}, 4] (rgb, or rgb and alpha, per ray); got {tuple(tg.shape)}")
+        return tg, None
+
+    def record(self, alpha, n, device, background=None):
+        """The knerf_baked_rgba of one launch, or None: no alpha, no background but the flag's and no opacity loss.  `background`: the
+        per-call [n,3] override of accumulate().  The tensors the record points to are kept in last_background and on the record."""
+        import torch
+        from . import _lib
+        from .runtime import _ptr
+        bg = None
+        if background is not None:
+            if isinstance(background, torch.Tensor):
+                bg = background.to(device=device, dtype=torch.float32).contiguous()
+            else:
+                bg = torch.as_tensor(np.asarray(background, dtype=np.float32)).to(device).contiguous()
+            if tuple(bg.shape) != (n, 3) or not bool(((bg >= 0) & (bg <= 1)).all()):      # (a NaN fails both comparisons)
+                raise ValueError(f"background must be [{n}, 3] with finite values in [0, 1], got shape {tuple(bg.shape)}")
+        elif self.mode == "random":
+            if alpha is None:
+                raise ValueError('background="random" needs [n, 4] targets: a random background against an RGB-only target is wrong')
+            if self._generator is None:
+                self._generator = torch.Generator(device=device)
+                self._generator.manual_seed(self.seed)
+            bg = torch.rand((n, 3), device=device, dtype=torch.float32, generator=self._generator)
+        elif self.mode == "colour":
+            bg = torch.tensor(self.colour, device=device, dtype=torch.float32).expand(n, 3).contiguous()
+        if self.opacity > 0.0 and alpha is None:
+            raise ValueError("opacity_loss > 0 needs [n, 4] targets: the fourth column is the alpha the opacity is compared with")
+        self.last_background = bg
+        if bg is None and alpha is None and self.opacity == 0.0:
+            return None
+        rec = _lib.KnerfBakedRgba(_ptr(bg), _ptr(alpha), self.stored, self.opacity)
+        rec._keep = (bg, alpha)
+        return rec
+
+
+def rgba_value(obj, rec, terms, norm):
+    """objective_value for the per-ray terms [n, 5] of an rgba launch: the fifth mean is "opacity", the unweighted mean of
+    (O - alpha)^2, and the loss adds the record's weight times it.  obj None: the plain objective (mean squared error)."""
+    import torch
+    total = terms.to(torch.float64).sum(dim=0)
+    n = float(max(norm, 1))
+    means = {"photometric": total[0] / (3.0 * n), "mse": total[1] / (3.0 * n), "distortion": total[2] / n,
+             "opacity_entropy": total[3] / n, "opacity": total[4] / n}
+    loss = means["photometric"] + float(rec.opacity) * means["opacity"]
+    if obj is not None:
+        loss = loss + float(obj.distortion) * means["distortion"] + float(obj.opacity_entropy) * means["opacity_entropy"]
+    return loss, means
 
 
 def bias_corrected_rate(learning_rate: float, beta_1: float, beta_2: float, t: int) -> float:
@@ -113,12 +215,15 @@ class BakedFieldOptimizer:
     """Adam on the records of a baked field (BakedField.optimizer builds one).  `field` is the live field: it owns the records the
     optimiser rewrites, its bits are the support, and it can be rendered at any time."""
 
+    _rgba = RgbaTargets()               # the rgba keywords at their defaults: every launch is what it was without them
+
     def __init__(self, source, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
                  white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6, loss=None,
-                 regularizers=None):
+                 regularizers=None, background=None, opacity_loss=0.0, target_background=None, background_seed=0):
         import torch
         from . import _lib
         from .runtime import occupancy_words_from_grid
+        self._rgba = RgbaTargets(white_background, background, opacity_loss, target_background, background_seed)
         self.learning_rate_sigma, self.learning_rate_sh, self.beta_1, self.beta_2, self.epsilon, self.dilation = \
             check_optimizer_args(learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation)
         self.tv_sigma, self.tv_sh, self.tv_epsilon = check_tv_args(tv_sigma, tv_sh, tv_epsilon)
@@ -126,7 +231,7 @@ class BakedFieldOptimizer:
         self._terms = None                                                  # the last accumulate's means (objective_terms)
         self.last_regularizer = None                                        # what the latest train_step's regularize() returned
         check_render_args(step, termination, ("image",), source.sh_degree, lanes_per_ray)
-        self.step, self.white_background, self.termination, self.lanes_per_ray = step, bool(white_background), float(termination), \
+        self.step, self.white_background, self.termination, self.lanes_per_ray = step, self._rgba.white, float(termination), \
             int(lanes_per_ray)
         dev, res, deg = source.device, source.resolution, source.sh_degree
         K = n_coefficients(deg)
@@ -164,26 +269,39 @@ class BakedFieldOptimizer:
                                        self.n_slots)
 
     # ---- the two launches
-    def accumulate(self, origins, directions, near, far, target, n_total=None):
+    def accumulate(self, origins, directions, near, far, target, n_total=None, background=None):
         """knerf_baked_train_rays: adds the gradient of the batch's mean squared error to the gradient rows and returns the loss, a
         float64 device scalar (the per-ray errors are summed in float64 on the device; nothing waits).  n_total: the N of the loss
         1 / (3 N) sum (out - target)^2 when the batch is one part of several accumulated before apply() (default: this batch's rays).
         With a loss= / regularizers= objective that is not the plain one: knerf_baked_train_rays_ext, and the value returned is that
         of the function whose gradient was added, the mean of rho plus distortion x mean D plus opacity_entropy x mean H (the per-ray
-        terms summed in float64 on the device); objective_terms() then gives the four means."""
+        terms summed in float64 on the device); objective_terms() then gives the four means.
+        With the rgba keywords (background=, opacity_loss=), an [n,4] target (the fourth column is the photograph's alpha) or a
+        per-call `background` ([n,3], values in [0,1], overrides the keyword): knerf_baked_train_rays_rgba, the prediction and the
+        photograph composited over the ray's own background and opacity_loss x mean (O - alpha)^2 added; objective_terms() then has
+        a fifth mean, "opacity", and last_background is the background tensor of the launch."""
         import torch
         from . import _lib
         from .runtime import _f32, _ptr
         f = self.field
         o, d, n, h, (near_t, near0), (far_t, far0) = _ray_args(f, origins, directions, near, far, self.step)
-        tg = _f32(target, f.device)
-        check_target_shape(tuple(tg.shape), n)
+        tg, alpha = self._rgba.split_target(_f32(target, f.device), n)
+        rgba = self._rgba.record(alpha, n, f.device, background)
         norm = n if n_total is None else int(n_total)
         if norm < 1 and n:
             raise ValueError(f"n_total must be a positive ray count, got {n_total!r}")
         sq = torch.empty((n,), device=f.device, dtype=torch.float32)
         flags = (_lib.BAKED_WHITE_BACKGROUND if self.white_background else 0) | _lib.BAKED_SKIP_EMPTY | \
             (self.lanes_per_ray << _lib.BAKED_LANES_SHIFT)
+        if rgba is not None:
+            terms = torch.zeros((n, 5), device=f.device, dtype=torch.float32)
+            if n:
+                _check(_lib.load().knerf_baked_train_rays_rgba(_stream(f.device), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t),
+                                                               _ptr(far_t), near0, far0, _ptr(tg), n, norm, h, self.termination, flags,
+                                                               _ptr(sq), C.byref(self.objective) if self.objective is not None else None,
+                                                               _ptr(terms), C.byref(rgba)), "knerf_baked_train_rays_rgba")
+            loss, self._terms = rgba_value(self.objective, rgba, terms, norm)
+            return loss
         if self.objective is not None:
             terms = torch.zeros((n, 4), device=f.device, dtype=torch.float32)
             if n:
@@ -202,8 +320,14 @@ class BakedFieldOptimizer:
     def objective_terms(self):
         """{"photometric", "mse", "distortion", "opacity_entropy"}: the four means of the last accumulate() as float64 device scalars
         (photometric: the mean of rho over rays and channels; mse: of the squared difference; the other two: mean D and mean H over
-        the rays, unweighted).  None before any accumulate(), and always under the plain objective."""
+        the rays, unweighted); after an rgba launch also "opacity", the mean of (O - alpha)^2 over the rays, unweighted.  None before
+        any accumulate(), and always under the plain objective without the rgba keywords."""
         return None if self._terms is None else dict(self._terms)
+
+    @property
+    def last_background(self):
+        """the background tensor [n,3] of the last accumulate() (None: the launch used the flag's colour)"""
+        return self._rgba.last_background
 
     def apply(self):
         """knerf_baked_train_apply: one Adam step from the accumulated gradient, the records rewritten, the gradient zeroed"""
@@ -255,7 +379,7 @@ class BakedFieldOptimizer:
         not used: the baked march places its own samples), at most `steps` of them.  {"loss": [...]}: read from the device once, after
         the last step.  With a total-variation weight > 0 the dict also holds "tv_sigma" and "tv_sh": regularize()'s two means per
         step; with an objective that is not the plain one also "photometric", "mse", "distortion" and "opacity_entropy":
-        objective_terms() per step."""
+        objective_terms() per step, and "opacity" behind them where the steps were rgba launches."""
         import torch
         if steps is not None and (isinstance(steps, bool) or int(steps) != steps or int(steps) < 0):
             raise ValueError(f"steps must be a non-negative integer or None, got {steps!r}")
@@ -266,13 +390,13 @@ class BakedFieldOptimizer:
             losses.append(self.train_step(o, d, near, far, target))
             if self.regularized:
                 tvs.append(torch.stack(self.last_regularizer))
-            if self.objective is not None:
+            if self._terms is not None:
                 terms.append(self.objective_terms())
         out = {"loss": torch.stack(losses).cpu().tolist() if losses else []}
         if self.regularized:
             both = torch.stack(tvs).cpu() if tvs else torch.zeros((0, 2))
             out["tv_sigma"], out["tv_sh"] = both[:, 0].tolist(), both[:, 1].tolist()
-        if self.objective is not None:
+        if self.objective is not None or terms:
             fit_terms(out, terms)
         return out
 
@@ -317,18 +441,21 @@ class BakedFieldOptimizer:
 
 
 def brick_optimizer(field, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
-                    white_background=False, termination=0.0, lanes_per_ray=0, loss=None, regularizers=None):
+                    white_background=False, termination=0.0, lanes_per_ray=0, loss=None, regularizers=None, background=None,
+                    opacity_loss=0.0, target_background=None, background_seed=0):
     """A BrickFieldOptimizer (baked_bricks_train.py) over a COPY of a BrickBakedField's bricks: BakedField.optimizer for a field
     stored as sparse bricks, with the same arguments and meaning, optimised as it is (no table of the dense lattice's size is formed;
     finish() gives a BrickBakedField).  There is no total-variation regulariser here: tv_sigma, tv_sh and tv_epsilon belong to the
     dense optimiser and, on bricks, to baked_bricks_grow.grid_trainer, beside resample_bricks and fit_coarse_to_fine_bricks.
-    loss, regularizers: the objective, as BakedField.optimizer takes it (knerf_baked_bricks_train_rays_ext)."""
+    loss, regularizers: the objective, as BakedField.optimizer takes it (knerf_baked_bricks_train_rays_ext); background, opacity_loss,
+    target_background, background_seed: the rgba keywords, as there (knerf_baked_bricks_train_rays_rgba)."""
     from .baked_bricks_train import BrickFieldOptimizer
     from .baked_quant import QuantizedBrickField
     if isinstance(field, QuantizedBrickField):
         raise ValueError("a brick optimiser is built on a BrickBakedField, got a QuantizedBrickField: dequantize() gives one")
     return BrickFieldOptimizer(field, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
-                               termination, lanes_per_ray, loss, regularizers)
+                               termination, lanes_per_ray, loss, regularizers, background, opacity_loss, target_background,
+                               background_seed)
 
 
 def __getattr__(name):

@@ -29,6 +29,11 @@
 //                             prefix; the early exit of a ray with g = 0 holds only where no regulariser has a gradient.  Every line
 //                             of it stands under `if constexpr`: the plain instantiations are instruction for instruction what they
 //                             were.  tests/baked_objective_reference.py restates it in fp64.
+//                             Args::kRgba (Rgba<TrainArgs>, Rgba<BrickTrainArgs>): the extended kernel against RGBA photographs
+//                             (knerf_baked_train_rays_rgba) -- a background per ray where the flag's colour is
+//                             otherwise, the target recomposited over it with the photograph's alpha, and the opacity loss
+//                             (lambda_o / N)(O - alpha)^2, a function of O alone that enters r_j and the total like the entropy term.
+//                             Every line of it stands under `if constexpr (RGBA)`; tests/baked_rgba_reference.py restates it in fp64.
 //   Gradient rows: fp32 [n_slots][1 + 3 K], sigma first, then [k][c]: the columns of a record.  Every lane of a group holds the whole
 //   basis and the same dL/dr and dL/dsigma, so any lane can form any column: lane `sub` adds the columns sub, sub + G, ... of a
 //   corner's row, so that ONE atomic instruction of the group adds G consecutive floats (the memory side works in 64-byte requests;
@@ -47,7 +52,7 @@ namespace baked_train {
 using namespace baked;
 
 struct TrainArgs {
-    static constexpr bool kBrick = false, kExt = false;
+    static constexpr bool kBrick = false, kExt = false, kRgba = false;
     const uint4* rec;
     const unsigned* bits;
     int R[3];
@@ -64,7 +69,7 @@ struct TrainArgs {
 };
 
 struct BrickTrainArgs {
-    static constexpr bool kBrick = true, kExt = false;
+    static constexpr bool kBrick = true, kExt = false, kRgba = false;
     const uint4* rec;
     const int* brick_of;
     const unsigned* bits;
@@ -89,12 +94,27 @@ struct Objective {
     float huber_delta;
     float hscale;                                   // 1 / (3 N): g_c = rho'(d_c) hscale (for mse the bits of diff * gscale)
     float wd, we;                                   // lambda_d / N, lambda_e / N
-    float* terms;                                   // [n][4] or NULL
+    float* terms;                                   // [n][4] ([n][5] under kRgba) or NULL
 };
 template <class Base>
 struct Ext : Base {
     static constexpr bool kExt = true;
     Objective obj;
+};
+
+// Per-ray backgrounds and alpha targets (knerf_baked_train_rays_rgba): the extended argument struct with the rgba record
+// behind it.  Args::kRgba is the second compile-time switch; every line it adds stands under `if constexpr (Args::kRgba)` (RGBA), so the
+// plain and the extended instantiations are the text they were.  One rgba instantiation per <DEG, G, storage>.
+struct RgbaArgs {
+    const float* background;                        // [n][3] or NULL: the flag's colour on every channel
+    const float* alpha;                             // [n] or NULL: every alpha reads as 1 and the target is used as it is
+    float stored;                                   // 0 or 1: what the target's rgb is composited over
+    float wo;                                       // lambda_o / N
+};
+template <class Base>
+struct Rgba : Ext<Base> {
+    static constexpr bool kRgba = true;
+    RgbaArgs rgba;
 };
 
 // kExt: what the regularisers keep per ray, with m_j = (i_j - first) delta and the exclusive prefixes W_k = sum_{j<k} w_j (the march's own
@@ -110,6 +130,7 @@ struct RegState {
 // what the second march needs from the first: g = dL/dout (already gated by the output clamp) and the totals
 struct Totals {
     float g[3], img[3], opa, bg;
+    float b3[3];                                    // kRgba: the ray's background per channel, used where bg is otherwise
 };
 
 // One march of one ray over the samples [i, i1): the loop of baked_render_kernel without depth and statistics.  BWD = false: img / opa
@@ -123,7 +144,7 @@ __device__ __forceinline__ void march(const Args& a, const float (&o3)[3], const
                                       const float (&gy)[(1 + 3 * n_coeff(DEG) + G - 1) / G][3], float (&img)[3], float& opa, const Totals& tt,
                                       [[maybe_unused]] RegState& rs) {
     constexpr int K = n_coeff(DEG), NCH = rec_bytes(DEG) / 16, CPL = (NCH + G - 1) / G, W = 1 + 3 * K, NI = (W + G - 1) / G;
-    constexpr bool BRICK = Args::kBrick, EXT = Args::kExt;
+    constexpr bool BRICK = Args::kBrick, EXT = Args::kExt, RGBA = Args::kRgba;
     [[maybe_unused]] const long long sy = a.R[2], sx = (long long)a.R[1] * a.R[2];     // dense: the lattice's strides
     const int cyc = a.R[1] - 1, czc = a.R[2] - 1;
     [[maybe_unused]] const int L = brick_log2(a), inm = (1 << L) - 1;
@@ -257,8 +278,13 @@ __device__ __forceinline__ void march(const Args& a, const float (&o3)[3], const
                 const float rest_o = tt.opa - opa;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    A = __builtin_fmaf(tt.g[c], col[c] - tt.bg, A);
-                    later = __builtin_fmaf(tt.g[c], (tt.img[c] - img[c]) - tt.bg * rest_o, later);
+                    if constexpr (RGBA) {
+                        A = __builtin_fmaf(tt.g[c], col[c] - tt.b3[c], A);
+                        later = __builtin_fmaf(tt.g[c], (tt.img[c] - img[c]) - tt.b3[c] * rest_o, later);
+                    } else {
+                        A = __builtin_fmaf(tt.g[c], col[c] - tt.bg, A);
+                        later = __builtin_fmaf(tt.g[c], (tt.img[c] - img[c]) - tt.bg * rest_o, later);
+                    }
                     dr[c] = (raw[c] >= 0.f && raw[c] <= 1.f) ? tt.g[c] * w : 0.f;
                 }
                 if constexpr (EXT) {
@@ -307,7 +333,7 @@ __device__ __forceinline__ void march(const Args& a, const float (&o3)[3], const
 template <int DEG, int G, class Args>
 __global__ __launch_bounds__(kBlock) void baked_train_rays_kernel(Args a) {
     constexpr int K = n_coeff(DEG), NCH = rec_bytes(DEG) / 16, CPL = (NCH + G - 1) / G;
-    constexpr bool EXT = Args::kExt;
+    constexpr bool EXT = Args::kExt, RGBA = Args::kRgba;
     static_assert(G == 1 || G == 2 || G == 4, "a group is a lane, a pair or a quad");
     const long long gid = (long long)blockIdx.x * kBlock + threadIdx.x;
     const long long ray = gid / G;
@@ -393,12 +419,29 @@ __global__ __launch_bounds__(kBlock) void baked_train_rays_kernel(Args a) {
         const Objective& ob = a.obj;
         float diff[3], dv[3], rv[3];
         bool gate[3];
+        [[maybe_unused]] float al = 1.f;                    // RGBA: the ray's alpha; without an alpha array every ray reads 1
+        if constexpr (RGBA) {
+            // the photograph over the ray's own background: pre = C + b (1 - O) (b = 1: the bits of the white flag's 1 - O; b = 0: of C),
+            // tgt = target + (1 - alpha)(b - stored), not clipped
+            if (a.rgba.alpha) al = a.rgba.alpha[ray];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float pre = tt.img[c] + bg, out = fminf(fmaxf(pre, 0.f), 1.f);
-            diff[c] = out - a.target[ray * 3 + c];
-            gate[c] = pre >= 0.f && pre <= 1.f;
-            sq = sq + diff[c] * diff[c];
+            for (int c = 0; c < 3; ++c) {
+                tt.b3[c] = a.rgba.background ? a.rgba.background[ray * 3 + c] : tt.bg;
+                const float pre = tt.img[c] + tt.b3[c] * (1.f - tt.opa), out = fminf(fmaxf(pre, 0.f), 1.f);
+                float tgt = a.target[ray * 3 + c];
+                if (a.rgba.alpha) tgt = tgt + (1.f - al) * (tt.b3[c] - a.rgba.stored);
+                diff[c] = out - tgt;
+                gate[c] = pre >= 0.f && pre <= 1.f;
+                sq = sq + diff[c] * diff[c];
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float pre = tt.img[c] + bg, out = fminf(fmaxf(pre, 0.f), 1.f);
+                diff[c] = out - a.target[ray * 3 + c];
+                gate[c] = pre >= 0.f && pre <= 1.f;
+                sq = sq + diff[c] * diff[c];
+            }
         }
         // rho and rho' of the ray's three differences: the kind is the same for every ray of the launch, one uniform branch
         if (ob.kind == KNERF_LOSS_MAE) {
@@ -442,15 +485,21 @@ __global__ __launch_bounds__(kBlock) void baked_train_rays_kernel(Args a) {
         if (sub == 0) {
             if (a.sq_err) a.sq_err[ray] = sq;
             if (ob.terms) {
-                float* tr = ob.terms + ray * 4;
+                float* tr = ob.terms + ray * (RGBA ? 5 : 4);
                 tr[0] = (rv[0] + rv[1]) + rv[2]; tr[1] = sq; tr[2] = D; tr[3] = H;
+                if constexpr (RGBA) tr[4] = (O - al) * (O - al);
             }
         }
         rs.mt = rs.M; rs.wd = ob.wd; rs.re = ob.we * dH;
+        if constexpr (RGBA) {
+            // the opacity term (lambda_o / N)(O - alpha)^2 is a function of O alone, as H is: it enters r_j and the total through re
+            if (a.rgba.wo > 0.f) rs.re = rs.re + a.rgba.wo * (2.f * (O - al));
+        }
         rs.total = ob.wd * (2.f * D) + rs.re * O;
         rs.M = 0.f; rs.run = 0.f;
         // a ray whose g is 0 on every channel still has the regularisers' gradient once it fetched a sample
-        any = any || ((ob.wd > 0.f || ob.we > 0.f) && rs.first >= 0);
+        if constexpr (RGBA) any = any || ((ob.wd > 0.f || ob.we > 0.f || a.rgba.wo > 0.f) && rs.first >= 0);
+        else any = any || ((ob.wd > 0.f || ob.we > 0.f) && rs.first >= 0);
     }
     if (!any) return;                                       // the same on every lane of the group
     float img[3], opa;
@@ -476,6 +525,17 @@ hipError_t launch_rays(int deg, int lanes, const Args& a, const Objective* obj, 
     return launch_rays(deg, lanes, e, s);
 }
 
+// ... or with an rgba record the rgba one (it always carries an objective: that of mean squared error where the caller gave none)
+template <class Args>
+hipError_t launch_rays(int deg, int lanes, const Args& a, const Objective* obj, const RgbaArgs* rg, hipStream_t s) {
+    if (!rg) return launch_rays(deg, lanes, a, obj, s);
+    Rgba<Args> e{};
+    static_cast<Args&>(e) = a;
+    e.obj = *obj;
+    e.rgba = *rg;
+    return launch_rays(deg, lanes, e, s);
+}
+
 // the objective record of the _ext entry points.  false: KNERF_ERR_INVALID.  plain: NULL, or mse with both weights 0 (the call is then
 // the plain launch).  Otherwise `out` is what the extended kernel takes, with the weights and 1 / (3 N) formed in double
 static bool check_objective(const knerf_objective* o, uint64_t n_rays, uint64_t n_norm, float* terms, bool& plain, Objective& out) {
@@ -493,6 +553,30 @@ static bool check_objective(const knerf_objective* o, uint64_t n_rays, uint64_t 
     out.wd = (float)((double)o->distortion / N);
     out.we = (float)((double)o->opacity_entropy / N);
     out.terms = terms;
+    return true;
+}
+
+// the rgba record of the _rgba entry points.  false: KNERF_ERR_INVALID.  none: NULL, or no background, no alpha and weight 0 (the call is
+// then the _ext call).  Otherwise `out` is what the rgba kernel takes and `obj` is filled even for the plain objective (the rgba kernel
+// is an extended one: it evaluates mean squared error as the objective's kind 0)
+static bool check_rgba(const knerf_baked_rgba* r, const knerf_objective* objective, uint64_t n_rays, uint64_t n_norm, float* terms,
+                       bool& none, RgbaArgs& out, Objective& obj) {
+    none = true;
+    if (!r) return true;
+    if (!(r->stored_background == 0.f || r->stored_background == 1.f)) return false;
+    if (!(r->opacity >= 0.f) || !std::isfinite(r->opacity)) return false;
+    if (r->opacity > 0.f && !r->alpha) return false;
+    none = !r->background && !r->alpha && r->opacity == 0.f;
+    if (none) return true;
+    const double N = (double)(n_norm ? n_norm : (n_rays ? n_rays : 1));
+    out.background = r->background; out.alpha = r->alpha; out.stored = r->stored_background;
+    out.wo = (float)((double)r->opacity / N);
+    if (!objective) {
+        knerf_objective mse{};
+        mse.loss_kind = KNERF_LOSS_MSE;
+        bool plain = true;
+        return check_objective(&mse, n_rays, n_norm, terms, plain, obj);
+    }
     return true;
 }
 
@@ -630,16 +714,19 @@ static bool check_adam(float rate_sigma, float rate_sh, float beta_1, float beta
 
 using namespace knerf;
 
-// knerf_baked_train_rays (objective = NULL) and knerf_baked_train_rays_ext
+// knerf_baked_train_rays (objective = NULL), knerf_baked_train_rays_ext (rgba = NULL) and knerf_baked_train_rays_rgba
 static int train_rays(void* stream, const knerf_baked_train* train, const float* origins, const float* directions, const float* near,
                       const float* far, float near_all, float far_all, const float* target, uint64_t n_rays, uint64_t n_norm, float step,
-                      float termination, int flags, float* sq_err, const knerf_objective* objective, float* terms) {
+                      float termination, int flags, float* sq_err, const knerf_objective* objective, float* terms,
+                      const knerf_baked_rgba* rgba = nullptr) {
     unsigned long long points = 0;
     int lanes = 0;
-    bool plain = true;
+    bool plain = true, none = true;
     baked_train::Objective obj{};
+    baked_train::RgbaArgs rg{};
     if (!baked_train::check_state(train, points)) return KNERF_ERR_INVALID;
     if (!baked_train::check_objective(objective, n_rays, n_norm, terms, plain, obj)) return KNERF_ERR_INVALID;
+    if (!baked_train::check_rgba(rgba, objective, n_rays, n_norm, terms, none, rg, obj)) return KNERF_ERR_INVALID;
     const knerf_baked_field* field = &train->field;
     const int deg = field->sh_degree;
     if (!baked_train::check_train_rays(deg, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination,
@@ -653,7 +740,16 @@ static int train_rays(void* stream, const knerf_baked_train* train, const float*
     a.slot_of = train->slot_of; a.n_slots = (long long)train->n_slots;
     baked_train::set_rays(a, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination, flags,
                           train->grad, sq_err);
-    return baked_train::launch_rays(deg, lanes, a, plain ? nullptr : &obj, (hipStream_t)stream) == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
+    return baked_train::launch_rays(deg, lanes, a, plain && none ? nullptr : &obj, none ? nullptr : &rg, (hipStream_t)stream) == hipSuccess
+               ? KNERF_OK : KNERF_ERR_HIP;
+}
+
+extern "C" int knerf_baked_train_rays_rgba(void* stream, const knerf_baked_train* train, const float* origins, const float* directions,
+                                           const float* near, const float* far, float near_all, float far_all, const float* target,
+                                           uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags, float* sq_err,
+                                           const knerf_objective* objective, float* terms, const knerf_baked_rgba* rgba) {
+    return train_rays(stream, train, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination, flags,
+                      sq_err, objective, terms, rgba);
 }
 
 extern "C" int knerf_baked_train_rays(void* stream, const knerf_baked_train* train, const float* origins, const float* directions,
@@ -694,14 +790,16 @@ extern "C" int knerf_baked_train_apply(void* stream, const knerf_baked_train* tr
 static int bricks_train_rays(void* stream, const knerf_baked_bricks_train* train, const float* origins, const float* directions,
                              const float* near, const float* far, float near_all, float far_all, const float* target, uint64_t n_rays,
                              uint64_t n_norm, float step, float termination, int flags, float* sq_err, const knerf_objective* objective,
-                             float* terms) {
+                             float* terms, const knerf_baked_rgba* rgba = nullptr) {
     int B[3], lanes = 0;
     unsigned long long n_records = 0;
-    bool plain = true;
+    bool plain = true, none = true;
     baked_train::Objective obj{};
+    baked_train::RgbaArgs rg{};
     baked_train::BrickTrainArgs a{};
     if (!baked_train::check_state(train, B, a.scale, n_records)) return KNERF_ERR_INVALID;
     if (!baked_train::check_objective(objective, n_rays, n_norm, terms, plain, obj)) return KNERF_ERR_INVALID;
+    if (!baked_train::check_rgba(rgba, objective, n_rays, n_norm, terms, none, rg, obj)) return KNERF_ERR_INVALID;
     const knerf_baked_bricks* field = &train->field;
     const int deg = field->sh_degree;
     // every lane variant of knerf_baked_train_rays exists here too: each builds without scratch (DESIGN.md 2.23 has hipcc's counts)
@@ -714,7 +812,17 @@ static int bricks_train_rays(void* stream, const knerf_baked_bricks_train* train
     a.L = field->brick_log2; a.By = B[1]; a.Bz = B[2]; a.n_bricks = (long long)field->n_bricks;
     baked_train::set_rays(a, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination, flags,
                           train->grad, sq_err);
-    return baked_train::launch_rays(deg, lanes, a, plain ? nullptr : &obj, (hipStream_t)stream) == hipSuccess ? KNERF_OK : KNERF_ERR_HIP;
+    return baked_train::launch_rays(deg, lanes, a, plain && none ? nullptr : &obj, none ? nullptr : &rg, (hipStream_t)stream) == hipSuccess
+               ? KNERF_OK : KNERF_ERR_HIP;
+}
+
+extern "C" int knerf_baked_bricks_train_rays_rgba(void* stream, const knerf_baked_bricks_train* train, const float* origins,
+                                                  const float* directions, const float* near, const float* far, float near_all,
+                                                  float far_all, const float* target, uint64_t n_rays, uint64_t n_norm, float step,
+                                                  float termination, int flags, float* sq_err, const knerf_objective* objective,
+                                                  float* terms, const knerf_baked_rgba* rgba) {
+    return bricks_train_rays(stream, train, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination,
+                             flags, sq_err, objective, terms, rgba);
 }
 
 extern "C" int knerf_baked_bricks_train_rays(void* stream, const knerf_baked_bricks_train* train, const float* origins,

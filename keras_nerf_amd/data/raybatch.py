@@ -95,9 +95,13 @@ class RayBatchDataset:
 
     Without `steps_per_epoch` an epoch is one permutation of the P pixels: P // rays_per_step steps, the tail of fewer than
     rays_per_step pixels dropped (the next epoch is another permutation, so no pixel is starved).  With it, epochs of that many
-    steps continue through the permutation and start the next one when fewer than rays_per_step positions are left."""
+    steps continue through the permutation and start the next one when fewer than rays_per_step positions are left.
 
-    def __init__(self, images, rays_per_step: int, seed: int = 0, steps_per_epoch: int = None):
+    alpha=True: the target is [n,4], the images' alpha behind the colour (gathered from the resident images by the flat pixel index the
+    draw returns), for the grid optimisers' RGBA training; o, d, t and the colour are what they are without it."""
+
+    def __init__(self, images, rays_per_step: int, seed: int = 0, steps_per_epoch: int = None, alpha: bool = False):
+        self.alpha = bool(alpha)
         self._images = images                                  # the RayImageDataset whose pixels are drawn
         self.rays_per_step, self.seed = int(rays_per_step), int(seed)
         self.steps_per_epoch = None if steps_per_epoch is None else int(steps_per_epoch)
@@ -193,9 +197,14 @@ class RayBatchDataset:
                 stream = self._drawn * world + rank
                 self._drawn += 1
                 self.last_draw = (perm, first, n)              # what the batch just yielded holds: positions [first, first + n) of `perm`
-                if self._cameras is None:
+                if self._cameras is None and not self.alpha:
                     o, d, t, target = draw_ray_batch(dev, cams, rg.focal_length, rg.near, rg.far, rg.n_sample, self.seed, perm, first, n,
                                                      noise_stream=stream, **extra)
+                elif self._cameras is None:
+                    import torch
+                    o, d, t, target, index = draw_ray_batch(dev, cams, rg.focal_length, rg.near, rg.far, rg.n_sample, self.seed, perm,
+                                                            first, n, noise_stream=stream, want_index=True, **extra)
+                    target = torch.cat([target, dev.reshape(-1, 4)[index.to(torch.int64), 3:4]], dim=1)
                 else:
                     import torch
                     now = self._cameras()
@@ -205,5 +214,7 @@ class RayBatchDataset:
                     o, d, t, target, index = draw_ray_batch(dev, now.contiguous(), rg.focal_length, rg.near, rg.far, rg.n_sample,
                                                             self.seed, perm, first, n, noise_stream=stream, want_index=True, **extra)
                     self.last_view = torch.div(index, self._rows * self._cols, rounding_mode="floor").to(torch.int32)
+                    if self.alpha:
+                        target = torch.cat([target, dev.reshape(-1, 4)[index.to(torch.int64), 3:4]], dim=1)
                 yield target, (o, d, t)
         return gen()
