@@ -562,16 +562,19 @@ class BakedField:
         launch from a generator seeded once; opacity_loss weighs the mean of (O - alpha)^2.  "random" and opacity_loss > 0 need
         [n,4] targets.  Without these keywords the optimiser makes exactly the calls it made before them."""
         from .baked_train import BakedFieldOptimizer
-        return BakedFieldOptimizer(self, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
-                                   termination, lanes_per_ray, tv_sigma, tv_sh, tv_epsilon, loss, regularizers, background, opacity_loss,
-                                   target_background, background_seed)
+        return BakedFieldOptimizer(self, learning_rate_sigma=learning_rate_sigma, learning_rate_sh=learning_rate_sh, beta_1=beta_1,
+                                   beta_2=beta_2, epsilon=epsilon, dilation=dilation, step=step, white_background=white_background,
+                                   termination=termination, lanes_per_ray=lanes_per_ray, tv_sigma=tv_sigma, tv_sh=tv_sh,
+                                   tv_epsilon=tv_epsilon, loss=loss, regularizers=regularizers, background=background,
+                                   opacity_loss=opacity_loss, target_background=target_background, background_seed=background_seed)
 
     # ---- how the objective moves when a ray moves (baked_pose.py: refining camera poses)
     def ray_gradients(self, origins, directions, near, far, target, step=None, white_background=False, termination=0.0, n_total=None,
                       lanes_per_ray=0):
         """baked_pose.ray_gradients(self, ...): (grad_origin [N,3], grad_direction [N,3], loss) of the squared error against `target`"""
         from .baked_pose import ray_gradients
-        return ray_gradients(self, origins, directions, near, far, target, step, white_background, termination, n_total, lanes_per_ray)
+        return ray_gradients(self, origins, directions, near, far, target, step=step, white_background=white_background,
+                             termination=termination, n_total=n_total, lanes_per_ray=lanes_per_ray)
 
     # ---- the field at points, on grids and as a mesh (baked_query.py)
     def query(self, points, directions=None, gradient=False, lanes_per_point=0):
@@ -869,7 +872,8 @@ class BrickBakedField:
                       lanes_per_ray=0):
         """baked_pose.ray_gradients(self, ...): (grad_origin [N,3], grad_direction [N,3], loss) of the squared error against `target`"""
         from .baked_pose import ray_gradients
-        return ray_gradients(self, origins, directions, near, far, target, step, white_background, termination, n_total, lanes_per_ray)
+        return ray_gradients(self, origins, directions, near, far, target, step=step, white_background=white_background,
+                             termination=termination, n_total=n_total, lanes_per_ray=lanes_per_ray)
 
     # ---- the field at points, on grids and as a mesh (baked_query.py): BakedField.query / density_grid / extract_mesh on this storage
     def query(self, points, directions=None, gradient=False, lanes_per_point=0):

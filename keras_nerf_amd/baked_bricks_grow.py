@@ -15,12 +15,10 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
-
 from .baked import (BakedField, BrickBakedField, _brick_points_device, _brick_slabs, _brick_table_device, _check, _stream, _unpack_words,
                     check_brick, check_lattice_spec, check_table_size, check_threshold, record_bytes)
 from .baked_bricks_train import FLAG_SIGMA, FLAG_SLOT, BrickFieldOptimizer, brick_sigma, train_state
-from .baked_train import check_optimizer_args, check_stages, check_tv_args, fit_terms
+from .baked_train import TotalVariation, check_optimizer_args, check_stages, is_number
 
 CARRY_ROWS = 1 << 22          # rows whose columns move in one piece when a prune carries the optimiser's state
 
@@ -118,74 +116,29 @@ def carry_state(old_row, sigma, old, new):
             new[r0:r0 + CARRY_ROWS][at, 0] = old[was[at].to(torch.int64), 0]
 
 
-class BrickGridTrainer(BrickFieldOptimizer):
+class BrickGridTrainer(TotalVariation, BrickFieldOptimizer):
     """A BrickFieldOptimizer that can grow a grid (grid_trainer builds one): the total-variation regulariser of the dense optimiser
-    (regularized, tv_weights(), regularize(), with the same meaning and, for the same values, the same gradient bits) and prune(), which
-    re-supports the trainer on what the field has become and keeps Adam's state where it can."""
+    (baked_train.TotalVariation: regularized, tv_weights(), regularize(), with the same meaning and, for the same values, the same
+    gradient bits; train_step() runs it between accumulate() and apply() when a weight is > 0 and fit() then returns "tv_sigma" and
+    "tv_sh" as well; with both weights 0 a step is BrickFieldOptimizer's, no further launch) and prune(), which re-supports the
+    trainer on what the field has become and keeps Adam's state where it can."""
 
     def __init__(self, source, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
                  white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6, loss=None,
                  regularizers=None, background=None, opacity_loss=0.0, target_background=None, background_seed=0):
-        self.tv_sigma, self.tv_sh, self.tv_epsilon = check_tv_args(tv_sigma, tv_sh, tv_epsilon)
-        self.last_regularizer = None                                        # what the latest train_step's regularize() returned
-        super().__init__(source, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
-                         termination, lanes_per_ray, loss, regularizers, background, opacity_loss, target_background, background_seed)
+        self._set_tv(tv_sigma, tv_sh, tv_epsilon)
+        super().__init__(source, learning_rate_sigma=learning_rate_sigma, learning_rate_sh=learning_rate_sh, beta_1=beta_1, beta_2=beta_2,
+                         epsilon=epsilon, dilation=dilation, step=step, white_background=white_background, termination=termination,
+                         lanes_per_ray=lanes_per_ray, loss=loss, regularizers=regularizers, background=background,
+                         opacity_loss=opacity_loss, target_background=target_background, background_seed=background_seed)
+
+    def _build(self, source) -> None:
+        super()._build(source)
         self._keys = stored_keys(self.field._brick_of)
 
-    # ---- the regulariser
-    @property
-    def regularized(self) -> bool:
-        """whether a total-variation weight is > 0: train_step then runs regularize() between accumulate() and apply()"""
-        return self.tv_sigma > 0.0 or self.tv_sh > 0.0
-
-    def tv_weights(self):
-        """the weights per term knerf_baked_bricks_train_tv takes, formed in double: tv_sigma / n_slots and tv_sh / (3 K n_slots)"""
-        return self.tv_sigma / float(self.n_slots), self.tv_sh / (float(self._width - 1) * float(self.n_slots))
-
-    def regularize(self):
-        """knerf_baked_bricks_train_tv, one launch: adds the gradient of R = tv_sigma mean_p tv_sigma(p) + tv_sh mean_{p,q} tv_q(p) (the
-        total variation of the master values over the slots) to the gradient rows and returns the two means, unweighted, as float64
-        device scalars (the per-record terms are summed in float64 on the device; nothing waits)."""
-        import torch
-        from . import _lib
+    def _tv_launch(self):
         from .runtime import _ptr
-        dev = self.field.device
-        tv = torch.empty((int(self._flags.numel()), 2), device=dev, dtype=torch.float32)
-        ws, wc = self.tv_weights()
-        _check(_lib.load().knerf_baked_bricks_train_tv(_stream(dev), C.byref(self._c), _ptr(self._keys), _ptr(self._flags), _ptr(self._master),
-                                                       ws, wc, self.tv_epsilon, _ptr(tv)), "knerf_baked_bricks_train_tv")
-        total = tv.to(torch.float64).sum(dim=0)                              # (a record that is no slot holds (0, 0))
-        return total[0] / float(self.n_slots), total[1] / (float(self._width - 1) * float(self.n_slots))
-
-    def train_step(self, origins, directions, near, far, target):
-        """accumulate, regularize (only when a total-variation weight is > 0; its return value is kept in last_regularizer), apply;
-        returns the batch's loss before the step (float64 device scalar, the data term alone).  With both weights 0 this is
-        BrickFieldOptimizer.train_step: no further launch."""
-        loss = self.accumulate(origins, directions, near, far, target)
-        if self.regularized:
-            self.last_regularizer = self.regularize()
-        self.apply()
-        return loss
-
-    def fit(self, batches, near, far, steps=None):
-        """BrickFieldOptimizer.fit; with a total-variation weight > 0 the dict also holds "tv_sigma" and "tv_sh": regularize()'s two
-        means per step"""
-        import torch
-        if not self.regularized:
-            return super().fit(batches, near, far, steps)
-        if steps is not None and (isinstance(steps, bool) or int(steps) != steps or int(steps) < 0):
-            raise ValueError(f"steps must be a non-negative integer or None, got {steps!r}")
-        losses, tvs, terms = [], [], []
-        for k, (target, (o, d, _t)) in enumerate(batches):
-            if steps is not None and k >= int(steps):
-                break
-            losses.append(self.train_step(o, d, near, far, target))
-            tvs.append(torch.stack(self.last_regularizer))
-            if self._terms is not None:
-                terms.append(self.objective_terms())
-        both = torch.stack(tvs).cpu() if tvs else torch.zeros((0, 2))
-        out = {"loss": torch.stack(losses).cpu().tolist() if losses else [], "tv_sigma": both[:, 0].tolist(), "tv_sh": both[:, 1].tolist()}
-        return out if self.objective is None and not terms else fit_terms(out, terms)
+        return "knerf_baked_bricks_train_tv", (_ptr(self._keys), _ptr(self._flags), _ptr(self._master)), int(self._flags.numel())
 
     # ---- going sparse while training
     def counts(self):
@@ -204,7 +157,6 @@ class BrickGridTrainer(BrickFieldOptimizer):
         and the new state exist side by side.  ValueError, with the trainer unchanged, when nothing would be left to optimise.
         Returns {"before": counts(), "after": counts()}."""
         import torch
-        from . import _lib
         from .runtime import occupancy_words_from_grid
         dil = self.dilation if dilation is None else check_optimizer_args(self.learning_rate_sigma, self.learning_rate_sh, self.beta_1,
                                                                           self.beta_2, self.epsilon, dilation)[5]
@@ -226,7 +178,7 @@ class BrickGridTrainer(BrickFieldOptimizer):
         self._grad = torch.zeros_like(master)
         self._keys = stored_keys(brick_of)
         self.n_slots = int((flags & FLAG_SLOT).sum())
-        self._c = _lib.KnerfBakedBricksTrain(self.field._c, C.c_void_p(self._grad.data_ptr()))
+        self._c = self._state()
         return {"before": before, "after": self.counts()}
 
 
@@ -238,16 +190,18 @@ def grid_trainer(field, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_
     prune().  With both weights 0 it trains exactly as brick_optimizer's BrickFieldOptimizer does.  loss, regularizers: the objective, as
     BakedField.optimizer takes it; background, opacity_loss, target_background, background_seed: the rgba keywords, as there."""
     _check_brick_field(field, "grid_trainer")
-    return BrickGridTrainer(field, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
-                            termination, lanes_per_ray, tv_sigma, tv_sh, tv_epsilon, loss, regularizers, background, opacity_loss,
-                            target_background, background_seed)
+    return BrickGridTrainer(field, learning_rate_sigma=learning_rate_sigma, learning_rate_sh=learning_rate_sh, beta_1=beta_1, beta_2=beta_2,
+                            epsilon=epsilon, dilation=dilation, step=step, white_background=white_background, termination=termination,
+                            lanes_per_ray=lanes_per_ray, tv_sigma=tv_sigma, tv_sh=tv_sh, tv_epsilon=tv_epsilon, loss=loss,
+                            regularizers=regularizers, background=background, opacity_loss=opacity_loss,
+                            target_background=target_background, background_seed=background_seed)
 
 
 def check_prune_every(prune_every):
     """ValueError unless prune_every is None or a positive integer; returns it as None or int"""
     if prune_every is None:
         return None
-    if isinstance(prune_every, bool) or not isinstance(prune_every, (int, np.integer)) or int(prune_every) < 1:
+    if not is_number(prune_every, integer=True) or int(prune_every) < 1:
         raise ValueError(f"prune_every must be a positive integer or None, got {prune_every!r}")
     return int(prune_every)
 

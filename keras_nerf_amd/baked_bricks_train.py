@@ -20,10 +20,10 @@ import ctypes as C
 
 import numpy as np
 
-from .baked import (BrickBakedField, _brick_points_device, _brick_slabs, _brick_table_device, _check, _ray_args, _stream, _unpack_words,
-                    check_render_args, check_table_size, check_threshold, n_coefficients, record_bytes)
-from .baked_train import (RgbaTargets, bias_corrected_rate, check_objective, check_optimizer_args, fit_terms, objective_value,
-                          rgba_value)
+from .baked import (BrickBakedField, _brick_points_device, _brick_slabs, _brick_table_device, _stream, _unpack_words, check_table_size,
+                    check_threshold, n_coefficients, record_bytes)
+from .baked_train import GridOptimizer, is_number, slot_masks        # (the launches run in GridOptimizer, on baked_train._stream;
+                                                                      # _stream above stays this module's name for the same lookup)
 
 # lanes per ray knerf_baked_bricks_train_rays is built for, per degree: every variant of the dense gradient kernel builds without
 # scratch with brick addressing as well (DESIGN.md 2.23 has hipcc's register counts)
@@ -34,8 +34,7 @@ FLAG_SLOT, FLAG_SIGMA = 1, 2            # bits of a record's flag: a corner of a
 
 def check_brick_lanes(sh_degree, lanes_per_ray) -> int:
     """ValueError unless lanes_per_ray is 0 (the library's default) or one of BRICK_TRAIN_VARIANTS[sh_degree]"""
-    if isinstance(lanes_per_ray, bool) or not isinstance(lanes_per_ray, (int, np.integer)) or \
-            (int(lanes_per_ray) != 0 and int(lanes_per_ray) not in BRICK_TRAIN_VARIANTS[sh_degree]):
+    if not is_number(lanes_per_ray, integer=True) or (int(lanes_per_ray) != 0 and int(lanes_per_ray) not in BRICK_TRAIN_VARIANTS[sh_degree]):
         raise ValueError(f"lanes_per_ray must be 0 (default) or one of {BRICK_TRAIN_VARIANTS[sh_degree]} for a brick optimiser of "
                          f"sh_degree {sh_degree}, got {lanes_per_ray!r}")
     return int(lanes_per_ray)
@@ -72,16 +71,7 @@ def train_state(source, support):
     if n == 0:
         raise ValueError("the field has no occupied cell: there is nothing to optimise")
     check_table_size(n * b3, deg)
-    cx, cy, cz = occ.shape
-    touched = torch.zeros(res, device=dev, dtype=torch.bool)
-    # a point's sigma is trainable when none of its 8 adjacent cells is a lattice cell outside the support
-    free = torch.ones(res, device=dev, dtype=torch.bool)
-    for i in (0, 1):
-        for j in (0, 1):
-            for k in (0, 1):
-                touched[i:i + cx, j:j + cy, k:k + cz] |= occ
-                free[i:i + cx, j:j + cy, k:k + cz] &= occ
-    touched, free = touched.reshape(-1), free.reshape(-1)
+    touched, free = (mask.reshape(-1) for mask in slot_masks(occ, res))
     records = torch.zeros((n, b3, rb), device=dev, dtype=torch.uint8)
     flags = torch.zeros((n * b3,), device=dev, dtype=torch.uint8)
     master = torch.zeros((n * b3, 1 + 3 * K), device=dev, dtype=torch.float32)
@@ -125,132 +115,38 @@ def kept_bricks(live, sigma_stored, words, sigma_threshold):
     return BrickBakedField(records, brick_of, words, res, live.bounds, deg, b, sigma_threshold)
 
 
-class BrickFieldOptimizer:
+class BrickFieldOptimizer(GridOptimizer):
     """Adam on the records of a brick baked field (baked_train.brick_optimizer builds one): BakedFieldOptimizer's surface without the
-    total-variation regulariser.  `field` is the live BrickBakedField: it owns the records the optimiser rewrites, its bricks are the
-    train bricks, its bits are the support, and it can be rendered at any time.  The source field is left as it is."""
+    total-variation regulariser (the keywords, accumulate(), apply(), train_step() and fit() are baked_train.GridOptimizer's, over
+    knerf_baked_bricks_train_rays[_ext|_rgba] and knerf_baked_bricks_train_apply).  `field` is the live BrickBakedField: it owns the
+    records the optimiser rewrites, its bricks are the train bricks, its bits are the support, and it can be rendered at any time.
+    The source field is left as it is."""
 
-    _rgba = RgbaTargets()               # the rgba keywords at their defaults: every launch is what it was without them
+    _train_rays = "knerf_baked_bricks_train_rays"
+    _check_lanes = staticmethod(check_brick_lanes)
 
-    def __init__(self, source, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
-                 white_background=False, termination=0.0, lanes_per_ray=0, loss=None, regularizers=None, background=None,
-                 opacity_loss=0.0, target_background=None, background_seed=0):
-        import torch
-        from . import _lib
-        from .runtime import occupancy_words_from_grid
-        self._rgba = RgbaTargets(white_background, background, opacity_loss, target_background, background_seed)
-        self.objective = check_objective(loss, regularizers)               # None: the plain objective, the plain entry point
-        self._terms = None                                                  # the last accumulate's means (objective_terms)
+    def _check_source(self, source) -> None:
         if not isinstance(source, BrickBakedField):
             raise ValueError(f"a brick optimiser is built on a BrickBakedField, got {type(source).__name__} (a BakedField has "
                              f"optimizer(), the dense BakedFieldOptimizer)")
-        self.learning_rate_sigma, self.learning_rate_sh, self.beta_1, self.beta_2, self.epsilon, self.dilation = \
-            check_optimizer_args(learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation)
-        check_render_args(step, termination, ("image",))
-        self.lanes_per_ray = check_brick_lanes(source.sh_degree, lanes_per_ray)
-        self.step, self.white_background, self.termination = step, self._rgba.white, float(termination)
-        self._width = 1 + 3 * n_coefficients(source.sh_degree)
+
+    def _build(self, source) -> None:
+        from .runtime import occupancy_words_from_grid
         sigma = brick_sigma(source)[1]
         support = occupancy_words_from_grid(sigma, 0.0, self.dilation, what="brick_optimizer")
         del sigma
         brick_of, records, self._flags, self._master = train_state(source, support)
         self.field = BrickBakedField(records, brick_of, support, source.resolution, source.bounds, source.sh_degree, source.brick,
                                      source.sigma_threshold)
-        self._grad = torch.zeros_like(self._master)
-        self._m, self._v = torch.zeros_like(self._master), torch.zeros_like(self._master)
         self.n_slots = int((self._flags & FLAG_SLOT).sum())                 # the one host read besides the brick count
-        self.iterations = 0                                                 # steps applied; the host's count, no device read
-        self._c = _lib.KnerfBakedBricksTrain(self.field._c, C.c_void_p(self._grad.data_ptr()))
 
-    # ---- the two launches
-    def accumulate(self, origins, directions, near, far, target, n_total=None, background=None):
-        """knerf_baked_bricks_train_rays: adds the gradient of the batch's mean squared error to the gradient rows and returns the
-        loss, a float64 device scalar; n_total as BakedFieldOptimizer.accumulate.  Under an objective that is not the plain one:
-        knerf_baked_bricks_train_rays_ext and the objective's value, as there; with the rgba keywords, an [n,4] target or a per-call
-        background: knerf_baked_bricks_train_rays_rgba, as there"""
-        import torch
+    def _state(self):
         from . import _lib
-        from .runtime import _f32, _ptr
-        f = self.field
-        o, d, n, h, (near_t, near0), (far_t, far0) = _ray_args(f, origins, directions, near, far, self.step)
-        tg, alpha = self._rgba.split_target(_f32(target, f.device), n)
-        rgba = self._rgba.record(alpha, n, f.device, background)
-        norm = n if n_total is None else int(n_total)
-        if norm < 1 and n:
-            raise ValueError(f"n_total must be a positive ray count, got {n_total!r}")
-        sq = torch.empty((n,), device=f.device, dtype=torch.float32)
-        flags = (_lib.BAKED_WHITE_BACKGROUND if self.white_background else 0) | _lib.BAKED_SKIP_EMPTY | \
-            (self.lanes_per_ray << _lib.BAKED_LANES_SHIFT)
-        if rgba is not None:
-            terms = torch.zeros((n, 5), device=f.device, dtype=torch.float32)
-            if n:
-                _check(_lib.load().knerf_baked_bricks_train_rays_rgba(_stream(f.device), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t),
-                                                                      _ptr(far_t), near0, far0, _ptr(tg), n, norm, h, self.termination,
-                                                                      flags, _ptr(sq),
-                                                                      C.byref(self.objective) if self.objective is not None else None,
-                                                                      _ptr(terms), C.byref(rgba)), "knerf_baked_bricks_train_rays_rgba")
-            loss, self._terms = rgba_value(self.objective, rgba, terms, norm)
-            return loss
-        if self.objective is not None:
-            terms = torch.zeros((n, 4), device=f.device, dtype=torch.float32)
-            if n:
-                _check(_lib.load().knerf_baked_bricks_train_rays_ext(_stream(f.device), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t),
-                                                                     _ptr(far_t), near0, far0, _ptr(tg), n, norm, h, self.termination,
-                                                                     flags, _ptr(sq), C.byref(self.objective), _ptr(terms)),
-                       "knerf_baked_bricks_train_rays_ext")
-            loss, self._terms = objective_value(self.objective, terms, norm)
-            return loss
-        if n:
-            _check(_lib.load().knerf_baked_bricks_train_rays(_stream(f.device), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t),
-                                                             _ptr(far_t), near0, far0, _ptr(tg), n, norm, h, self.termination, flags,
-                                                             _ptr(sq)), "knerf_baked_bricks_train_rays")
-        return sq.to(torch.float64).sum() / (3.0 * max(norm, 1))
+        return _lib.KnerfBakedBricksTrain(self.field._c, C.c_void_p(self._grad.data_ptr()))
 
-    def objective_terms(self):
-        """BakedFieldOptimizer.objective_terms: the four means of the last accumulate() (five after an rgba launch), None under the
-        plain objective"""
-        return None if self._terms is None else dict(self._terms)
-
-    @property
-    def last_background(self):
-        """the background tensor [n,3] of the last accumulate() (None: the launch used the flag's colour)"""
-        return self._rgba.last_background
-
-    def apply(self):
-        """knerf_baked_bricks_train_apply: one Adam step from the accumulated gradient, the slots' records rewritten, their gradient
-        zeroed"""
-        from . import _lib
+    def _apply_launch(self):
         from .runtime import _ptr
-        t = self.iterations + 1
-        _check(_lib.load().knerf_baked_bricks_train_apply(
-            _stream(self.field.device), C.byref(self._c), _ptr(self._flags), _ptr(self._master), _ptr(self._m), _ptr(self._v),
-            bias_corrected_rate(self.learning_rate_sigma, self.beta_1, self.beta_2, t),
-            bias_corrected_rate(self.learning_rate_sh, self.beta_1, self.beta_2, t), self.beta_1, self.beta_2, self.epsilon),
-            "knerf_baked_bricks_train_apply")
-        self.iterations = t
-
-    def train_step(self, origins, directions, near, far, target):
-        """accumulate, apply; returns the batch's loss before the step (float64 device scalar)"""
-        loss = self.accumulate(origins, directions, near, far, target)
-        self.apply()
-        return loss
-
-    def fit(self, batches, near, far, steps=None):
-        """train_step on every batch of `batches` (each (target [n,3], (origins, directions, t)) as RayBatchDataset yields them), at
-        most `steps` of them.  {"loss": [...]}: read from the device once, after the last step; under an objective that is not the
-        plain one also the four lists of objective_terms()."""
-        import torch
-        if steps is not None and (isinstance(steps, bool) or int(steps) != steps or int(steps) < 0):
-            raise ValueError(f"steps must be a non-negative integer or None, got {steps!r}")
-        losses, terms = [], []
-        for k, (target, (o, d, _t)) in enumerate(batches):
-            if steps is not None and k >= int(steps):
-                break
-            losses.append(self.train_step(o, d, near, far, target))
-            if self._terms is not None:
-                terms.append(self.objective_terms())
-        out = {"loss": torch.stack(losses).cpu().tolist() if losses else []}
-        return out if self.objective is None and not terms else fit_terms(out, terms)
+        return "knerf_baked_bricks_train_apply", (_ptr(self._flags),)
 
     # ---- views for tests and tools
     def _dense(self, per_record, dtype):

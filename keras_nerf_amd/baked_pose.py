@@ -18,7 +18,7 @@ import ctypes as C
 import numpy as np
 
 from .baked import BakedField, BrickBakedField, _check, _ray_args, _stream, check_render_args
-from .baked_train import bias_corrected_rate, check_target_shape
+from .baked_train import bias_corrected_rate, check_steps, check_target_shape, finite_numbers, march_flags, ray_norm
 
 
 def check_ray_model(model) -> None:
@@ -47,19 +47,15 @@ def ray_gradients(field, origins, directions, near, far, target, step=None, whit
     o, d, n, h, (near_t, near0), (far_t, far0) = _ray_args(field, origins, directions, near, far, step)
     tg = _f32(target, dev)
     check_target_shape(tuple(tg.shape), n)
-    norm = n if n_total is None else int(n_total)
-    if norm < 1 and n:
-        raise ValueError(f"n_total must be a positive ray count, got {n_total!r}")
+    norm = ray_norm(n, n_total)
     go = torch.empty((n, 3), device=dev, dtype=torch.float32)
     gd = torch.empty((n, 3), device=dev, dtype=torch.float32)
     sq = torch.empty((n,), device=dev, dtype=torch.float32)
-    flags = (_lib.BAKED_WHITE_BACKGROUND if white_background else 0) | _lib.BAKED_SKIP_EMPTY | (int(lanes_per_ray) << _lib.BAKED_LANES_SHIFT)
     if n:
-        bricks = isinstance(field, BrickBakedField)
-        fn = _lib.load().knerf_baked_ray_gradients_bricks if bricks else _lib.load().knerf_baked_ray_gradients
-        _check(fn(_stream(dev), C.byref(field._c), _ptr(o), _ptr(d), _ptr(near_t), _ptr(far_t), near0, far0, _ptr(tg), n, norm, h,
-                  float(termination), flags, _ptr(go), _ptr(gd), _ptr(sq)),
-               "knerf_baked_ray_gradients_bricks" if bricks else "knerf_baked_ray_gradients")
+        name = "knerf_baked_ray_gradients_bricks" if isinstance(field, BrickBakedField) else "knerf_baked_ray_gradients"
+        _check(getattr(_lib.load(), name)(_stream(dev), C.byref(field._c), _ptr(o), _ptr(d), _ptr(near_t), _ptr(far_t), near0, far0, _ptr(tg),
+                                          n, norm, h, float(termination), march_flags(white_background, lanes_per_ray), _ptr(go), _ptr(gd),
+                                          _ptr(sq)), name)
     return go, gd, sq.to(torch.float64).sum() / (3.0 * max(norm, 1))
 
 
@@ -109,13 +105,9 @@ def check_pose_args(c2w_shape, learning_rate_rotation, learning_rate_translation
     lie in [0, 1) and epsilon is finite and > 0; returns the five numbers as floats"""
     if len(c2w_shape) != 3 or tuple(c2w_shape[1:]) != (4, 4) or c2w_shape[0] < 1:
         raise ValueError(f"c2w must be [V,4,4] camera-to-world matrices, got {tuple(c2w_shape)}")
-    out = []
-    for name, v in (("learning_rate_rotation", learning_rate_rotation), ("learning_rate_translation", learning_rate_translation),
-                    ("beta_1", beta_1), ("beta_2", beta_2), ("epsilon", epsilon)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not np.isfinite(float(v)):
-            raise ValueError(f"{name} must be a finite number, got {v!r}")
-        out.append(float(v))
-    lr_r, lr_t, b1, b2, eps = out
+    lr_r, lr_t, b1, b2, eps = finite_numbers((("learning_rate_rotation", learning_rate_rotation),
+                                              ("learning_rate_translation", learning_rate_translation), ("beta_1", beta_1),
+                                              ("beta_2", beta_2), ("epsilon", epsilon)))
     if lr_r < 0.0 or lr_t < 0.0 or not (lr_r > 0.0 or lr_t > 0.0):
         raise ValueError(f"learning rates must be >= 0 and one of them > 0, got {learning_rate_rotation!r} and {learning_rate_translation!r}")
     if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
@@ -195,8 +187,8 @@ class PoseOptimizer:
         knerf_ray_model if it has one -- NDC rays are refused with ValueError before any launch.  step, white_background, termination,
         n_total, lanes_per_ray: as field.ray_gradients (beside a field optimiser: that optimiser's own)."""
         check_ray_model(ray_model)
-        go, gd, loss = ray_gradients(field, origins, directions, near, far, target, step, white_background, termination, n_total,
-                                     lanes_per_ray)
+        go, gd, loss = ray_gradients(field, origins, directions, near, far, target, step=step, white_background=white_background,
+                                     termination=termination, n_total=n_total, lanes_per_ray=lanes_per_ray)
         from .runtime import _f32
         self._grad += pose_gradients(go, gd, _f32(directions, field.device).reshape(-1, 3), view, self.n_views)
         return loss
@@ -269,11 +261,8 @@ def fit_with_poses(opt, pose_opt, batches, near, far, steps=None, field_steps_fi
     whose ray_model() says so) raise ValueError before the first launch.  The dataset keeps the provider afterwards: its next batches
     are drawn with the refined poses (set_cameras(None) gives the stored ones back)."""
     import torch
-    for name, v in (("steps", steps), ("field_steps_first", field_steps_first)):
-        if v is not None and (isinstance(v, bool) or int(v) != v or int(v) < 0):
-            raise ValueError(f"{name} must be a non-negative integer{' or None' if name == 'steps' else ''}, got {v!r}")
-    if field_steps_first is None:
-        raise ValueError("field_steps_first must be a non-negative integer, got None")
+    check_steps(steps)
+    check_steps(field_steps_first, "field_steps_first", optional=False)
     if not isinstance(pose_opt, PoseOptimizer):
         raise ValueError(f"pose_opt must be a PoseOptimizer, got {type(pose_opt).__name__}")
     if (opt is None) == (field is None):

@@ -27,22 +27,34 @@ import numpy as np
 from .baked import BakedField, _check, _ray_args, _stream, _unpack_words, check_render_args, check_threshold, n_coefficients
 
 
+def is_number(v, finite_as=float, integer=False) -> bool:
+    """whether v is a number and no bool: an int, a float or their NumPy kinds that is finite as a `finite_as` (float, or np.float32
+    where the value ends up in one); with integer=True an int or a NumPy integer"""
+    if integer:
+        return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+    return not isinstance(v, bool) and isinstance(v, (int, float, np.floating, np.integer)) and bool(np.isfinite(finite_as(v)))
+
+
+def finite_numbers(named, finite_as=float):
+    """the values of `named` ((name, value) pairs) as floats; ValueError for the first that is not is_number(value, finite_as)"""
+    for name, v in named:
+        if not is_number(v, finite_as):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+    return tuple(float(v) for _, v in named)
+
+
 def check_optimizer_args(learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation):
     """ValueError unless both learning rates and epsilon are finite and > 0, both betas lie in [0, 1) and dilation is an integer 0..8
     (what knerf_occupancy_from_grid takes); returns them as (float, float, float, float, float, int)"""
-    def number(name, v):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not np.isfinite(float(v)):
-            raise ValueError(f"{name} must be a finite number, got {v!r}")
-        return float(v)
-    lrs, lrc = number("learning_rate_sigma", learning_rate_sigma), number("learning_rate_sh", learning_rate_sh)
-    b1, b2, eps = number("beta_1", beta_1), number("beta_2", beta_2), number("epsilon", epsilon)
+    lrs, lrc, b1, b2, eps = finite_numbers((("learning_rate_sigma", learning_rate_sigma), ("learning_rate_sh", learning_rate_sh),
+                                            ("beta_1", beta_1), ("beta_2", beta_2), ("epsilon", epsilon)))
     if not (lrs > 0.0 and lrc > 0.0):
         raise ValueError(f"learning rates must be > 0, got {learning_rate_sigma!r} and {learning_rate_sh!r}")
     if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
         raise ValueError(f"beta_1 and beta_2 must lie in [0, 1), got {beta_1!r} and {beta_2!r}")
     if not np.float32(eps) > 0.0:
         raise ValueError(f"epsilon must be > 0 (as a float32), got {epsilon!r}")
-    if isinstance(dilation, bool) or not isinstance(dilation, (int, np.integer)) or not 0 <= int(dilation) <= 8:
+    if not is_number(dilation, integer=True) or not 0 <= int(dilation) <= 8:
         raise ValueError(f"dilation must be an integer 0..8, got {dilation!r}")
     return lrs, lrc, b1, b2, eps, int(dilation)
 
@@ -50,16 +62,48 @@ def check_optimizer_args(learning_rate_sigma, learning_rate_sh, beta_1, beta_2, 
 def check_tv_args(tv_sigma, tv_sh, tv_epsilon):
     """ValueError unless both total-variation weights are finite and >= 0 and tv_epsilon is finite and > 0 (as a float32); returns
     them as floats"""
-    out = []
-    for name, v in (("tv_sigma", tv_sigma), ("tv_sh", tv_sh), ("tv_epsilon", tv_epsilon)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.floating, np.integer)) or not np.isfinite(np.float32(v)):
-            raise ValueError(f"{name} must be a finite number, got {v!r}")
-        out.append(float(v))
+    out = finite_numbers((("tv_sigma", tv_sigma), ("tv_sh", tv_sh), ("tv_epsilon", tv_epsilon)), np.float32)
     if out[0] < 0.0 or out[1] < 0.0:
         raise ValueError(f"tv_sigma and tv_sh must be >= 0, got {tv_sigma!r} and {tv_sh!r}")
     if not np.float32(out[2]) > 0.0:
         raise ValueError(f"tv_epsilon must be > 0 (as a float32), got {tv_epsilon!r}")
-    return tuple(out)
+    return out
+
+
+def check_steps(steps, name="steps", optional=True) -> None:
+    """ValueError unless `steps` is a non-negative integer, or None where that is allowed (fit: every batch)"""
+    if (steps is None and not optional) or (steps is not None and (isinstance(steps, bool) or int(steps) != steps or int(steps) < 0)):
+        raise ValueError(f"{name} must be a non-negative integer{' or None' if optional else ''}, got {steps!r}")
+
+
+def ray_norm(n, n_total) -> int:
+    """the N of a launch's loss: n_total, or the batch's n rays; ValueError for an n_total below 1 beside rays"""
+    norm = n if n_total is None else int(n_total)
+    if norm < 1 and n:
+        raise ValueError(f"n_total must be a positive ray count, got {n_total!r}")
+    return norm
+
+
+def march_flags(white_background, lanes_per_ray) -> int:
+    """the flag word of a training march (include/knerf.h): the background, empty cells skipped, the kernel variant"""
+    from . import _lib
+    return (_lib.BAKED_WHITE_BACKGROUND if white_background else 0) | _lib.BAKED_SKIP_EMPTY | (int(lanes_per_ray) << _lib.BAKED_LANES_SHIFT)
+
+
+def slot_masks(occ, res):
+    """(touched, free), bool [Rx,Ry,Rz] on occ's device, from the support cells occ [Rx-1,Ry-1,Rz-1]: the lattice points that are a
+    corner of a support cell (the slots), and those none of whose 8 adjacent cells is a lattice cell outside the support (where sigma
+    is trainable)"""
+    import torch
+    cx, cy, cz = occ.shape
+    touched = torch.zeros(res, device=occ.device, dtype=torch.bool)
+    free = torch.ones(res, device=occ.device, dtype=torch.bool)
+    for a in (0, 1):
+        for b in (0, 1):
+            for c in (0, 1):
+                touched[a:a + cx, b:b + cy, c:c + cz] |= occ
+                free[a:a + cx, b:b + cy, c:c + cz] &= occ
+    return touched, free
 
 
 def check_target_shape(shape, n_rays) -> None:
@@ -84,15 +128,22 @@ def check_objective(loss, regularizers):
 TERM_NAMES = ("photometric", "mse", "distortion", "opacity_entropy")
 
 
+def term_means(total, norm):
+    """{name: mean} from the summed columns `total` [4] or [5] of a launch's per-ray terms: photometric and mse are means over rays and
+    channels, distortion, opacity_entropy and (the fifth column) opacity over rays (N = norm)"""
+    n = float(max(norm, 1))
+    means = {"photometric": total[0] / (3.0 * n), "mse": total[1] / (3.0 * n)}
+    for i, name in enumerate((TERM_NAMES + ("opacity",))[2:total.shape[0]], 2):
+        means[name] = total[i] / n
+    return means
+
+
 def objective_value(obj, terms, norm):
     """(loss, {name: mean}) from the per-ray terms [n, 4] of an extended launch, float64 device scalars: the terms are summed in float64
-    on the device; photometric and mse are means over rays and channels, distortion and opacity_entropy over rays (N = norm); loss =
-    photometric + distortion weight x mean D + opacity_entropy weight x mean H, the function whose gradient the launch added."""
+    on the device (term_means; N = norm); loss = photometric + distortion weight x mean D + opacity_entropy weight x mean H, the
+    function whose gradient the launch added."""
     import torch
-    total = terms.to(torch.float64).sum(dim=0)
-    n = float(max(norm, 1))
-    means = {"photometric": total[0] / (3.0 * n), "mse": total[1] / (3.0 * n), "distortion": total[2] / n,
-             "opacity_entropy": total[3] / n}
+    means = term_means(terms.to(torch.float64).sum(dim=0), norm)
     loss = means["photometric"] + float(obj.distortion) * means["distortion"] + float(obj.opacity_entropy) * means["opacity_entropy"]
     return loss, means
 
@@ -138,14 +189,13 @@ class RgbaTargets:
                 raise ValueError(f"white_background=True contradicts background={background!r}")
             self.mode = "colour"
         self.white = white
-        if isinstance(opacity_loss, bool) or not isinstance(opacity_loss, (int, float, np.floating, np.integer)) or \
-                not np.isfinite(np.float32(opacity_loss)) or float(opacity_loss) < 0.0:
+        if not is_number(opacity_loss, np.float32) or float(opacity_loss) < 0.0:
             raise ValueError(f"opacity_loss must be a finite number >= 0, got {opacity_loss!r}")
         self.opacity = float(opacity_loss)
         if target_background not in (None, "black", "white"):
             raise ValueError(f'target_background must be None, "black" or "white", got {target_background!r}')
         self.stored = float(white) if target_background is None else float(target_background == "white")
-        if isinstance(background_seed, bool) or not isinstance(background_seed, (int, np.integer)):
+        if not is_number(background_seed, integer=True):
             raise ValueError(f"background_seed must be an integer, got {background_seed!r}")
         self.seed = int(background_seed)
         self._generator = None
@@ -196,10 +246,7 @@ def rgba_value(obj, rec, terms, norm):
     """objective_value for the per-ray terms [n, 5] of an rgba launch: the fifth mean is "opacity", the unweighted mean of
     (O - alpha)^2, and the loss adds the record's weight times it.  obj None: the plain objective (mean squared error)."""
     import torch
-    total = terms.to(torch.float64).sum(dim=0)
-    n = float(max(norm, 1))
-    means = {"photometric": total[0] / (3.0 * n), "mse": total[1] / (3.0 * n), "distortion": total[2] / n,
-             "opacity_entropy": total[3] / n, "opacity": total[4] / n}
+    means = term_means(terms.to(torch.float64).sum(dim=0), norm)
     loss = means["photometric"] + float(rec.opacity) * means["opacity"]
     if obj is not None:
         loss = loss + float(obj.distortion) * means["distortion"] + float(obj.opacity_entropy) * means["opacity_entropy"]
@@ -211,75 +258,59 @@ def bias_corrected_rate(learning_rate: float, beta_1: float, beta_2: float, t: i
     return float(learning_rate) * float(np.sqrt(1.0 - float(beta_2) ** t)) / (1.0 - float(beta_1) ** t)
 
 
-class BakedFieldOptimizer:
-    """Adam on the records of a baked field (BakedField.optimizer builds one).  `field` is the live field: it owns the records the
-    optimiser rewrites, its bits are the support, and it can be rendered at any time."""
+class GridOptimizer:
+    """What the optimisers of a baked field share, whatever its storage (BakedFieldOptimizer here, BrickFieldOptimizer in
+    baked_bricks_train.py): the keywords' checks, the gradient launch, Adam's launch, train_step() and fit().  A subclass names its
+    entry points and builds its state:
+      _train_rays            the stem of its gradient launch; accumulate() appends "", "_ext" or "_rgba"
+      _check_source(source)  its refusal of a source of the wrong kind
+      _check_lanes(sh_degree, lanes_per_ray)   the lane counts its gradient kernel is built for
+      _build(source)         the live `field`, `_master` [rows][1 + 3 K] fp32, `n_slots` and its own index tensors
+      _state()               its struct for the launches, over `field` and `_grad`
+      _apply_launch()        (the name of its Adam launch, the arguments between the struct and the master rows)"""
 
     _rgba = RgbaTargets()               # the rgba keywords at their defaults: every launch is what it was without them
+    _train_rays = None
 
     def __init__(self, source, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
-                 white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6, loss=None,
-                 regularizers=None, background=None, opacity_loss=0.0, target_background=None, background_seed=0):
+                 white_background=False, termination=0.0, lanes_per_ray=0, loss=None, regularizers=None, background=None,
+                 opacity_loss=0.0, target_background=None, background_seed=0):
+        """every keyword is checked (ValueError) before `source` is touched and before the library is loaded"""
         import torch
-        from . import _lib
-        from .runtime import occupancy_words_from_grid
         self._rgba = RgbaTargets(white_background, background, opacity_loss, target_background, background_seed)
         self.learning_rate_sigma, self.learning_rate_sh, self.beta_1, self.beta_2, self.epsilon, self.dilation = \
             check_optimizer_args(learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation)
-        self.tv_sigma, self.tv_sh, self.tv_epsilon = check_tv_args(tv_sigma, tv_sh, tv_epsilon)
         self.objective = check_objective(loss, regularizers)               # None: the plain objective, the plain entry point
         self._terms = None                                                  # the last accumulate's means (objective_terms)
-        self.last_regularizer = None                                        # what the latest train_step's regularize() returned
-        check_render_args(step, termination, ("image",), source.sh_degree, lanes_per_ray)
-        self.step, self.white_background, self.termination, self.lanes_per_ray = step, self._rgba.white, float(termination), \
-            int(lanes_per_ray)
-        dev, res, deg = source.device, source.resolution, source.sh_degree
-        K = n_coefficients(deg)
-        self._width = 1 + 3 * K
-        sigma = source.sigma
-        support = occupancy_words_from_grid(sigma, 0.0, self.dilation, what="BakedField.optimizer")
-        self.field = BakedField(source._records.clone(), support, res, source.bounds, deg, source.sigma_threshold)
-        cells = tuple(r - 1 for r in res)
-        occ = _unpack_words(support, cells)
-        cx, cy, cz = cells
-        touched = torch.zeros(res, device=dev, dtype=torch.bool)
-        # a point's sigma is trainable when none of its 8 adjacent cells is a lattice cell outside the support
-        free = torch.ones(res, device=dev, dtype=torch.bool)
-        for a in (0, 1):
-            for b in (0, 1):
-                for c in (0, 1):
-                    touched[a:a + cx, b:b + cy, c:c + cz] |= occ
-                    free[a:a + cx, b:b + cy, c:c + cz] &= occ
-        index = touched.reshape(-1).nonzero().reshape(-1)                   # int64, ascending: the lattice point of every slot
-        self.n_slots = int(index.numel())                                   # the one host read of the construction
-        if self.n_slots == 0:
-            raise ValueError("the field has no occupied cell: there is nothing to optimise")
-        self._index = index
-        self._point_of = index.to(torch.int32)
-        self._slot_of = torch.full((touched.numel(),), -1, device=dev, dtype=torch.int32)
-        self._slot_of[index] = torch.arange(self.n_slots, device=dev, dtype=torch.int32)
-        self._trainable = free.reshape(-1)[index].to(torch.uint8).contiguous()
-        co = source.coefficients.reshape(-1, 3 * K)[index].to(torch.float32)
-        sg = sigma.reshape(-1)[index] * self._trainable.to(torch.float32)   # elsewhere sigma is 0 by the construction of the bits
-        self._master = torch.cat([sg[:, None], co], dim=1).contiguous()
+        self._check_source(source)
+        check_render_args(step, termination, ("image",))
+        self.lanes_per_ray = self._check_lanes(source.sh_degree, lanes_per_ray)
+        self.step, self.white_background, self.termination = step, self._rgba.white, float(termination)
+        self._width = 1 + 3 * n_coefficients(source.sh_degree)
+        self._build(source)
         self._grad = torch.zeros_like(self._master)
         self._m, self._v = torch.zeros_like(self._master), torch.zeros_like(self._master)
         self.iterations = 0                                                 # steps applied; the host's count, no device read
-        self._c = _lib.KnerfBakedTrain(self.field._c, C.c_void_p(self._slot_of.data_ptr()), C.c_void_p(self._grad.data_ptr()),
-                                       self.n_slots)
+        self._c = self._state()
+
+    def _check_source(self, source) -> None:
+        pass
 
     # ---- the two launches
     def accumulate(self, origins, directions, near, far, target, n_total=None, background=None):
-        """knerf_baked_train_rays: adds the gradient of the batch's mean squared error to the gradient rows and returns the loss, a
-        float64 device scalar (the per-ray errors are summed in float64 on the device; nothing waits).  n_total: the N of the loss
-        1 / (3 N) sum (out - target)^2 when the batch is one part of several accumulated before apply() (default: this batch's rays).
-        With a loss= / regularizers= objective that is not the plain one: knerf_baked_train_rays_ext, and the value returned is that
-        of the function whose gradient was added, the mean of rho plus distortion x mean D plus opacity_entropy x mean H (the per-ray
-        terms summed in float64 on the device); objective_terms() then gives the four means.
+        """knerf_baked_train_rays / knerf_baked_bricks_train_rays: adds the gradient of the batch's mean squared error to the gradient
+        rows and returns the loss, a float64 device scalar (the per-ray errors are summed in float64 on the device; nothing waits).
+        n_total: the N of the loss 1 / (3 N) sum (out - target)^2 when the batch is one part of several accumulated before apply()
+        (default: this batch's rays).
+        With a loss= / regularizers= objective that is not the plain one: knerf_baked_train_rays_ext /
+        knerf_baked_bricks_train_rays_ext, and the value returned is that of the function whose gradient was added, the mean of rho
+        plus distortion x mean D plus opacity_entropy x mean H (the per-ray terms summed in float64 on the device);
+        objective_terms() then gives the four means.
         With the rgba keywords (background=, opacity_loss=), an [n,4] target (the fourth column is the photograph's alpha) or a
-        per-call `background` ([n,3], values in [0,1], overrides the keyword): knerf_baked_train_rays_rgba, the prediction and the
-        photograph composited over the ray's own background and opacity_loss x mean (O - alpha)^2 added; objective_terms() then has
-        a fifth mean, "opacity", and last_background is the background tensor of the launch."""
+        per-call `background` ([n,3], values in [0,1], overrides the keyword): knerf_baked_train_rays_rgba /
+        knerf_baked_bricks_train_rays_rgba, the prediction and the photograph composited over the ray's own background and
+        opacity_loss x mean (O - alpha)^2 added; objective_terms() then has a fifth mean, "opacity", and last_background is the
+        background tensor of the launch."""
         import torch
         from . import _lib
         from .runtime import _f32, _ptr
@@ -287,35 +318,23 @@ class BakedFieldOptimizer:
         o, d, n, h, (near_t, near0), (far_t, far0) = _ray_args(f, origins, directions, near, far, self.step)
         tg, alpha = self._rgba.split_target(_f32(target, f.device), n)
         rgba = self._rgba.record(alpha, n, f.device, background)
-        norm = n if n_total is None else int(n_total)
-        if norm < 1 and n:
-            raise ValueError(f"n_total must be a positive ray count, got {n_total!r}")
+        norm = ray_norm(n, n_total)
         sq = torch.empty((n,), device=f.device, dtype=torch.float32)
-        flags = (_lib.BAKED_WHITE_BACKGROUND if self.white_background else 0) | _lib.BAKED_SKIP_EMPTY | \
-            (self.lanes_per_ray << _lib.BAKED_LANES_SHIFT)
-        if rgba is not None:
-            terms = torch.zeros((n, 5), device=f.device, dtype=torch.float32)
-            if n:
-                _check(_lib.load().knerf_baked_train_rays_rgba(_stream(f.device), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t),
-                                                               _ptr(far_t), near0, far0, _ptr(tg), n, norm, h, self.termination, flags,
-                                                               _ptr(sq), C.byref(self.objective) if self.objective is not None else None,
-                                                               _ptr(terms), C.byref(rgba)), "knerf_baked_train_rays_rgba")
-            loss, self._terms = rgba_value(self.objective, rgba, terms, norm)
-            return loss
-        if self.objective is not None:
-            terms = torch.zeros((n, 4), device=f.device, dtype=torch.float32)
-            if n:
-                _check(_lib.load().knerf_baked_train_rays_ext(_stream(f.device), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t),
-                                                              _ptr(far_t), near0, far0, _ptr(tg), n, norm, h, self.termination, flags,
-                                                              _ptr(sq), C.byref(self.objective), _ptr(terms)),
-                       "knerf_baked_train_rays_ext")
-            loss, self._terms = objective_value(self.objective, terms, norm)
-            return loss
+        route = "_rgba" if rgba is not None else "_ext" if self.objective is not None else ""
+        args = [_stream(f.device), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t), _ptr(far_t), near0, far0, _ptr(tg), n, norm, h,
+                self.termination, march_flags(self.white_background, self.lanes_per_ray), _ptr(sq)]
+        if route:
+            terms = torch.zeros((n, 5 if rgba is not None else 4), device=f.device, dtype=torch.float32)
+            args += [C.byref(self.objective) if self.objective is not None else None, _ptr(terms)]
+            if rgba is not None:
+                args.append(C.byref(rgba))
         if n:
-            _check(_lib.load().knerf_baked_train_rays(_stream(f.device), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t), _ptr(far_t),
-                                                      near0, far0, _ptr(tg), n, norm, h, self.termination, flags, _ptr(sq)),
-                   "knerf_baked_train_rays")
-        return sq.to(torch.float64).sum() / (3.0 * max(norm, 1))
+            _check(getattr(_lib.load(), self._train_rays + route)(*args), self._train_rays + route)
+        if not route:
+            return sq.to(torch.float64).sum() / (3.0 * max(norm, 1))
+        loss, self._terms = rgba_value(self.objective, rgba, terms, norm) if rgba is not None else \
+            objective_value(self.objective, terms, norm)
+        return loss
 
     def objective_terms(self):
         """{"photometric", "mse", "distortion", "opacity_entropy"}: the four means of the last accumulate() as float64 device scalars
@@ -330,46 +349,23 @@ class BakedFieldOptimizer:
         return self._rgba.last_background
 
     def apply(self):
-        """knerf_baked_train_apply: one Adam step from the accumulated gradient, the records rewritten, the gradient zeroed"""
+        """knerf_baked_train_apply / knerf_baked_bricks_train_apply: one Adam step from the accumulated gradient, the slots' records
+        rewritten, their gradient zeroed"""
         from . import _lib
         from .runtime import _ptr
         t = self.iterations + 1
-        _check(_lib.load().knerf_baked_train_apply(
-            _stream(self.field.device), C.byref(self._c), _ptr(self._point_of), _ptr(self._trainable), _ptr(self._master), _ptr(self._m),
-            _ptr(self._v), bias_corrected_rate(self.learning_rate_sigma, self.beta_1, self.beta_2, t),
-            bias_corrected_rate(self.learning_rate_sh, self.beta_1, self.beta_2, t), self.beta_1, self.beta_2, self.epsilon),
-            "knerf_baked_train_apply")
+        name, middle = self._apply_launch()
+        _check(getattr(_lib.load(), name)(
+            _stream(self.field.device), C.byref(self._c), *middle, _ptr(self._master), _ptr(self._m), _ptr(self._v),
+            bias_corrected_rate(self.learning_rate_sigma, self.beta_1, self.beta_2, t),
+            bias_corrected_rate(self.learning_rate_sh, self.beta_1, self.beta_2, t), self.beta_1, self.beta_2, self.epsilon), name)
         self.iterations = t
 
-    @property
-    def regularized(self) -> bool:
-        """whether a total-variation weight is > 0: train_step then runs regularize() between accumulate() and apply()"""
-        return self.tv_sigma > 0.0 or self.tv_sh > 0.0
-
-    def tv_weights(self):
-        """the weights per term knerf_baked_train_tv takes, formed in double: tv_sigma / n_slots and tv_sh / (3 K n_slots)"""
-        return self.tv_sigma / float(self.n_slots), self.tv_sh / (float(self._width - 1) * float(self.n_slots))
-
-    def regularize(self):
-        """knerf_baked_train_tv, one launch: adds the gradient of R = tv_sigma mean_p tv_sigma(p) + tv_sh mean_{p,q} tv_q(p) (the total
-        variation of the master values over the slots, include/knerf.h) to the gradient rows and returns the two means, unweighted,
-        as float64 device scalars (the per-slot terms are summed in float64 on the device; nothing waits)."""
-        import torch
-        from . import _lib
-        from .runtime import _ptr
-        dev = self.field.device
-        tv = torch.empty((self.n_slots, 2), device=dev, dtype=torch.float32)
-        ws, wc = self.tv_weights()
-        _check(_lib.load().knerf_baked_train_tv(_stream(dev), C.byref(self._c), _ptr(self._point_of), _ptr(self._master), ws, wc,
-                                                self.tv_epsilon, _ptr(tv)), "knerf_baked_train_tv")
-        total = tv.to(torch.float64).sum(dim=0)
-        return total[0] / float(self.n_slots), total[1] / (float(self._width - 1) * float(self.n_slots))
-
     def train_step(self, origins, directions, near, far, target):
-        """accumulate, regularize (only when a total-variation weight is > 0; its return value is kept in last_regularizer), apply;
-        returns the batch's loss before the step (float64 device scalar, the data term alone)"""
+        """accumulate, regularize (only where the class has the total-variation regulariser and a weight is > 0; its return value is
+        kept in last_regularizer), apply; returns the batch's loss before the step (float64 device scalar, the data term alone)"""
         loss = self.accumulate(origins, directions, near, far, target)
-        if self.regularized:
+        if getattr(self, "regularized", False):
             self.last_regularizer = self.regularize()
         self.apply()
         return loss
@@ -381,24 +377,115 @@ class BakedFieldOptimizer:
         step; with an objective that is not the plain one also "photometric", "mse", "distortion" and "opacity_entropy":
         objective_terms() per step, and "opacity" behind them where the steps were rgba launches."""
         import torch
-        if steps is not None and (isinstance(steps, bool) or int(steps) != steps or int(steps) < 0):
-            raise ValueError(f"steps must be a non-negative integer or None, got {steps!r}")
+        check_steps(steps)
+        regularized = getattr(self, "regularized", False)
         losses, tvs, terms = [], [], []
         for k, (target, (o, d, _t)) in enumerate(batches):
             if steps is not None and k >= int(steps):
                 break
             losses.append(self.train_step(o, d, near, far, target))
-            if self.regularized:
+            if regularized:
                 tvs.append(torch.stack(self.last_regularizer))
             if self._terms is not None:
                 terms.append(self.objective_terms())
         out = {"loss": torch.stack(losses).cpu().tolist() if losses else []}
-        if self.regularized:
+        if regularized:
             both = torch.stack(tvs).cpu() if tvs else torch.zeros((0, 2))
             out["tv_sigma"], out["tv_sh"] = both[:, 0].tolist(), both[:, 1].tolist()
         if self.objective is not None or terms:
             fit_terms(out, terms)
         return out
+
+
+class TotalVariation:
+    """The total-variation regulariser of a grid optimiser, for the classes that have one (BakedFieldOptimizer,
+    baked_bricks_grow.BrickGridTrainer; mixed in before the optimiser class).  The class supplies _tv_launch(): (the name of its
+    launch, the arguments between the struct and the weights, the rows of the per-row output)."""
+
+    def _set_tv(self, tv_sigma, tv_sh, tv_epsilon) -> None:
+        self.tv_sigma, self.tv_sh, self.tv_epsilon = check_tv_args(tv_sigma, tv_sh, tv_epsilon)
+        self.last_regularizer = None                                        # what the latest train_step's regularize() returned
+
+    @property
+    def regularized(self) -> bool:
+        """whether a total-variation weight is > 0: train_step then runs regularize() between accumulate() and apply()"""
+        return self.tv_sigma > 0.0 or self.tv_sh > 0.0
+
+    def tv_weights(self):
+        """the weights per term knerf_baked_train_tv / knerf_baked_bricks_train_tv takes, formed in double: tv_sigma / n_slots and
+        tv_sh / (3 K n_slots)"""
+        return self.tv_sigma / float(self.n_slots), self.tv_sh / (float(self._width - 1) * float(self.n_slots))
+
+    def regularize(self):
+        """knerf_baked_train_tv / knerf_baked_bricks_train_tv, one launch: adds the gradient of R = tv_sigma mean_p tv_sigma(p) +
+        tv_sh mean_{p,q} tv_q(p) (the total variation of the master values over the slots, include/knerf.h) to the gradient rows and
+        returns the two means, unweighted, as float64 device scalars (the per-row terms are summed in float64 on the device; a brick
+        record that is no slot holds (0, 0); nothing waits)."""
+        import torch
+        from . import _lib
+        from .runtime import _ptr
+        dev = self.field.device
+        name, middle, rows = self._tv_launch()
+        tv = torch.empty((rows, 2), device=dev, dtype=torch.float32)
+        ws, wc = self.tv_weights()
+        _check(getattr(_lib.load(), name)(_stream(dev), C.byref(self._c), *middle, ws, wc, self.tv_epsilon, _ptr(tv)), name)
+        total = tv.to(torch.float64).sum(dim=0)
+        return total[0] / float(self.n_slots), total[1] / (float(self._width - 1) * float(self.n_slots))
+
+
+class BakedFieldOptimizer(TotalVariation, GridOptimizer):
+    """Adam on the records of a baked field (BakedField.optimizer builds one).  `field` is the live field: it owns the records the
+    optimiser rewrites, its bits are the support, and it can be rendered at any time."""
+
+    _train_rays = "knerf_baked_train_rays"
+
+    def __init__(self, source, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
+                 white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6, loss=None,
+                 regularizers=None, background=None, opacity_loss=0.0, target_background=None, background_seed=0):
+        self._set_tv(tv_sigma, tv_sh, tv_epsilon)
+        super().__init__(source, learning_rate_sigma=learning_rate_sigma, learning_rate_sh=learning_rate_sh, beta_1=beta_1, beta_2=beta_2,
+                         epsilon=epsilon, dilation=dilation, step=step, white_background=white_background, termination=termination,
+                         lanes_per_ray=lanes_per_ray, loss=loss, regularizers=regularizers, background=background,
+                         opacity_loss=opacity_loss, target_background=target_background, background_seed=background_seed)
+
+    @staticmethod
+    def _check_lanes(sh_degree, lanes_per_ray) -> int:
+        check_render_args(None, 0.0, ("image",), sh_degree, lanes_per_ray)
+        return int(lanes_per_ray)
+
+    def _build(self, source) -> None:
+        import torch
+        from .runtime import occupancy_words_from_grid
+        dev, res, deg = source.device, source.resolution, source.sh_degree
+        K = n_coefficients(deg)
+        sigma = source.sigma
+        support = occupancy_words_from_grid(sigma, 0.0, self.dilation, what="BakedField.optimizer")
+        self.field = BakedField(source._records.clone(), support, res, source.bounds, deg, source.sigma_threshold)
+        touched, free = slot_masks(_unpack_words(support, tuple(r - 1 for r in res)), res)
+        index = touched.reshape(-1).nonzero().reshape(-1)                   # int64, ascending: the lattice point of every slot
+        self.n_slots = int(index.numel())                                   # the one host read of the construction
+        if self.n_slots == 0:
+            raise ValueError("the field has no occupied cell: there is nothing to optimise")
+        self._index = index
+        self._point_of = index.to(torch.int32)
+        self._slot_of = torch.full((touched.numel(),), -1, device=dev, dtype=torch.int32)
+        self._slot_of[index] = torch.arange(self.n_slots, device=dev, dtype=torch.int32)
+        self._trainable = free.reshape(-1)[index].to(torch.uint8).contiguous()
+        co = source.coefficients.reshape(-1, 3 * K)[index].to(torch.float32)
+        sg = sigma.reshape(-1)[index] * self._trainable.to(torch.float32)   # elsewhere sigma is 0 by the construction of the bits
+        self._master = torch.cat([sg[:, None], co], dim=1).contiguous()
+
+    def _state(self):
+        from . import _lib
+        return _lib.KnerfBakedTrain(self.field._c, C.c_void_p(self._slot_of.data_ptr()), C.c_void_p(self._grad.data_ptr()), self.n_slots)
+
+    def _apply_launch(self):
+        from .runtime import _ptr
+        return "knerf_baked_train_apply", (_ptr(self._point_of), _ptr(self._trainable))
+
+    def _tv_launch(self):
+        from .runtime import _ptr
+        return "knerf_baked_train_tv", (_ptr(self._point_of), _ptr(self._master)), self.n_slots
 
     # ---- views for tests and tools
     def gradients(self):
@@ -453,9 +540,11 @@ def brick_optimizer(field, learning_rate_sigma, learning_rate_sh, beta_1=0.9, be
     from .baked_quant import QuantizedBrickField
     if isinstance(field, QuantizedBrickField):
         raise ValueError("a brick optimiser is built on a BrickBakedField, got a QuantizedBrickField: dequantize() gives one")
-    return BrickFieldOptimizer(field, learning_rate_sigma, learning_rate_sh, beta_1, beta_2, epsilon, dilation, step, white_background,
-                               termination, lanes_per_ray, loss, regularizers, background, opacity_loss, target_background,
-                               background_seed)
+    return BrickFieldOptimizer(field, learning_rate_sigma=learning_rate_sigma, learning_rate_sh=learning_rate_sh, beta_1=beta_1,
+                               beta_2=beta_2, epsilon=epsilon, dilation=dilation, step=step, white_background=white_background,
+                               termination=termination, lanes_per_ray=lanes_per_ray, loss=loss, regularizers=regularizers,
+                               background=background, opacity_loss=opacity_loss, target_background=target_background,
+                               background_seed=background_seed)
 
 
 def __getattr__(name):
@@ -479,7 +568,7 @@ def check_stages(stages):
     if not out:
         raise ValueError("stages must name at least one stage")
     for r, s in out:
-        if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or int(s) < 0:
+        if not is_number(s, integer=True) or int(s) < 0:
             raise ValueError(f"the steps of a stage must be a non-negative integer, got {s!r}")
     return [(r, int(s)) for r, s in out]
 
