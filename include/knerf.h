@@ -657,6 +657,37 @@ int knerf_baked_train_rays_rgba(void* stream, const knerf_baked_train* train, co
                                 const float* near, const float* far, float near_all, float far_all, const float* target, uint64_t n_rays,
                                 uint64_t n_norm, float step, float termination, int flags, float* sq_err,
                                 const knerf_objective* objective, float* terms, const knerf_baked_rgba* rgba);
+/* knerf_baked_train_rays_depth -- extension, no reference counterpart.  knerf_baked_train_rays_rgba with depth supervision: a measured
+ * depth per ray (a structure-from-motion point seen through the pixel, an RGB-D capture, another model's depth map) and a squared loss
+ * between it and the ray's expected depth, the one term of the objective that says WHERE along the ray the weight sits. */
+typedef struct knerf_baked_depth {
+    const float* target;   /* DEVICE [n_rays], ray-parameter units: what knerf_baked_render writes as depth */
+    const float* weight;   /* DEVICE [n_rays] >= 0, or NULL: every ray 1 */
+    float depth;           /* lambda_z >= 0 */
+} knerf_baked_depth;
+/* Everything of knerf_baked_train_rays_rgba, and all fp32 without contraction, in the order written.  Per ray:
+ *   t_j = near + (i_j + 0.5) step, the ray parameter of the fetched sample i_j, as the march forms it
+ *   Z = sum_j w_j t_j, accumulated in march order as Z = Z + w t over the fetched samples up to and including the one behind which a
+ *       termination cut falls: the bits of knerf_baked_render's depth for the same ray, step, termination, lane variant and
+ *       KNERF_BAKED_SKIP_EMPTY over the support bits
+ *   z* = target[ray],   c = weight[ray], or 1
+ *   L gains (depth / N) sum_rays c (Z - z*)^2
+ *   zeta = (depth / N) 2 c (Z - z*);   r_j gains zeta t_j (the depth share of A_j),   total gains zeta Z
+ * A ray with c == 0 has a depth term and a zeta of exactly 0 whatever z* holds, NaN included (a select, not a product: sparse depth
+ * maps are mostly empty).  t, step and the cut carry no gradient.  The term passes neither clamp: a ray whose g is 0 on every channel
+ * still adds its gradient once it fetched a sample and c > 0; a ray without a fetched sample has Z = 0, stores c z*^2 and adds none.
+ * terms, fp32 [n_rays][6] or NULL: the five of _rgba, then c (Z - z*)^2.
+ * depth == NULL, or depth->depth == 0: the call IS knerf_baked_train_rays_rgba (the same launch, the same bits, terms with that route's
+ * stride, and that route's own fall-through to _ext and the plain call).  Otherwise the depth kernel runs, also under a plain objective
+ * and without an rgba record: its rgba fields then read as that contract's defaults (the flag's background, every alpha 1, opacity 0).
+ * KNERF_ERR_INVALID, before any launch: everything knerf_baked_train_rays_rgba refuses; depth->depth negative or not finite;
+ * depth->depth > 0 with target == NULL.  Every lane variant of _rgba exists for the depth kernel too.  The device values of target and
+ * weight are not read back. */
+int knerf_baked_train_rays_depth(void* stream, const knerf_baked_train* train, const float* origins, const float* directions,
+                                 const float* near, const float* far, float near_all, float far_all, const float* target, uint64_t n_rays,
+                                 uint64_t n_norm, float step, float termination, int flags, float* sq_err,
+                                 const knerf_objective* objective, float* terms, const knerf_baked_rgba* rgba,
+                                 const knerf_baked_depth* depth);
 /* knerf_baked_train_apply -- extension, no reference counterpart.  One Adam step over all slots and the records rewritten.
  * point_of: int32 [n_slots], the lattice point of a slot (the inverse of slot_of); sigma_trainable: uint8 [n_slots]; master, m, v:
  * fp32 [n_slots][1 + 3 K] like grad.  Per column, Keras form: m += (g - m)(1 - beta_1), v += (g g - v)(1 - beta_2),
@@ -781,6 +812,15 @@ int knerf_baked_bricks_train_rays_rgba(void* stream, const knerf_baked_bricks_tr
                                        const float* near, const float* far, float near_all, float far_all, const float* target,
                                        uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags, float* sq_err,
                                        const knerf_objective* objective, float* terms, const knerf_baked_rgba* rgba);
+/* knerf_baked_bricks_train_rays_depth -- extension, no reference counterpart.  knerf_baked_train_rays_depth through the brick table: the
+ * same record, arithmetic, terms [n_rays][6] and refusals (depth NULL or weight 0: the call IS knerf_baked_bricks_train_rays_rgba); Z has
+ * the bits of knerf_baked_render_bricks' depth, and for a brick set that holds every corner of every support cell the addends are those
+ * of the dense call, bit for bit. */
+int knerf_baked_bricks_train_rays_depth(void* stream, const knerf_baked_bricks_train* train, const float* origins, const float* directions,
+                                        const float* near, const float* far, float near_all, float far_all, const float* target,
+                                        uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags, float* sq_err,
+                                        const knerf_objective* objective, float* terms, const knerf_baked_rgba* rgba,
+                                        const knerf_baked_depth* depth);
 /* knerf_baked_bricks_train_apply -- extension, no reference counterpart.  knerf_baked_train_apply over the stored records: the same Adam
  * step, projection, record rewrite (fp32 sigma, coefficients to fp16 to nearest even, zero padding) and zeroing of the gradient row.
  * flags: uint8 [n_bricks b^3]; bit 0: the record is a slot (a corner of a support cell), bit 1: its sigma is trainable.  A record without

@@ -87,6 +87,12 @@ class KnerfBakedRgba(C.Structure):
     _fields_ = [("background", C.c_void_p), ("alpha", C.c_void_p), ("stored_background", C.c_float), ("opacity", C.c_float)]
 
 
+class KnerfBakedDepth(C.Structure):
+    """struct knerf_baked_depth (include/knerf.h): device depth targets [n] in ray-parameter units, weights [n] (may be NULL: every ray
+    1), the depth loss's weight"""
+    _fields_ = [("target", C.c_void_p), ("weight", C.c_void_p), ("depth", C.c_float)]
+
+
 BAKED_WHITE_BACKGROUND, BAKED_SKIP_EMPTY, BAKED_LANES_SHIFT = 1, 2, 8
 SPACING_LINEAR, SPACING_DISPARITY = 0, 1
 SPACINGS = {"linear": SPACING_LINEAR, "disparity": SPACING_DISPARITY}
@@ -186,6 +192,9 @@ SIGNATURES = {
     "knerf_baked_train_rays_rgba": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _F, _F, _F, _F, C.c_float, C.c_float, _F, C.c_uint64,
                                               C.c_uint64, C.c_float, C.c_float, C.c_int, _F, C.POINTER(KnerfObjective), _F,
                                               C.POINTER(KnerfBakedRgba)]),
+    "knerf_baked_train_rays_depth": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _F, _F, _F, _F, C.c_float, C.c_float, _F, C.c_uint64,
+                                               C.c_uint64, C.c_float, C.c_float, C.c_int, _F, C.POINTER(KnerfObjective), _F,
+                                               C.POINTER(KnerfBakedRgba), C.POINTER(KnerfBakedDepth)]),
     "knerf_baked_train_apply": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _P, _P, _F, _F, _F, C.c_float, C.c_float, C.c_float, C.c_float,
                                           C.c_float]),
     "knerf_baked_train_tv": (C.c_int, [_P, C.POINTER(KnerfBakedTrain), _P, _F, C.c_float, C.c_float, C.c_float, _F]),
@@ -200,6 +209,10 @@ SIGNATURES = {
     "knerf_baked_bricks_train_rays_rgba": (C.c_int, [_P, C.POINTER(KnerfBakedBricksTrain), _F, _F, _F, _F, C.c_float, C.c_float, _F,
                                                      C.c_uint64, C.c_uint64, C.c_float, C.c_float, C.c_int, _F,
                                                      C.POINTER(KnerfObjective), _F, C.POINTER(KnerfBakedRgba)]),
+    "knerf_baked_bricks_train_rays_depth": (C.c_int, [_P, C.POINTER(KnerfBakedBricksTrain), _F, _F, _F, _F, C.c_float, C.c_float, _F,
+                                                      C.c_uint64, C.c_uint64, C.c_float, C.c_float, C.c_int, _F,
+                                                      C.POINTER(KnerfObjective), _F, C.POINTER(KnerfBakedRgba),
+                                                      C.POINTER(KnerfBakedDepth)]),
     "knerf_baked_bricks_train_apply": (C.c_int, [_P, C.POINTER(KnerfBakedBricksTrain), _P, _F, _F, _F, C.c_float, C.c_float, C.c_float,
                                                  C.c_float, C.c_float]),
     "knerf_baked_resample_bricks_sigma": (C.c_int, [_P, C.POINTER(KnerfBakedBricks), C.POINTER(C.c_int32), C.c_float, _F]),

@@ -339,6 +339,38 @@ def _ray_args(field, origins, directions, near, far, step):
     return o, d, n, h, ends[0], ends[1]
 
 
+def check_depth_loss(depth_loss) -> float:
+    """ValueError unless depth_loss (lambda_z, the weight of mean c (Z - z*)^2) is a finite number >= 0 as a float32; returns it"""
+    ok = not isinstance(depth_loss, bool) and isinstance(depth_loss, (int, float, np.floating, np.integer))
+    with np.errstate(over="ignore"):                                       # (a value beyond float32 becomes inf and is refused)
+        ok = ok and bool(np.isfinite(np.float32(depth_loss)))
+    if not ok or float(depth_loss) < 0.0:
+        raise ValueError(f"depth_loss must be a finite number >= 0, got {depth_loss!r}")
+    return float(depth_loss)
+
+
+def takes_depth_loss(make):
+    """Gives a grid optimiser's constructor or factory the keyword depth_loss=0.0 (lambda_z, the weight of the depth term; DESIGN.md
+    2.33) beside its declared ones: keyword-only, checked (ValueError) before anything else runs, and kept on the optimiser as
+    `depth_loss`, which accumulate() reads.  An __init__ gets it set on `self` before it runs (a subclass's __init__ calls its parent's
+    without the keyword, which leaves the value alone); a factory gets it set on the optimiser it returns.  The declared positional
+    parameters stay what they were, so every caller that passes keywords by position keeps working."""
+    import functools
+
+    @functools.wraps(make)
+    def wrapped(*args, depth_loss=None, **kwargs):
+        value = None if depth_loss is None else check_depth_loss(depth_loss)
+        if make.__name__ == "__init__":
+            if value is not None:
+                args[0].depth_loss = value
+            return make(*args, **kwargs)
+        opt = make(*args, **kwargs)
+        if value is not None:
+            opt.depth_loss = value
+        return opt
+    return wrapped
+
+
 class BakedField:
     """A lattice of (sigma fp32, 3 K fp16 SH coefficients) records over a box plus the occupancy bits of its cells; render() marches
     rays through it on the GPU.  Built by NeRF.bake, BakedField.from_arrays or BakedField.load."""
@@ -544,6 +576,7 @@ class BakedField:
         return out
 
     # ---- optimisation against ray batches
+    @takes_depth_loss
     def optimizer(self, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
                   white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6, loss=None,
                   regularizers=None, background=None, opacity_loss=0.0, target_background=None, background_seed=0):
@@ -560,7 +593,10 @@ class BakedField:
         what the targets' rgb is composited over; default: the white flag), background_seed: training on RGBA targets [n,4]
         (knerf_baked_train_rays_rgba).  "white" equals white_background=True; "random" draws torch.rand((n, 3)) per
         launch from a generator seeded once; opacity_loss weighs the mean of (O - alpha)^2.  "random" and opacity_loss > 0 need
-        [n,4] targets.  Without these keywords the optimiser makes exactly the calls it made before them."""
+        [n,4] targets.  Without these keywords the optimiser makes exactly the calls it made before them.
+        depth_loss (>= 0, default off): the weight of the mean over the rays of c (Z - z*)^2 between a ray's expected depth Z (what
+        render() writes as depth) and a depth target z* per ray with weight c, given to accumulate() / train_step() as depth= and
+        depth_weight= (knerf_baked_train_rays_depth).  With 0 the optimiser makes exactly the calls it made before."""
         from .baked_train import BakedFieldOptimizer
         return BakedFieldOptimizer(self, learning_rate_sigma=learning_rate_sigma, learning_rate_sh=learning_rate_sh, beta_1=beta_1,
                                    beta_2=beta_2, epsilon=epsilon, dilation=dilation, step=step, white_background=white_background,

@@ -18,7 +18,7 @@ import ctypes as C
 from .baked import (BakedField, BrickBakedField, _brick_points_device, _brick_slabs, _brick_table_device, _check, _stream, _unpack_words,
                     check_brick, check_lattice_spec, check_table_size, check_threshold, record_bytes)
 from .baked_bricks_train import FLAG_SIGMA, FLAG_SLOT, BrickFieldOptimizer, brick_sigma, train_state
-from .baked_train import TotalVariation, check_optimizer_args, check_stages, is_number
+from .baked_train import TotalVariation, check_optimizer_args, check_stages, is_number, takes_depth_loss
 
 CARRY_ROWS = 1 << 22          # rows whose columns move in one piece when a prune carries the optimiser's state
 
@@ -123,6 +123,7 @@ class BrickGridTrainer(TotalVariation, BrickFieldOptimizer):
     "tv_sh" as well; with both weights 0 a step is BrickFieldOptimizer's, no further launch) and prune(), which re-supports the
     trainer on what the field has become and keeps Adam's state where it can."""
 
+    @takes_depth_loss
     def __init__(self, source, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
                  white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6, loss=None,
                  regularizers=None, background=None, opacity_loss=0.0, target_background=None, background_seed=0):
@@ -182,13 +183,15 @@ class BrickGridTrainer(TotalVariation, BrickFieldOptimizer):
         return {"before": before, "after": self.counts()}
 
 
+@takes_depth_loss
 def grid_trainer(field, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
                  white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6, loss=None,
                  regularizers=None, background=None, opacity_loss=0.0, target_background=None, background_seed=0):
     """A BrickGridTrainer over a COPY of a BrickBakedField's bricks: baked_train.brick_optimizer with the dense optimiser's
     total-variation keywords (tv_sigma, tv_sh: the weights of mean tv_sigma and mean tv_q, both >= 0; tv_epsilon > 0 under the root) and
     prune().  With both weights 0 it trains exactly as brick_optimizer's BrickFieldOptimizer does.  loss, regularizers: the objective, as
-    BakedField.optimizer takes it; background, opacity_loss, target_background, background_seed: the rgba keywords, as there."""
+    BakedField.optimizer takes it; background, opacity_loss, target_background, background_seed: the rgba keywords, as there; depth_loss:
+    the weight of the depth term, as there."""
     _check_brick_field(field, "grid_trainer")
     return BrickGridTrainer(field, learning_rate_sigma=learning_rate_sigma, learning_rate_sh=learning_rate_sh, beta_1=beta_1, beta_2=beta_2,
                             epsilon=epsilon, dilation=dilation, step=step, white_background=white_background, termination=termination,
@@ -210,7 +213,8 @@ def fit_coarse_to_fine_bricks(field, batches, near, far, stages, sigma_threshold
     """baked_train.fit_coarse_to_fine on bricks: for every stage (resolution | None, steps) (baked_train.check_stages) the field is
     resampled onto `resolution` (resample_bricks with sigma_threshold; None keeps the lattice), a trainer is built on it
     (grid_trainer(field, **trainer_kwargs)), fit for `steps` batches -- with prune(sigma_threshold) after every `prune_every` steps that
-    are not the stage's last, when prune_every is given -- and finished (finish(sigma_threshold)).  `batches` is consumed continuously.
+    are not the stage's last, when prune_every is given -- and finished (finish(sigma_threshold)).  `batches` is consumed continuously,
+    and its last_depth, where it has one, reaches every step (depth_loss= among the trainer's keywords).
     sigma_threshold None: every field's own threshold.
 
     Adam's moments are carried across a prune (BrickGridTrainer.prune) and NOT across a resample: a stage starts a fresh trainer.
@@ -218,7 +222,7 @@ def fit_coarse_to_fine_bricks(field, batches, near, far, stages, sigma_threshold
     Returns (the finished BrickBakedField of the last stage, history): history["loss"] (and "tv_sigma", "tv_sh" when a weight is > 0) run
     over all stages; history["stages"] holds one {"resolution", "steps", "n_slots", "n_bricks", "n_records", "prunes"} per stage: the
     counts are the trainer's at the end of the stage, steps those actually run, prunes the list of what every prune() returned."""
-    import itertools
+    from .baked_train import StageBatches
     _check_brick_field(field, "fit_coarse_to_fine_bricks")
     todo = check_stages(stages)
     every = check_prune_every(prune_every)
@@ -233,7 +237,7 @@ def fit_coarse_to_fine_bricks(field, batches, near, far, stages, sigma_threshold
         done, prunes = 0, []
         while True:
             want = steps - done if every is None else min(every, steps - done)
-            hist = opt.fit(itertools.islice(it, want), near, far)
+            hist = opt.fit(StageBatches(batches, it, want), near, far)
             for key, values in hist.items():
                 history.setdefault(key, []).extend(values)
             done += len(hist["loss"])

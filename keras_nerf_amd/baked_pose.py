@@ -285,7 +285,8 @@ def fit_with_poses(opt, pose_opt, batches, near, far, steps=None, field_steps_fi
             break
         moving = k >= int(field_steps_first)
         if opt is not None:
-            losses.append(opt.accumulate(o, d, near, far, target))
+            z, c = getattr(batches, "last_depth", None) or (None, None)       # the field's depth term; the pose gradient stays MSE
+            losses.append(opt.accumulate(o, d, near, far, target, depth=z, depth_weight=c))
             if moving:
                 pose_opt.accumulate(field, o, d, near, far, target, batches.last_view, ray_model=model, **march)
             if getattr(opt, "regularized", False):

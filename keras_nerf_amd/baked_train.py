@@ -24,7 +24,8 @@ import ctypes as C
 
 import numpy as np
 
-from .baked import BakedField, _check, _ray_args, _stream, _unpack_words, check_render_args, check_threshold, n_coefficients
+from .baked import (BakedField, _check, _ray_args, _stream, _unpack_words, check_depth_loss, check_render_args, check_threshold, n_coefficients,
+                    takes_depth_loss)
 
 
 def is_number(v, finite_as=float, integer=False) -> bool:
@@ -129,11 +130,11 @@ TERM_NAMES = ("photometric", "mse", "distortion", "opacity_entropy")
 
 
 def term_means(total, norm):
-    """{name: mean} from the summed columns `total` [4] or [5] of a launch's per-ray terms: photometric and mse are means over rays and
-    channels, distortion, opacity_entropy and (the fifth column) opacity over rays (N = norm)"""
+    """{name: mean} from the summed columns `total` [4], [5] or [6] of a launch's per-ray terms: photometric and mse are means over rays
+    and channels, distortion, opacity_entropy, (the fifth column) opacity and (the sixth) depth over rays (N = norm)"""
     n = float(max(norm, 1))
     means = {"photometric": total[0] / (3.0 * n), "mse": total[1] / (3.0 * n)}
-    for i, name in enumerate((TERM_NAMES + ("opacity",))[2:total.shape[0]], 2):
+    for i, name in enumerate((TERM_NAMES + ("opacity", "depth"))[2:total.shape[0]], 2):
         means[name] = total[i] / n
     return means
 
@@ -149,10 +150,10 @@ def objective_value(obj, terms, norm):
 
 
 def fit_terms(out, rows):
-    """adds the four lists of TERM_NAMES (with "opacity" behind them where the steps were rgba launches) to a fit() dict from the
-    per-step objective_terms() (one device read)"""
+    """adds the four lists of TERM_NAMES (with "opacity" behind them where the steps were rgba launches, and "depth" where they were
+    depth launches) to a fit() dict from the per-step objective_terms() (one device read)"""
     import torch
-    names = TERM_NAMES + (("opacity",) if rows and all("opacity" in r for r in rows) else ())
+    names = TERM_NAMES + tuple(k for k in ("opacity", "depth") if rows and all(k in r for r in rows))
     both = torch.stack([torch.stack([r[k] for k in names]) for r in rows]).cpu() if rows else torch.zeros((0, 4))
     for i, k in enumerate(names):
         out[k] = both[:, i].tolist()
@@ -253,6 +254,39 @@ def rgba_value(obj, rec, terms, norm):
     return loss, means
 
 
+def depth_record(depth_loss, depth, depth_weight, n, device):
+    """The knerf_baked_depth of one launch, or None: depth_loss is 0 (depth tensors are then ignored: the launch is the one made
+    without them).  depth [n]: the rays' depth targets in ray-parameter units; depth_weight [n] >= 0 or None (every ray 1).  ValueError
+    for depth_loss > 0 without depth and for another shape.  The tensors the record points to are kept on it."""
+    from . import _lib
+    from .runtime import _f32, _ptr
+    if depth_loss == 0.0:
+        return None
+    if depth is None:
+        raise ValueError("depth_loss > 0 needs depth: one depth target per ray, in ray-parameter units")
+    z = _f32(depth, device)
+    c = None if depth_weight is None else _f32(depth_weight, device)
+    for name, t in (("depth", z), ("depth_weight", c)):
+        if t is not None and tuple(t.shape) != (n,):
+            raise ValueError(f"{name} must be [{n}], one value per ray; got {tuple(t.shape)}")
+    rec = _lib.KnerfBakedDepth(_ptr(z), _ptr(c), depth_loss)
+    rec._keep = (z, c)
+    return rec
+
+
+def depth_value(obj, rgba, rec, terms, norm):
+    """objective_value for the per-ray terms [n, 6] of a depth launch: the sixth mean is "depth", the unweighted mean of c (Z - z*)^2,
+    and the loss adds the record's weight times it.  obj None: the plain objective; rgba None: no opacity loss."""
+    import torch
+    means = term_means(terms.to(torch.float64).sum(dim=0), norm)
+    loss = means["photometric"] + float(rec.depth) * means["depth"]
+    if rgba is not None:
+        loss = loss + float(rgba.opacity) * means["opacity"]
+    if obj is not None:
+        loss = loss + float(obj.distortion) * means["distortion"] + float(obj.opacity_entropy) * means["opacity_entropy"]
+    return loss, means
+
+
 def bias_corrected_rate(learning_rate: float, beta_1: float, beta_2: float, t: int) -> float:
     """Keras-form Adam: learning_rate sqrt(1 - beta_2^t) / (1 - beta_1^t) in double, t the step being applied (from 1)"""
     return float(learning_rate) * float(np.sqrt(1.0 - float(beta_2) ** t)) / (1.0 - float(beta_1) ** t)
@@ -262,7 +296,7 @@ class GridOptimizer:
     """What the optimisers of a baked field share, whatever its storage (BakedFieldOptimizer here, BrickFieldOptimizer in
     baked_bricks_train.py): the keywords' checks, the gradient launch, Adam's launch, train_step() and fit().  A subclass names its
     entry points and builds its state:
-      _train_rays            the stem of its gradient launch; accumulate() appends "", "_ext" or "_rgba"
+      _train_rays            the stem of its gradient launch; accumulate() appends "", "_ext", "_rgba" or "_depth"
       _check_source(source)  its refusal of a source of the wrong kind
       _check_lanes(sh_degree, lanes_per_ray)   the lane counts its gradient kernel is built for
       _build(source)         the live `field`, `_master` [rows][1 + 3 K] fp32, `n_slots` and its own index tensors
@@ -271,7 +305,9 @@ class GridOptimizer:
 
     _rgba = RgbaTargets()               # the rgba keywords at their defaults: every launch is what it was without them
     _train_rays = None
+    depth_loss = 0.0                    # lambda_z at its default: no launch is a depth launch
 
+    @takes_depth_loss
     def __init__(self, source, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
                  white_background=False, termination=0.0, lanes_per_ray=0, loss=None, regularizers=None, background=None,
                  opacity_loss=0.0, target_background=None, background_seed=0):
@@ -297,7 +333,7 @@ class GridOptimizer:
         pass
 
     # ---- the two launches
-    def accumulate(self, origins, directions, near, far, target, n_total=None, background=None):
+    def accumulate(self, origins, directions, near, far, target, n_total=None, background=None, depth=None, depth_weight=None):
         """knerf_baked_train_rays / knerf_baked_bricks_train_rays: adds the gradient of the batch's mean squared error to the gradient
         rows and returns the loss, a float64 device scalar (the per-ray errors are summed in float64 on the device; nothing waits).
         n_total: the N of the loss 1 / (3 N) sum (out - target)^2 when the batch is one part of several accumulated before apply()
@@ -310,7 +346,11 @@ class GridOptimizer:
         per-call `background` ([n,3], values in [0,1], overrides the keyword): knerf_baked_train_rays_rgba /
         knerf_baked_bricks_train_rays_rgba, the prediction and the photograph composited over the ray's own background and
         opacity_loss x mean (O - alpha)^2 added; objective_terms() then has a fifth mean, "opacity", and last_background is the
-        background tensor of the launch."""
+        background tensor of the launch.
+        With depth_loss > 0: knerf_baked_train_rays_depth / knerf_baked_bricks_train_rays_depth, and depth_loss x the
+        mean over the rays of c (Z - z*)^2 added: Z the ray's expected depth (what render() writes as depth), z* = depth [n] in
+        ray-parameter units, c = depth_weight [n] >= 0 (None: 1; a ray of weight 0 has no depth term whatever its z*);
+        objective_terms() then has a sixth mean, "depth".  ValueError without `depth`.  With depth_loss == 0 both are ignored."""
         import torch
         from . import _lib
         from .runtime import _f32, _ptr
@@ -318,29 +358,39 @@ class GridOptimizer:
         o, d, n, h, (near_t, near0), (far_t, far0) = _ray_args(f, origins, directions, near, far, self.step)
         tg, alpha = self._rgba.split_target(_f32(target, f.device), n)
         rgba = self._rgba.record(alpha, n, f.device, background)
+        zrec = depth_record(self.depth_loss, depth, depth_weight, n, f.device)
         norm = ray_norm(n, n_total)
         sq = torch.empty((n,), device=f.device, dtype=torch.float32)
         route = "_rgba" if rgba is not None else "_ext" if self.objective is not None else ""
+        if zrec is not None:
+            route = "_depth"
         args = [_stream(f.device), C.byref(self._c), _ptr(o), _ptr(d), _ptr(near_t), _ptr(far_t), near0, far0, _ptr(tg), n, norm, h,
                 self.termination, march_flags(self.white_background, self.lanes_per_ray), _ptr(sq)]
         if route:
-            terms = torch.zeros((n, 5 if rgba is not None else 4), device=f.device, dtype=torch.float32)
+            terms = torch.zeros((n, 6 if zrec is not None else 5 if rgba is not None else 4), device=f.device, dtype=torch.float32)
             args += [C.byref(self.objective) if self.objective is not None else None, _ptr(terms)]
-            if rgba is not None:
-                args.append(C.byref(rgba))
+            if rgba is not None or zrec is not None:
+                args.append(C.byref(rgba) if rgba is not None else None)
+            if zrec is not None:
+                args.append(C.byref(zrec))
         if n:
             _check(getattr(_lib.load(), self._train_rays + route)(*args), self._train_rays + route)
         if not route:
             return sq.to(torch.float64).sum() / (3.0 * max(norm, 1))
-        loss, self._terms = rgba_value(self.objective, rgba, terms, norm) if rgba is not None else \
-            objective_value(self.objective, terms, norm)
+        if zrec is not None:
+            loss, self._terms = depth_value(self.objective, rgba, zrec, terms, norm)
+        elif rgba is not None:
+            loss, self._terms = rgba_value(self.objective, rgba, terms, norm)
+        else:
+            loss, self._terms = objective_value(self.objective, terms, norm)
         return loss
 
     def objective_terms(self):
         """{"photometric", "mse", "distortion", "opacity_entropy"}: the four means of the last accumulate() as float64 device scalars
         (photometric: the mean of rho over rays and channels; mse: of the squared difference; the other two: mean D and mean H over
-        the rays, unweighted); after an rgba launch also "opacity", the mean of (O - alpha)^2 over the rays, unweighted.  None before
-        any accumulate(), and always under the plain objective without the rgba keywords."""
+        the rays, unweighted); after an rgba launch also "opacity", the mean of (O - alpha)^2 over the rays, unweighted; after a depth
+        launch "opacity" and "depth", the mean of c (Z - z*)^2 over the rays, unweighted.  None before any accumulate(), and always
+        under the plain objective without the rgba and depth keywords."""
         return None if self._terms is None else dict(self._terms)
 
     @property
@@ -361,10 +411,11 @@ class GridOptimizer:
             bias_corrected_rate(self.learning_rate_sh, self.beta_1, self.beta_2, t), self.beta_1, self.beta_2, self.epsilon), name)
         self.iterations = t
 
-    def train_step(self, origins, directions, near, far, target):
+    def train_step(self, origins, directions, near, far, target, depth=None, depth_weight=None):
         """accumulate, regularize (only where the class has the total-variation regulariser and a weight is > 0; its return value is
-        kept in last_regularizer), apply; returns the batch's loss before the step (float64 device scalar, the data term alone)"""
-        loss = self.accumulate(origins, directions, near, far, target)
+        kept in last_regularizer), apply; returns the batch's loss before the step (float64 device scalar, the data term alone).
+        depth, depth_weight: the rays' depth targets and weights, as accumulate() takes them"""
+        loss = self.accumulate(origins, directions, near, far, target, depth=depth, depth_weight=depth_weight)
         if getattr(self, "regularized", False):
             self.last_regularizer = self.regularize()
         self.apply()
@@ -375,7 +426,9 @@ class GridOptimizer:
         not used: the baked march places its own samples), at most `steps` of them.  {"loss": [...]}: read from the device once, after
         the last step.  With a total-variation weight > 0 the dict also holds "tv_sigma" and "tv_sh": regularize()'s two means per
         step; with an objective that is not the plain one also "photometric", "mse", "distortion" and "opacity_entropy":
-        objective_terms() per step, and "opacity" behind them where the steps were rgba launches."""
+        objective_terms() per step, "opacity" behind them where the steps were rgba launches and "depth" where they were depth
+        launches.  Where `batches` has a `last_depth` (RayBatchDataset.set_depth: (z [n], c [n] | None) of the batch just drawn) it
+        is read after each batch is drawn and passed on as the step's depth targets and weights."""
         import torch
         check_steps(steps)
         regularized = getattr(self, "regularized", False)
@@ -383,7 +436,8 @@ class GridOptimizer:
         for k, (target, (o, d, _t)) in enumerate(batches):
             if steps is not None and k >= int(steps):
                 break
-            losses.append(self.train_step(o, d, near, far, target))
+            z, c = getattr(batches, "last_depth", None) or (None, None)
+            losses.append(self.train_step(o, d, near, far, target, depth=z, depth_weight=c))
             if regularized:
                 tvs.append(torch.stack(self.last_regularizer))
             if self._terms is not None:
@@ -439,6 +493,7 @@ class BakedFieldOptimizer(TotalVariation, GridOptimizer):
 
     _train_rays = "knerf_baked_train_rays"
 
+    @takes_depth_loss
     def __init__(self, source, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
                  white_background=False, termination=0.0, lanes_per_ray=0, tv_sigma=0.0, tv_sh=0.0, tv_epsilon=1e-6, loss=None,
                  regularizers=None, background=None, opacity_loss=0.0, target_background=None, background_seed=0):
@@ -527,6 +582,7 @@ class BakedFieldOptimizer(TotalVariation, GridOptimizer):
         return BakedField(records, words, f.resolution, f.bounds, f.sh_degree, thr)
 
 
+@takes_depth_loss
 def brick_optimizer(field, learning_rate_sigma, learning_rate_sh, beta_1=0.9, beta_2=0.999, epsilon=1e-7, dilation=0, step=None,
                     white_background=False, termination=0.0, lanes_per_ray=0, loss=None, regularizers=None, background=None,
                     opacity_loss=0.0, target_background=None, background_seed=0):
@@ -535,7 +591,8 @@ def brick_optimizer(field, learning_rate_sigma, learning_rate_sh, beta_1=0.9, be
     finish() gives a BrickBakedField).  There is no total-variation regulariser here: tv_sigma, tv_sh and tv_epsilon belong to the
     dense optimiser and, on bricks, to baked_bricks_grow.grid_trainer, beside resample_bricks and fit_coarse_to_fine_bricks.
     loss, regularizers: the objective, as BakedField.optimizer takes it (knerf_baked_bricks_train_rays_ext); background, opacity_loss,
-    target_background, background_seed: the rgba keywords, as there (knerf_baked_bricks_train_rays_rgba)."""
+    target_background, background_seed: the rgba keywords, as there (knerf_baked_bricks_train_rays_rgba); depth_loss: the weight of the
+    depth term, as there (knerf_baked_bricks_train_rays_depth)."""
     from .baked_bricks_train import BrickFieldOptimizer
     from .baked_quant import QuantizedBrickField
     if isinstance(field, QuantizedBrickField):
@@ -573,18 +630,34 @@ def check_stages(stages):
     return [(r, int(s)) for r, s in out]
 
 
+class StageBatches:
+    """At most `steps` further batches of an iterator `it` over `batches`, for one stage's fit(): what itertools.islice gives, with the
+    source's last_depth (RayBatchDataset.set_depth) still readable after each batch is drawn"""
+
+    def __init__(self, batches, it, steps):
+        self._batches, self._it, self._steps = batches, it, int(steps)
+
+    @property
+    def last_depth(self):
+        return getattr(self._batches, "last_depth", None)
+
+    def __iter__(self):
+        import itertools
+        return itertools.islice(self._it, self._steps)
+
+
 def fit_coarse_to_fine(field, batches, near, far, stages, **optimizer_kwargs):
     """Coarse-to-fine optimisation of a baked field: for every stage (resolution | None, steps) in turn the field is resampled onto
     `resolution` (BakedField.resample; None keeps the lattice), an optimiser is built on it (field.optimizer(**optimizer_kwargs):
     learning rates, dilation, march, total-variation and objective (loss=, regularizers=) keywords), fit for `steps` batches and finished (finish()).  `batches` is
-    consumed continuously: a stage goes on where the one before stopped, and no batch is dropped in between.
+    consumed continuously: a stage goes on where the one before stopped, and no batch is dropped in between.  Its last_depth, where it
+    has one (RayBatchDataset.set_depth), reaches every step: with depth_loss= among the keywords the stages are depth-supervised.
 
     Adam's moments are NOT carried across stages.  A resample changes the lattice, the support and with them the set of slots, so
     every stage gets a new slot set and a fresh optimiser whose moments start at zero and whose bias correction starts at t = 1.
 
     Returns (the finished field of the last stage, history): history["loss"] (and "tv_sigma", "tv_sh" when a weight is > 0, and the four
     lists of objective_terms() under an objective that is not the plain one) run over all stages, history["stages"] holds one {"resolution", "steps", "n_slots"} per stage (steps: those actually run)."""
-    import itertools
     todo = check_stages(stages)
     it = iter(batches)
     history = {"loss": [], "stages": []}
@@ -592,7 +665,7 @@ def fit_coarse_to_fine(field, batches, near, far, stages, **optimizer_kwargs):
         if resolution is not None:
             field = field.resample(resolution)
         opt = field.optimizer(**optimizer_kwargs)
-        hist = opt.fit(itertools.islice(it, steps), near, far)
+        hist = opt.fit(StageBatches(batches, it, steps), near, far)
         for key, values in hist.items():
             history.setdefault(key, []).extend(values)
         history["stages"].append({"resolution": tuple(field.resolution), "steps": len(hist["loss"]), "n_slots": opt.n_slots})

@@ -34,6 +34,11 @@
 //                             otherwise, the target recomposited over it with the photograph's alpha, and the opacity loss
 //                             (lambda_o / N)(O - alpha)^2, a function of O alone that enters r_j and the total like the entropy term.
 //                             Every line of it stands under `if constexpr (RGBA)`; tests/baked_rgba_reference.py restates it in fp64.
+//                             Args::kDepth (Depth<TrainArgs>, Depth<BrickTrainArgs>): the rgba kernel with depth supervision
+//                             (knerf_baked_train_rays_depth) -- the first march also sums Z = sum w_j t_j, the render
+//                             kernel's depth bit for bit, and the term (lambda_z / N) c (Z - z*)^2, linear in the weights through Z,
+//                             enters r_j as zeta t_j and the total as zeta Z, zeta = (lambda_z / N) 2 c (Z - z*).  Every line of it
+//                             stands under `if constexpr (DEPTH)`; tests/baked_depth_reference.py restates it in fp64.
 //   Gradient rows: fp32 [n_slots][1 + 3 K], sigma first, then [k][c]: the columns of a record.  Every lane of a group holds the whole
 //   basis and the same dL/dr and dL/dsigma, so any lane can form any column: lane `sub` adds the columns sub, sub + G, ... of a
 //   corner's row, so that ONE atomic instruction of the group adds G consecutive floats (the memory side works in 64-byte requests;
@@ -52,7 +57,7 @@ namespace baked_train {
 using namespace baked;
 
 struct TrainArgs {
-    static constexpr bool kBrick = false, kExt = false, kRgba = false;
+    static constexpr bool kBrick = false, kExt = false, kRgba = false, kDepth = false;
     const uint4* rec;
     const unsigned* bits;
     int R[3];
@@ -69,7 +74,7 @@ struct TrainArgs {
 };
 
 struct BrickTrainArgs {
-    static constexpr bool kBrick = true, kExt = false, kRgba = false;
+    static constexpr bool kBrick = true, kExt = false, kRgba = false, kDepth = false;
     const uint4* rec;
     const int* brick_of;
     const unsigned* bits;
@@ -94,7 +99,7 @@ struct Objective {
     float huber_delta;
     float hscale;                                   // 1 / (3 N): g_c = rho'(d_c) hscale (for mse the bits of diff * gscale)
     float wd, we;                                   // lambda_d / N, lambda_e / N
-    float* terms;                                   // [n][4] ([n][5] under kRgba) or NULL
+    float* terms;                                   // [n][4] ([n][5] under kRgba, [n][6] under kDepth) or NULL
 };
 template <class Base>
 struct Ext : Base {
@@ -117,6 +122,20 @@ struct Rgba : Ext<Base> {
     RgbaArgs rgba;
 };
 
+// Depth supervision (knerf_baked_train_rays_depth): the rgba argument struct with the depth record behind it.
+// Args::kDepth is the third compile-time switch; every line it adds stands under `if constexpr (Args::kDepth)` (DEPTH), so the plain, the
+// extended and the rgba instantiations are the text they were.  One depth instantiation per <DEG, G, storage>.
+struct DepthArgs {
+    const float* target;                            // [n]: z*, in ray-parameter units (what baked_render_kernel writes as depth)
+    const float* weight;                            // [n] >= 0 or NULL: every ray 1
+    float wz;                                       // lambda_z / N
+};
+template <class Base>
+struct Depth : Rgba<Base> {
+    static constexpr bool kDepth = true;
+    DepthArgs depth;
+};
+
 // kExt: what the regularisers keep per ray, with m_j = (i_j - first) delta and the exclusive prefixes W_k = sum_{j<k} w_j (the march's own
 // opa) and M_k = sum_{j<k} w_j m_j.  First march: M ends as MT, S1 = sum w_k (m_k W_k - M_k), S2 = sum w_k^2, so D = 2 S1 + delta S2 / 3.
 // Second march: M runs again as the prefix, run = sum_{i<=j} w_i r_i, r_j = wd dD/dw_j + re the regularisers' share of A_j; the later
@@ -125,6 +144,7 @@ struct RegState {
     float M, S1, S2, run;
     int first;                                      // index of the ray's first fetched sample, -1: none yet
     float mt, wd, re, total;                        // MT, lambda_d / N, (lambda_e / N) dH/dw, sum_i w_i r_i
+    float Z, zeta;                                  // kDepth: Z = sum_j w_j t_j of the first march; zeta = (lambda_z / N) 2 c (Z - z*)
 };
 
 // what the second march needs from the first: g = dL/dout (already gated by the output clamp) and the totals
@@ -133,7 +153,7 @@ struct Totals {
     float b3[3];                                    // kRgba: the ray's background per channel, used where bg is otherwise
 };
 
-// One march of one ray over the samples [i, i1): the loop of baked_render_kernel without depth and statistics.  BWD = false: img / opa
+// One march of one ray over the samples [i, i1): the loop of baked_render_kernel without statistics (and without depth but under kDepth).  BWD = false: img / opa
 // end as C / O.  BWD = true: the same arithmetic again (img / opa are then the prefix sums), and per sample the gradient is added.
 template <int DEG, int G, bool BWD, class Args>
 __device__ __forceinline__ void march(const Args& a, const float (&o3)[3], const float (&d3)[3], float near, int i, int i1,
@@ -144,7 +164,7 @@ __device__ __forceinline__ void march(const Args& a, const float (&o3)[3], const
                                       const float (&gy)[(1 + 3 * n_coeff(DEG) + G - 1) / G][3], float (&img)[3], float& opa, const Totals& tt,
                                       [[maybe_unused]] RegState& rs) {
     constexpr int K = n_coeff(DEG), NCH = rec_bytes(DEG) / 16, CPL = (NCH + G - 1) / G, W = 1 + 3 * K, NI = (W + G - 1) / G;
-    constexpr bool BRICK = Args::kBrick, EXT = Args::kExt, RGBA = Args::kRgba;
+    constexpr bool BRICK = Args::kBrick, EXT = Args::kExt, RGBA = Args::kRgba, DEPTH = Args::kDepth;
     [[maybe_unused]] const long long sy = a.R[2], sx = (long long)a.R[1] * a.R[2];     // dense: the lattice's strides
     const int cyc = a.R[1] - 1, czc = a.R[2] - 1;
     [[maybe_unused]] const int L = brick_log2(a), inm = (1 << L) - 1;
@@ -270,6 +290,9 @@ __device__ __forceinline__ void march(const Args& a, const float (&o3)[3], const
                 rs.M = Mk + w * mk;
             }
             img[0] = img[0] + w * col[0]; img[1] = img[1] + w * col[1]; img[2] = img[2] + w * col[2];
+            if constexpr (DEPTH) {
+                if constexpr (!BWD) rs.Z = rs.Z + w * t;            // the render kernel's dep = dep + w * t
+            }
             opa = opa + w;
             T = T * (1.f - alpha);
             if constexpr (BWD) {
@@ -290,7 +313,9 @@ __device__ __forceinline__ void march(const Args& a, const float (&o3)[3], const
                 if constexpr (EXT) {
                     // the regularisers are functions of the weights alone: they pass neither clamp.  The photometric share of
                     // `later` above stays what it is (exactly 0 at the last sample); this share carries the rounding of `total`
-                    const float r = rs.wd * (2.f * (2.f * mk * Wk - 2.f * Mk + rs.mt - mk * tt.opa) + (2.f / 3.f) * delta * w) + rs.re;
+                    float r = rs.wd * (2.f * (2.f * mk * Wk - 2.f * Mk + rs.mt - mk * tt.opa) + (2.f / 3.f) * delta * w) + rs.re;
+                    // the depth term is linear in the weights: its share of A_j is zeta t_j (t carries no gradient)
+                    if constexpr (DEPTH) r = r + rs.zeta * t;
                     rs.run = rs.run + w * r;
                     A = A + r;
                     later = later + (rs.total - rs.run);
@@ -333,7 +358,7 @@ __device__ __forceinline__ void march(const Args& a, const float (&o3)[3], const
 template <int DEG, int G, class Args>
 __global__ __launch_bounds__(kBlock) void baked_train_rays_kernel(Args a) {
     constexpr int K = n_coeff(DEG), NCH = rec_bytes(DEG) / 16, CPL = (NCH + G - 1) / G;
-    constexpr bool EXT = Args::kExt, RGBA = Args::kRgba;
+    constexpr bool EXT = Args::kExt, RGBA = Args::kRgba, DEPTH = Args::kDepth;
     static_assert(G == 1 || G == 2 || G == 4, "a group is a lane, a pair or a quad");
     const long long gid = (long long)blockIdx.x * kBlock + threadIdx.x;
     const long long ray = gid / G;
@@ -482,12 +507,21 @@ __global__ __launch_bounds__(kBlock) void baked_train_rays_kernel(Args a) {
         const float O = tt.opa, ac = fminf(fmaxf(O, 1e-4f), 1.f - 1e-4f);
         const float H = -ac * logf(ac) - (1.f - ac) * logf(1.f - ac);
         const float dH = (O >= 1e-4f && O <= 1.f - 1e-4f) ? logf((1.f - ac) / ac) : 0.f;
+        // DEPTH: c (Z - z*)^2 and zeta.  A ray of weight 0 has neither, whatever its z* holds (a select: sparse maps are mostly empty)
+        [[maybe_unused]] float cz = 1.f, zterm = 0.f;
+        if constexpr (DEPTH) {
+            if (a.depth.weight) cz = a.depth.weight[ray];
+            const float dz = rs.Z - a.depth.target[ray];
+            zterm = cz == 0.f ? 0.f : cz * (dz * dz);
+            rs.zeta = cz == 0.f ? 0.f : a.depth.wz * (2.f * (cz * dz));
+        }
         if (sub == 0) {
             if (a.sq_err) a.sq_err[ray] = sq;
             if (ob.terms) {
-                float* tr = ob.terms + ray * (RGBA ? 5 : 4);
+                float* tr = ob.terms + ray * (DEPTH ? 6 : RGBA ? 5 : 4);
                 tr[0] = (rv[0] + rv[1]) + rv[2]; tr[1] = sq; tr[2] = D; tr[3] = H;
                 if constexpr (RGBA) tr[4] = (O - al) * (O - al);
+                if constexpr (DEPTH) tr[5] = zterm;
             }
         }
         rs.mt = rs.M; rs.wd = ob.wd; rs.re = ob.we * dH;
@@ -496,10 +530,13 @@ __global__ __launch_bounds__(kBlock) void baked_train_rays_kernel(Args a) {
             if (a.rgba.wo > 0.f) rs.re = rs.re + a.rgba.wo * (2.f * (O - al));
         }
         rs.total = ob.wd * (2.f * D) + rs.re * O;
+        if constexpr (DEPTH) rs.total = rs.total + rs.zeta * rs.Z;
         rs.M = 0.f; rs.run = 0.f;
         // a ray whose g is 0 on every channel still has the regularisers' gradient once it fetched a sample
         if constexpr (RGBA) any = any || ((ob.wd > 0.f || ob.we > 0.f || a.rgba.wo > 0.f) && rs.first >= 0);
         else any = any || ((ob.wd > 0.f || ob.we > 0.f) && rs.first >= 0);
+        // ... and so has the depth term, which passes neither clamp, on a ray whose weight is > 0
+        if constexpr (DEPTH) any = any || (cz > 0.f && rs.first >= 0);
     }
     if (!any) return;                                       // the same on every lane of the group
     float img[3], opa;
@@ -533,6 +570,18 @@ hipError_t launch_rays(int deg, int lanes, const Args& a, const Objective* obj, 
     static_cast<Args&>(e) = a;
     e.obj = *obj;
     e.rgba = *rg;
+    return launch_rays(deg, lanes, e, s);
+}
+
+// ... or with a depth record the depth one (it always carries an objective and an rgba record: the defaults where the caller gave none)
+template <class Args>
+hipError_t launch_rays(int deg, int lanes, const Args& a, const Objective* obj, const RgbaArgs* rg, const DepthArgs* dp, hipStream_t s) {
+    if (!dp) return launch_rays(deg, lanes, a, obj, rg, s);
+    Depth<Args> e{};
+    static_cast<Args&>(e) = a;
+    e.obj = *obj;
+    e.rgba = *rg;
+    e.depth = *dp;
     return launch_rays(deg, lanes, e, s);
 }
 
@@ -572,6 +621,30 @@ static bool check_rgba(const knerf_baked_rgba* r, const knerf_objective* objecti
     out.background = r->background; out.alpha = r->alpha; out.stored = r->stored_background;
     out.wo = (float)((double)r->opacity / N);
     if (!objective) {
+        knerf_objective mse{};
+        mse.loss_kind = KNERF_LOSS_MSE;
+        bool plain = true;
+        return check_objective(&mse, n_rays, n_norm, terms, plain, obj);
+    }
+    return true;
+}
+
+// the depth record of the _depth entry points.  false: KNERF_ERR_INVALID.  off: NULL or weight 0 (the call is then the _rgba call).
+// Otherwise `out` is what the depth kernel takes, `obj` is filled even for the plain objective and `rg` holds the rgba contract's
+// defaults where there is no rgba record (no background but the flag's, every alpha 1, no opacity loss)
+static bool check_depth(const knerf_baked_depth* z, const knerf_objective* objective, bool none, uint64_t n_rays, uint64_t n_norm,
+                        float* terms, bool& off, DepthArgs& out, RgbaArgs& rg, Objective& obj) {
+    off = true;
+    if (!z) return true;
+    if (!(z->depth >= 0.f) || !std::isfinite(z->depth)) return false;
+    if (z->depth > 0.f && !z->target) return false;
+    off = z->depth == 0.f;
+    if (off) return true;
+    const double N = (double)(n_norm ? n_norm : (n_rays ? n_rays : 1));
+    out.target = z->target; out.weight = z->weight;
+    out.wz = (float)((double)z->depth / N);
+    if (none) rg = RgbaArgs{};
+    if (!objective && none) {
         knerf_objective mse{};
         mse.loss_kind = KNERF_LOSS_MSE;
         bool plain = true;
@@ -718,15 +791,17 @@ using namespace knerf;
 static int train_rays(void* stream, const knerf_baked_train* train, const float* origins, const float* directions, const float* near,
                       const float* far, float near_all, float far_all, const float* target, uint64_t n_rays, uint64_t n_norm, float step,
                       float termination, int flags, float* sq_err, const knerf_objective* objective, float* terms,
-                      const knerf_baked_rgba* rgba = nullptr) {
+                      const knerf_baked_rgba* rgba = nullptr, const knerf_baked_depth* depth = nullptr) {
     unsigned long long points = 0;
     int lanes = 0;
-    bool plain = true, none = true;
+    bool plain = true, none = true, off = true;
     baked_train::Objective obj{};
     baked_train::RgbaArgs rg{};
+    baked_train::DepthArgs dp{};
     if (!baked_train::check_state(train, points)) return KNERF_ERR_INVALID;
     if (!baked_train::check_objective(objective, n_rays, n_norm, terms, plain, obj)) return KNERF_ERR_INVALID;
     if (!baked_train::check_rgba(rgba, objective, n_rays, n_norm, terms, none, rg, obj)) return KNERF_ERR_INVALID;
+    if (!baked_train::check_depth(depth, objective, none, n_rays, n_norm, terms, off, dp, rg, obj)) return KNERF_ERR_INVALID;
     const knerf_baked_field* field = &train->field;
     const int deg = field->sh_degree;
     if (!baked_train::check_train_rays(deg, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination,
@@ -740,7 +815,8 @@ static int train_rays(void* stream, const knerf_baked_train* train, const float*
     a.slot_of = train->slot_of; a.n_slots = (long long)train->n_slots;
     baked_train::set_rays(a, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination, flags,
                           train->grad, sq_err);
-    return baked_train::launch_rays(deg, lanes, a, plain && none ? nullptr : &obj, none ? nullptr : &rg, (hipStream_t)stream) == hipSuccess
+    return baked_train::launch_rays(deg, lanes, a, plain && none && off ? nullptr : &obj, none && off ? nullptr : &rg, off ? nullptr : &dp,
+                                    (hipStream_t)stream) == hipSuccess
                ? KNERF_OK : KNERF_ERR_HIP;
 }
 
@@ -750,6 +826,15 @@ extern "C" int knerf_baked_train_rays_rgba(void* stream, const knerf_baked_train
                                            const knerf_objective* objective, float* terms, const knerf_baked_rgba* rgba) {
     return train_rays(stream, train, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination, flags,
                       sq_err, objective, terms, rgba);
+}
+
+extern "C" int knerf_baked_train_rays_depth(void* stream, const knerf_baked_train* train, const float* origins, const float* directions,
+                                            const float* near, const float* far, float near_all, float far_all, const float* target,
+                                            uint64_t n_rays, uint64_t n_norm, float step, float termination, int flags, float* sq_err,
+                                            const knerf_objective* objective, float* terms, const knerf_baked_rgba* rgba,
+                                            const knerf_baked_depth* depth) {
+    return train_rays(stream, train, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination, flags,
+                      sq_err, objective, terms, rgba, depth);
 }
 
 extern "C" int knerf_baked_train_rays(void* stream, const knerf_baked_train* train, const float* origins, const float* directions,
@@ -790,16 +875,18 @@ extern "C" int knerf_baked_train_apply(void* stream, const knerf_baked_train* tr
 static int bricks_train_rays(void* stream, const knerf_baked_bricks_train* train, const float* origins, const float* directions,
                              const float* near, const float* far, float near_all, float far_all, const float* target, uint64_t n_rays,
                              uint64_t n_norm, float step, float termination, int flags, float* sq_err, const knerf_objective* objective,
-                             float* terms, const knerf_baked_rgba* rgba = nullptr) {
+                             float* terms, const knerf_baked_rgba* rgba = nullptr, const knerf_baked_depth* depth = nullptr) {
     int B[3], lanes = 0;
     unsigned long long n_records = 0;
-    bool plain = true, none = true;
+    bool plain = true, none = true, off = true;
     baked_train::Objective obj{};
     baked_train::RgbaArgs rg{};
+    baked_train::DepthArgs dp{};
     baked_train::BrickTrainArgs a{};
     if (!baked_train::check_state(train, B, a.scale, n_records)) return KNERF_ERR_INVALID;
     if (!baked_train::check_objective(objective, n_rays, n_norm, terms, plain, obj)) return KNERF_ERR_INVALID;
     if (!baked_train::check_rgba(rgba, objective, n_rays, n_norm, terms, none, rg, obj)) return KNERF_ERR_INVALID;
+    if (!baked_train::check_depth(depth, objective, none, n_rays, n_norm, terms, off, dp, rg, obj)) return KNERF_ERR_INVALID;
     const knerf_baked_bricks* field = &train->field;
     const int deg = field->sh_degree;
     // every lane variant of knerf_baked_train_rays exists here too: each builds without scratch (DESIGN.md 2.23 has hipcc's counts)
@@ -812,7 +899,8 @@ static int bricks_train_rays(void* stream, const knerf_baked_bricks_train* train
     a.L = field->brick_log2; a.By = B[1]; a.Bz = B[2]; a.n_bricks = (long long)field->n_bricks;
     baked_train::set_rays(a, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination, flags,
                           train->grad, sq_err);
-    return baked_train::launch_rays(deg, lanes, a, plain && none ? nullptr : &obj, none ? nullptr : &rg, (hipStream_t)stream) == hipSuccess
+    return baked_train::launch_rays(deg, lanes, a, plain && none && off ? nullptr : &obj, none && off ? nullptr : &rg, off ? nullptr : &dp,
+                                    (hipStream_t)stream) == hipSuccess
                ? KNERF_OK : KNERF_ERR_HIP;
 }
 
@@ -823,6 +911,15 @@ extern "C" int knerf_baked_bricks_train_rays_rgba(void* stream, const knerf_bake
                                                   float* terms, const knerf_baked_rgba* rgba) {
     return bricks_train_rays(stream, train, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination,
                              flags, sq_err, objective, terms, rgba);
+}
+
+extern "C" int knerf_baked_bricks_train_rays_depth(void* stream, const knerf_baked_bricks_train* train, const float* origins,
+                                                   const float* directions, const float* near, const float* far, float near_all,
+                                                   float far_all, const float* target, uint64_t n_rays, uint64_t n_norm, float step,
+                                                   float termination, int flags, float* sq_err, const knerf_objective* objective,
+                                                   float* terms, const knerf_baked_rgba* rgba, const knerf_baked_depth* depth) {
+    return bricks_train_rays(stream, train, origins, directions, near, far, near_all, far_all, target, n_rays, n_norm, step, termination,
+                             flags, sq_err, objective, terms, rgba, depth);
 }
 
 extern "C" int knerf_baked_bricks_train_rays(void* stream, const knerf_baked_bricks_train* train, const float* origins,

@@ -110,6 +110,22 @@ def read_point_tracks(path: str) -> list:
     return out
 
 
+def read_points(path: str):
+    """points3D.txt -> (xyz float64 [P,3], error float64 [P], tracks: per point the int array of the ids of its observing images)"""
+    xyz, err, tracks = [], [], []
+    with open(path) as f:
+        for line in f:
+            w = line.split()
+            if not w or w[0].startswith("#"):
+                continue
+            if len(w) < 8:
+                raise ValueError(f"{path}: expected POINT3D_ID X Y Z R G B ERROR TRACK[], got {line.rstrip()!r}")
+            xyz.append([float(v) for v in w[1:4]])
+            err.append(float(w[7]))
+            tracks.append(np.array([int(v) for v in w[8::2]], np.int64))
+    return np.array(xyz, np.float64).reshape(-1, 3), np.array(err, np.float64), tracks
+
+
 class ColmapDatasetLoader:
     def __init__(self, data_dir: str, model_dir: str = "sparse/0", images_dir: str = "images", holdout: int = 8, bd_factor: float = None,
                  white_background: bool = False, **kwargs):
@@ -120,6 +136,7 @@ class ColmapDatasetLoader:
         if bd_factor is not None and not bd_factor > 0:
             raise ValueError(f"bd_factor = {bd_factor}: expected a positive number or None")
         self.poses = self.bounds = self.camera = self.image_paths = None
+        self.image_ids, self.scale, self._subsets = None, 1.0, {}
 
     def _load_model(self, image_width: int, image_height: int):
         """sets image_paths, poses [V,4,4] float64, bounds [V,2] or None and the per-view camera at the requested size"""
@@ -166,6 +183,8 @@ class ColmapDatasetLoader:
             sc = 1.0 / (bounds.min() * self.bd_factor)
             poses[:, :3, 3] *= sc
             bounds = bounds * sc
+            self.scale = float(sc)
+        self.image_ids = [im[0] for im in images]
         self.image_paths = [os.path.join(self.data_dir, self.images_dir, im[4]) for im in images]
         self.poses, self.bounds = poses, bounds
         self.camera = CameraModel(model, fx, fy, cx, cy, np.array(dist, np.float64).reshape(len(images), n_coeff), pixel_offset=0.5)
@@ -193,5 +212,24 @@ class ColmapDatasetLoader:
                                      n_sample=n_sample, seed=1000 + k + 4096 * rank, camera=camera)     # replicas jitter differently
             out.append(RayImageDataset([self.image_paths[i] for i in idx], [self.poses[i].astype(np.float32) for i in idx],
                                        image_loader, factory, batch_size, seed=k))
+            self._subsets[subset] = (out[-1], [self.image_ids[i] for i in idx])
             logging.info(f"Loaded {subset} dataset. {len(idx)} images, {self.camera.model} cameras.")
         return out
+
+    def sparse_depth(self, subset: str = "train"):
+        """(depth [V,H,W], weight [V,H,W]) float32 on the device for the views of a split of the last load_dataset(): the points of
+        points3D.txt as depth targets for the grid optimisers' depth_loss= keyword, in their unit (data/depth.py sparse_depth_maps:
+        every point lands on the nearest pixel of each image of its track, the nearest wins, weight exp(-(err / mean err)^2); pixels
+        without a point have weight 0).  bd_factor's scale applies to the points as it does to the poses.  Feed them to
+        ray_batches(n, depth=, depth_weight=).  ValueError before load_dataset(), for an unknown split and without points3D.txt."""
+        from .depth import sparse_depth_maps
+        if subset not in self._subsets:
+            raise ValueError(f"subset = {subset!r}: load_dataset() first, then one of {sorted(self._subsets) or ['train', 'val', 'test']}")
+        pts = os.path.join(self.data_dir, self.model_dir, "points3D.txt")
+        if not os.path.exists(pts):
+            raise ValueError(f"{pts} does not exist: sparse depth needs the model's points3D.txt")
+        xyz, err, tracks = read_points(pts)
+        if not len(err):
+            raise ValueError(f"{pts} lists no point")
+        dataset, ids = self._subsets[subset]
+        return sparse_depth_maps(xyz * self.scale, err, tracks, dataset, ids)

@@ -128,14 +128,19 @@ class RayImageDataset:
                                seed=seed, limit=self._limit if limit is None else limit, rank=self._rank, world=self._world,
                                device_cache_gb=self.device_cache_gb, _shared=self._shared)
 
-    def ray_batches(self, rays_per_step, seed=0, steps_per_epoch=None, alpha=False):
+    def ray_batches(self, rays_per_step, seed=0, steps_per_epoch=None, alpha=False, depth=None, depth_weight=None):
         """the same data as batches of `rays_per_step` rays drawn at random over all pixels of all images, one permutation of the
         pixels per epoch (raybatch.RayBatchDataset; needs the whole dataset within `device_cache_gb`).  Data parallel:
         `rays_per_step` is the GLOBAL count, every rank draws its 1/world slice of the same permutation.
         alpha=True: the targets are [n,4], the images' alpha as the fourth column (what the grid optimisers' background= and
-        opacity_loss= keywords train against); without it the batches and the launches are what they were."""
+        opacity_loss= keywords train against); without it the batches and the launches are what they were.
+        depth, depth_weight: [V,H,W] maps of depth targets and weights (RayBatchDataset.set_depth; what the grid optimisers'
+        depth_loss= keyword trains against); without them the batches and the launches are what they were."""
         from .raybatch import RayBatchDataset
-        return RayBatchDataset(self, rays_per_step, seed=seed, steps_per_epoch=steps_per_epoch, alpha=alpha)
+        batches = RayBatchDataset(self, rays_per_step, seed=seed, steps_per_epoch=steps_per_epoch, alpha=alpha)
+        if depth is not None or depth_weight is not None:
+            batches.set_depth(depth, depth_weight)
+        return batches
 
     def _image(self, i):
         if i not in self._cache:

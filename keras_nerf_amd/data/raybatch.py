@@ -98,7 +98,10 @@ class RayBatchDataset:
     steps continue through the permutation and start the next one when fewer than rays_per_step positions are left.
 
     alpha=True: the target is [n,4], the images' alpha behind the colour (gathered from the resident images by the flat pixel index the
-    draw returns), for the grid optimisers' RGBA training; o, d, t and the colour are what they are without it."""
+    draw returns), for the grid optimisers' RGBA training; o, d, t and the colour are what they are without it.
+
+    set_depth(depth, weight): per-pixel depth targets for the grid optimisers' depth_loss= keyword; every batch then leaves the drawn
+    rays' targets and weights in `last_depth`, gathered by the same flat pixel index."""
 
     def __init__(self, images, rays_per_step: int, seed: int = 0, steps_per_epoch: int = None, alpha: bool = False):
         self.alpha = bool(alpha)
@@ -116,6 +119,7 @@ class RayBatchDataset:
         self._perm, self._step, self._drawn = 0, 0, 0          # permutation in use, steps taken from it, batches drawn in all
         self._rg, self.last_draw = None, None
         self._cameras, self.last_view = None, None             # set_cameras: who says where the cameras stand; the rays' views
+        self._depth, self.last_depth = None, None              # set_depth: the depth maps (and weights); the rays' (z, c)
 
     def set_cameras(self, provider):
         """provider: None (default: the dataset's own camera matrices, and the batches are what they always were) or a callable
@@ -127,6 +131,35 @@ class RayBatchDataset:
         self._cameras = provider
         if provider is None:
             self.last_view = None
+
+    def set_depth(self, depth, weight=None):
+        """depth: None (default: no flat index is requested, last_depth is None and the batches are what they always were) or a
+        [V,H,W] float32 map of depth targets at the dataset's image size, in ray-parameter units (data/depth.py converts z-depth,
+        distances and structure-from-motion points); weight: None or a [V,H,W] float32 map of weights >= 0 (0: the pixel has no
+        target).  Arrays or tensors; they are kept on the device and count against the dataset's device_cache_gb beside the images.
+        Every draw then leaves last_depth = (z [n], c [n] | None), the maps at the drawn rays' pixels (GridOptimizer.fit reads it)."""
+        if depth is None:
+            if weight is not None:
+                raise ValueError("a depth weight without depth")
+            self._depth, self.last_depth = None, None
+            return
+        want = (self.n_views, self._rows, self._cols)
+        maps = []
+        for name, m in (("depth", depth), ("weight", weight)):
+            if m is None:
+                maps.append(None)
+                continue
+            if tuple(m.shape) != want:
+                raise ValueError(f"{name} must be {list(want)} (views, rows, columns of the dataset's images), got {list(m.shape)}")
+            maps.append(m)
+        need = self.n_pixels * 4 * (4 + sum(m is not None for m in maps))
+        if need > self._images.device_cache_gb * 1e9:
+            raise ValueError(f"depth maps beside the images need {need / 1e9:.2f} GB on the device: more than device_cache_gb = "
+                             f"{self._images.device_cache_gb}")
+        import torch
+        to_dev = lambda m: None if m is None else (m if isinstance(m, torch.Tensor) else torch.as_tensor(np.asarray(m, np.float32))).to(
+            "cuda", torch.float32).contiguous()
+        self._depth = (to_dev(maps[0]), to_dev(maps[1]))
 
     def ray_model(self):
         """the struct knerf_ray_model the batches are drawn with, None for the plain pinhole rays (the ray generator's own answer)"""
@@ -197,14 +230,16 @@ class RayBatchDataset:
                 stream = self._drawn * world + rank
                 self._drawn += 1
                 self.last_draw = (perm, first, n)              # what the batch just yielded holds: positions [first, first + n) of `perm`
-                if self._cameras is None and not self.alpha:
+                index = None
+                if self._cameras is None and not self.alpha and self._depth is None:
                     o, d, t, target = draw_ray_batch(dev, cams, rg.focal_length, rg.near, rg.far, rg.n_sample, self.seed, perm, first, n,
                                                      noise_stream=stream, **extra)
                 elif self._cameras is None:
                     import torch
                     o, d, t, target, index = draw_ray_batch(dev, cams, rg.focal_length, rg.near, rg.far, rg.n_sample, self.seed, perm,
                                                             first, n, noise_stream=stream, want_index=True, **extra)
-                    target = torch.cat([target, dev.reshape(-1, 4)[index.to(torch.int64), 3:4]], dim=1)
+                    if self.alpha:
+                        target = torch.cat([target, dev.reshape(-1, 4)[index.to(torch.int64), 3:4]], dim=1)
                 else:
                     import torch
                     now = self._cameras()
@@ -216,5 +251,11 @@ class RayBatchDataset:
                     self.last_view = torch.div(index, self._rows * self._cols, rounding_mode="floor").to(torch.int32)
                     if self.alpha:
                         target = torch.cat([target, dev.reshape(-1, 4)[index.to(torch.int64), 3:4]], dim=1)
+                if self._depth is not None:                    # the maps at the drawn pixels
+                    at = index.to("cuda").long()
+                    z, c = self._depth
+                    self.last_depth = (z.reshape(-1)[at], None if c is None else c.reshape(-1)[at])
+                else:
+                    self.last_depth = None
                 yield target, (o, d, t)
         return gen()
